@@ -164,6 +164,39 @@ def make_trainer(cfg, dtype, device, rank, world, grad_sync_factory, n_batches=4
 
 
 SETUP_STEPS = 6
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, limit=DUMP_LIMIT_BYTES):
+    """Write the arrays CoTrainer._run_step returned (sup_<m>, jsd, adv, preds_<m>, unlab_probs_<m>) as <directory>/<name>.npy in
+    float32, so that two builds run with the same arguments can be compared output for output.  When they exceed `limit` bytes
+    in all, every array is cut to its share of the limit by a fixed sample of its flattened elements (torch.randperm seeded
+    with 0, indices sorted); manifest.json records each array's full shape and whether it was sampled."""
+    import numpy as np
+    arrays = {}
+    for key in sorted(out):
+        vals = out[key] if isinstance(out[key], (list, tuple)) else [out[key]]
+        for m, v in enumerate(vals):
+            name = f"{key}_{m}" if isinstance(out[key], (list, tuple)) else key
+            t = v.detach() if torch.is_tensor(v) else torch.tensor(float(v))
+            arrays[name] = t.to(device="cpu", dtype=torch.float32).contiguous()
+    total = sum(a.numel() for a in arrays.values())
+    budget = (limit - (1 << 20)) // 4             # (room for the .npy headers)
+    os.makedirs(directory, exist_ok=True)
+    manifest = {}
+    for name, a in arrays.items():
+        keep = a.numel() if total <= budget else max(1, a.numel() * budget // total)
+        flat = a.flatten()
+        if keep < a.numel():
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            flat = flat[idx]
+            data = flat.numpy()
+        else:
+            data = a.numpy()
+        np.save(os.path.join(directory, name + ".npy"), data)
+        manifest[name] = {"shape": list(a.shape), "dtype": "float32", "sampled": keep < a.numel(), "elements": int(data.size)}
+    with open(os.path.join(directory, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
 
 
 def host_cores() -> int:
@@ -297,7 +330,7 @@ class DryLegs:
         return {"igemm": {"ms": 0.0, "launches": 0}} if record else None
 
 
-def measure(args, tr, one_step, legs, rank, world, ddp_on, meters_leg=None, operand_leg=None, enter_event_leg=None):
+def measure(args, tr, one_step, legs, rank, world, ddp_on, meters_leg=None, operand_leg=None, enter_event_leg=None, last_step=None):
     """W warm-up steps, the timed regions, and every leg behind them.  ONE rule keeps `--gpus N` from hanging: a leg that runs
     `one_step` (which issues the gradient all-reduces when N > 1) is executed by EVERY rank; what is rank-conditional is only
     who records or prints.  (Round 4 ran the HIP-event leg on rank 0 alone while the other ranks went on to the barrier:
@@ -333,6 +366,8 @@ def measure(args, tr, one_step, legs, rank, world, ddp_on, meters_leg=None, oper
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             t_rep = float(tt.item())
         regions.append(t_rep)
+    if last_step is not None:           # the timed path's last outputs, read before the legs below run more steps over them
+        last_step(out)
     res = {"regions": regions, "elapsed": sorted(regions)[len(regions) // 2], "out": out, "exchange": None, "meters_ms": None,
            "operand_stats": None, "prof": None, "clock": None,
            # (the timed steps' layout: the legs below switch to one stream, where the adversarial step recomputes the FGSM generator's encoder)
@@ -478,6 +513,8 @@ def main():
     ap.add_argument("--dry-timeout", type=int, default=180, help="--dry-launch: seconds before a stuck gloo collective fails the run")
     ap.add_argument("--dry-break-rank0-leg", action="store_true",
                     help="--dry-launch self-test: run the per-launch event leg on rank 0 only (the round-4 defect); the run must FAIL")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (CoTrainer._run_step's arrays) as DIR/<name>.npy, float32, <= 64 MB in all")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -599,8 +636,12 @@ def main():
         tr.use_hip_graph = False      # event records are host calls around each launch
         tr.model_streams = False      # per-kernel durations are taken with one kernel on the device at a time
 
+    def last_step(out):
+        if args.dump_outputs and rank == 0:
+            dump_outputs(out, args.dump_outputs)
+
     m = measure(args, tr, one_step, HipLegs(device), rank, world, ddp_on, meters_leg=meters_leg,
-                operand_leg=operand_leg, enter_event_leg=enter_event_leg)
+                operand_leg=operand_leg, enter_event_leg=enter_event_leg, last_step=last_step)
     regions, elapsed, out = m["regions"], m["elapsed"], m["out"]
     exchange, meters_ms, operand_stats, prof = m["exchange"], m["meters_ms"], m["operand_stats"], m["prof"]
     clock = m["clock"]

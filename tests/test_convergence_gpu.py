@@ -12,6 +12,7 @@ and the foreground Dice of the last 20 steps must sit within a stated band of th
 import json
 import os
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -28,7 +29,7 @@ from helpers import FakeLoader, blob_batches  # noqa: E402
 DEV = "cuda:0"
 
 
-def run_curves(arch, H, B, C, steps, n_batches, dtype, adv=False, tmp="/tmp/dct_conv"):
+def run_curves(arch, H, B, C, steps, n_batches, dtype, adv=False, tmp=None):
     """-> dict(hip=..., ref=...) of per-step supervised losses (mean over the models) and foreground 2-D Dice."""
     from dct_amd.loss import get_loss_fn
     from dct_amd.metrics import DiceMeter
@@ -48,7 +49,7 @@ def run_curves(arch, H, B, C, steps, n_batches, dtype, adv=False, tmp="/tmp/dct_
     lab = [FakeLoader(blob_batches(201 + i, n_batches, B, H, C), B) for i in range(2)]
     unl = FakeLoader(blob_batches(301, n_batches, B, H, C), B)
     crit = {"sup": get_loss_fn("cross_entropy"), "jsd": get_loss_fn("jsd"), "adv": get_loss_fn("jsd")}
-    os.makedirs(tmp, exist_ok=True)
+    tmp = str(tmp) if tmp is not None else tempfile.mkdtemp(prefix="dct_conv_")
     tr = CoTrainer(segs, lab, unl, unl, crit, max_epoch=1, save_dir=tmp, device=DEV, axises=list(range(1, C)),
                    cot_scheduler_dict={"name": "ConstantScheduler", "begin_epoch": 0, "max_value": 0.5},
                    adv_scheduler_dict={"name": "ConstantScheduler", "begin_epoch": 0, "max_value": 0.05},
@@ -91,14 +92,14 @@ def _check(c, tail=20, loss_band=0.25, dice_band=0.10):
         assert hd[-tail:].mean() > hd[:10].mean() + 0.05, (hd[:10].mean(), hd[-tail:].mean())
 
 
-def test_enet_bf16_trains_like_the_fp32_oracle():
+def test_enet_bf16_trains_like_the_fp32_oracle(tmp_path):
     """2 x Enet, 96 x 96, C = 3, bs 4 + 4, CE + JSD, 200 steps over 10 distinct batches."""
-    _check(run_curves("enet", 96, 4, 3, 200, 10, torch.bfloat16))
+    _check(run_curves("enet", 96, 4, 3, 200, 10, torch.bfloat16, tmp=tmp_path))
 
 
-def test_unet_bf16_trains_like_the_fp32_oracle():
+def test_unet_bf16_trains_like_the_fp32_oracle(tmp_path):
     """2 x UNet, 176 x 176, C = 3, bs 1 + 1, CE + JSD, 60 steps over 6 distinct batches."""
-    _check(run_curves("unet", 176, 1, 3, 60, 6, torch.bfloat16), tail=15)
+    _check(run_curves("unet", 176, 1, 3, 60, 6, torch.bfloat16, tmp=tmp_path), tail=15)
 
 
 if __name__ == "__main__":

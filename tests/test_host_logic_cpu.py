@@ -386,3 +386,33 @@ def test_refused_capture_filter_recognises_the_runtime_messages():
         assert _is_refused_capture(RuntimeError(msg)), msg
     for msg in ("dct_amd: dct_conv2d failed (DCT_ERR_BAD_ARG)", "shape mismatch", "dct_amd: dct_enet_conv failed (DCT_ERR_LAUNCH)"):
         assert not _is_refused_capture(RuntimeError(msg)), msg
+
+
+def test_bench_dump_outputs_writes_the_step_arrays(tmp_path):
+    """bench.py --dump-outputs: every array of the step's result as float32 .npy; above the byte limit a seeded sample that is the same
+    from run to run and keeps the dump under the limit."""
+    import json
+    import bench
+    g = torch.Generator().manual_seed(3)
+    out = dict(sup=[torch.rand((), generator=g), torch.rand((), generator=g)], jsd=torch.rand((), generator=g), adv=0,
+               preds=[torch.rand(2, 3, 64, 64, generator=g).bfloat16() for _ in range(2)],
+               unlab_probs=[torch.rand(4, 3, 64, 64, generator=g) for _ in range(2)])
+    full = tmp_path / "full"
+    bench.dump_outputs(out, str(full))
+    names = sorted(p.name for p in full.glob("*.npy"))
+    assert names == sorted(f"{n}.npy" for n in ["adv", "jsd", "sup_0", "sup_1", "preds_0", "preds_1", "unlab_probs_0", "unlab_probs_1"])
+    p0 = np.load(full / "preds_0.npy")
+    assert p0.dtype == np.float32 and p0.shape == (2, 3, 64, 64)
+    assert np.array_equal(p0, out["preds"][0].float().numpy())
+    assert float(np.load(full / "adv.npy")) == 0.0 and float(np.load(full / "jsd.npy")) == float(out["jsd"])
+    limit = (1 << 20) + 64 * 1024                   # room for 16 K float32 elements of the ~74 K returned
+    cut = [tmp_path / "cut_a", tmp_path / "cut_b"]
+    for d in cut:
+        bench.dump_outputs(out, str(d), limit=limit)
+    assert sum(p.stat().st_size for p in cut[0].glob("*.npy")) <= limit
+    man = json.loads((cut[0] / "manifest.json").read_text())
+    assert man["unlab_probs_1"]["sampled"] and man["unlab_probs_1"]["shape"] == [4, 3, 64, 64]
+    u = np.load(cut[0] / "unlab_probs_1.npy")
+    assert u.size == man["unlab_probs_1"]["elements"] < 4 * 3 * 64 * 64 and np.isin(u, out["unlab_probs"][1].numpy()).all()
+    for p in cut[0].glob("*.npy"):
+        assert np.array_equal(np.load(p), np.load(cut[1] / p.name))
