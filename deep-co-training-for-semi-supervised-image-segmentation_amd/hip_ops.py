@@ -633,7 +633,9 @@ def adam_flat(p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, 
 
 def adam_flat_dev(p, g, m, v, state, table, beta1, beta2, eps, weight_decay, bf16_shadow=None, grad_scale=1.0):
     """Adam with {step count, lr, table base, table length} in the float64[4] device tensor ``state`` and the
-    host-computed {step_size, bc2_sqrt} pairs in the float32 device tensor ``table`` (dct_adam_flat_dev)."""
+    host-computed {1 - beta1^t, sqrt(1 - beta2^t)} pairs for t = base + 1 ... base + length in the float64 device tensor ``table``
+    (the kernel divides lr by the first in double; past the table it forms both itself).  The kernel adds 1 to state[0] first
+    (dct_adam_flat_dev)."""
     call("dct_adam_flat_dev", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(state), ptr(table), float(beta1), float(beta2),
          float(eps), float(weight_decay), float(grad_scale), ptr(bf16_shadow), stream())
     return p

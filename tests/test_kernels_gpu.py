@@ -656,8 +656,19 @@ def test_conv2d_wgrad_unpools_on_load_bit_identical(ops, B, C, H, W, Cq):
 def test_ce_step_is_bit_identical_to_forward_then_backward(ops, C, accumulate, ignored):
     """dct_ce_step (the backward kernel folds the forward kernel's block partials itself) against dct_ce_fwd + dct_ce_bwd: loss, count and
     every gradient bit."""
+    _ce_step_bit_identical(ops, 5 * 131 * 67, C, accumulate, ignored)
+
+
+# above the 1024-block cap of the forward grid (every thread of it walks several pixels) and the 8192-block cap of the backward's;
+# 524,291 pixels: cfg2's labelled batch (C = 4) and cfg4's (C = 2) plus a ragged tail
+@pytest.mark.parametrize("P,C,accumulate,ignored", [(524291, 4, False, False), (524291, 2, True, True), (262145, 8, False, True),
+                                                    (2097153, 3, True, False)])
+def test_ce_step_is_bit_identical_above_the_grid_caps(ops, P, C, accumulate, ignored):
+    _ce_step_bit_identical(ops, P, C, accumulate, ignored)
+
+
+def _ce_step_bit_identical(ops, P, C, accumulate, ignored):
     g = torch.Generator().manual_seed(71)
-    P = 5 * 131 * 67
     logits = (3 * torch.randn(P, C, generator=g)).to(DEV)
     t = torch.randint(0, C, (P,), generator=g)
     if ignored:
@@ -678,8 +689,20 @@ def test_ce_step_is_bit_identical_to_forward_then_backward(ops, C, accumulate, i
 def test_jsd_step_in_one_pass_is_bit_identical(ops, S, C, accumulate):
     """dct_jsd_logits_step (mean JSD + the S softmax maps + the S logit gradients in one pass) against dct_jsd_logits_fwd, dct_softmax_fwd
     and dct_jsd_logits_bwd: every output bit -- the value because the pass keeps the forward kernel's grid and summation order."""
+    _jsd_step_bit_identical(ops, 3 * 97 * 101, S, C, accumulate)
+
+
+# Above the 1024-block cap, where the two-model pass takes two pixels per trip (`two` in jsd_step_kernel): 263,144 pixels -- some threads
+# take the second pixel, some do not; 524,291 -- cfg2's shape (S = 2, C = 4) and cfg4's (S = 2, C = 2): every thread takes it, plus a
+# ragged tail.  Also the one-pixel-per-trip forms (S = 3, S = 8) at the caps.
+@pytest.mark.parametrize("P,S,C,accumulate", [(263144, 2, 4, True), (524291, 2, 4, False), (524291, 2, 2, True), (524291, 1, 3, False),
+                                              (262145, 8, 8, True), (2097153, 3, 2, False)])
+def test_jsd_step_in_one_pass_is_bit_identical_above_the_grid_cap(ops, P, S, C, accumulate):
+    _jsd_step_bit_identical(ops, P, S, C, accumulate)
+
+
+def _jsd_step_bit_identical(ops, P, S, C, accumulate):
     g = torch.Generator().manual_seed(61)
-    P = 3 * 97 * 101
     logits = [torch.randn(P, C, generator=g).to(DEV) for _ in range(S)]
     gscale = torch.tensor([0.37], device=DEV)
     old = [torch.randn(P, C, generator=g).to(DEV) for _ in range(S)]
@@ -688,7 +711,7 @@ def test_jsd_step_in_one_pass_is_bit_identical(ops, S, C, accumulate):
     want_g = ops.jsd_logits_bwd(logits, C, [o.clone() for o in old], gscale=gscale, gmul=4.0, accumulate=accumulate)
     got_g = [o.clone() for o in old]
     got_v, got_p = ops.jsd_logits_step(logits, C, got_g, True, gscale=gscale, gmul=4.0, accumulate=accumulate)
-    assert torch.equal(got_v, want_v) and float(got_v) > 0
+    assert torch.equal(got_v, want_v) and (float(got_v) > 0 if S > 1 else float(got_v) == 0.0)   # one model: nothing to disagree with
     for a, b in zip(got_p, want_p):
         assert torch.equal(a, b)
     for a, b in zip(got_g, want_g):
