@@ -71,8 +71,9 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(BnP p, double* partial) 
 #pragma unroll
     for (int i = 0; i < 8; ++i) { sc[i] = p.scale[cv * 8 + i]; sh[i] = p.shift[cv * 8 + i]; mu[i] = p.mean[cv * 8 + i]; is[i] = p.invstd[cv * 8 + i]; }
   }
-  // fp32 running sums over short runs (<= 64 pixels), flushed into doubles: ATen's CPU BatchNorm accumulates in double-ish
-  // cascades; the parity tests hold mean / var to 1e-6
+  // fp32 running sums over short runs (<= 64 pixels), flushed into doubles: a sum is off by at most 64 U sum|terms| (U = 2^-24),
+  // the one-pass variance by that over count plus 2 |mean| times the mean's error (tests/test_bn_kernels_scale_gpu.py holds the
+  // kernels to these bounds against float64 references)
   double d0[8], d1[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) { d0[i] = 0.0; d1[i] = 0.0; }
