@@ -210,13 +210,6 @@ class UNet(nn.Module):
         self.batch_bias_grads = True         # the four up-convolutions' bias gradients in one launch pair per gradient bucket
         self.batch_skip_resize = True        # the four skip connections' bilinear resizes in one launch, in front of the centre
         self.fuse_drop_pool = True           # the fourth level's dropout + max-pool in one launch (the dropped tensor is never written)
-        self.unpool_max_level = 3            # the deepest level that does
-        self.unpool_on_load = False          # levels 1..unpool_max_level: the un-pooled gradient of an encoder block is never written -- its two consumers
-                                             # expand {pooled gradient + routing codes} while they stage (dct_conv_desc.unpool_codes).  Built, bit-identical,
-                                             # and OFF: on the captured cfg2 step level 1 alone is 0.5 % slower and levels 1-3 are 1.2 % slower than the
-                                             # un-pooling launches (profiles/r05_unpool_on_load_per_level.txt, r05_knob_sweep.txt) although 0.3 GB of
-                                             # writes and 0.7 GB of reads per step are gone: the expansion's ~40 vector instructions per thread and
-                                             # K-step land in the filter-row weight gradient's issue-bound loop (+10 % on that kernel)
         self._wgrad_stream = None
 
     # ------------------------------------------------------------------------------ weights
@@ -578,44 +571,25 @@ class UNet(nn.Module):
 
         stem_fused = [False]
 
-        def conv_bwd(conv, x_in, dy, dx_out, mask=None, mask_channels=0, mask_scale=1.0, accumulate=False, stem=None, unpool=None):
+        def conv_bwd(conv, x_in, dy, dx_out, mask=None, mask_channels=0, mask_scale=1.0, accumulate=False, stem=None):
             """dy: grad wrt the conv's pre-activation output (already ReLU-masked).  ``stem``: (x, dw, db, accumulate) -- try to take
-            the stem's weight gradient from this data gradient's output tile (dx_out is then not written; stem_fused[0] tells).
-            ``unpool`` = (codes, H, W): dy is the gradient at the POOLED tensor; the kernels expand it to the un-pooled gradient while
-            they stage where they can, else it is un-pooled into a buffer here, once, for whoever still needs it."""
-            def materialised():
-                codes, uh, uw = unpool
-                full = torch.empty(dy.shape[0], uh, uw, dy.shape[3], dtype=dt, device=dev)
-                return K.maxpool_bwd(None, dy, full, relu_mask=True, scale=1.0, codes=codes)
+            the stem's weight gradient from this data gradient's output tile (dx_out is then not written; stem_fused[0] tells)."""
             if need_dw:
                 with on_side(dy, x_in):
                     if dt == torch.bfloat16:     # bias gradient rides along in the weight-gradient launch
-                        try:
-                            K.conv2d_wgrad(dy, x_in, self._gw(conv), accumulate=gacc, db=self._gb(conv), unpool=unpool)
-                        except K.UnpoolOnLoadUnsupported:
-                            dy, unpool = materialised(), None
-                            K.conv2d_wgrad(dy, x_in, self._gw(conv), accumulate=gacc, db=self._gb(conv))
+                        K.conv2d_wgrad(dy, x_in, self._gw(conv), accumulate=gacc, db=self._gb(conv))
                     else:
-                        if unpool is not None:
-                            dy, unpool = materialised(), None
                         K.conv2d_wgrad(dy, x_in, self._gw(conv), accumulate=gacc)
                         K.bias_grad(dy, self._gb(conv), accumulate=gacc)
             if dx_out is not None:
                 mb = gate_bits.get(id(mask)) if mask is not None else None
                 if stem is not None and mb is not None:
                     try:
-                        K.conv2d(dy, P[id(conv)]["dgrad"], None, dx_out, pad_h=2, pad_w=2, mask=mask, mask_bits=mb, stem=stem, unpool=unpool)
+                        K.conv2d(dy, P[id(conv)]["dgrad"], None, dx_out, pad_h=2, pad_w=2, mask=mask, mask_bits=mb, stem=stem)
                         stem_fused[0] = True
                         return dx_out
                     except K.StemFusionUnsupported:
                         pass                     # (the stem's weight gradient then runs as its own launch)
-                if unpool is not None:
-                    try:
-                        K.conv2d(dy, P[id(conv)]["dgrad"], None, dx_out, pad_h=2, pad_w=2, mask=mask, mask_channels=mask_channels,
-                                 mask_scale=mask_scale, accumulate=accumulate, mask_bits=mb, unpool=unpool)
-                        return dx_out
-                    except K.UnpoolOnLoadUnsupported:
-                        dy, unpool = materialised(), None
                 K.conv2d(dy, P[id(conv)]["dgrad"], None, dx_out, pad_h=2, pad_w=2, mask=mask,
                          mask_channels=mask_channels, mask_scale=mask_scale, accumulate=accumulate, mask_bits=mb)
             return dx_out
@@ -672,15 +646,11 @@ class UNet(nn.Module):
         dp: Dict[int, torch.Tensor] = {}
         skip_g: Dict[int, torch.Tensor] = {}
         skip_fused = bool(self.fuse_skip_grad and all(A.get(f"pc{k}") is not None for k in (1, 2, 3, 4)))
-        # Levels whose un-pooled gradient is expanded on load (no un-pooling launch to gather the skip gradient in): the bilinear
-        # backward of the skip connection is written to dp and the next block's data gradient accumulates onto it.
-        up_levels = {k for k in (1, 2, 3) if self.unpool_on_load and k <= int(self.unpool_max_level) and dt == torch.bfloat16 and A.get(f"pc{k}") is not None and
-                     isinstance(A[f"d{k}"], _ShapeOf) and self._debug is None}
         for lvl, co in ((2, 64), (3, 128), (4, 256)):
             ca, _, cb, _, ct = self._roles[f"enc{lvl}"]
             ea, eb = A[f"e{lvl}a"], A[f"e{lvl}b"]
             p = A[f"p{lvl - 1}"]
-            if skip_fused and (lvl - 1) not in up_levels:
+            if skip_fused:
                 skip_g[lvl - 1] = dcat[..., co:]          # gathered by level (lvl - 1)'s un-pooling (K.maxpool_bwd(..., skip=))
             else:
                 dp[lvl - 1] = K.bilinear_bwd(dcat[..., co:], new_like(p))
@@ -714,19 +684,15 @@ class UNet(nn.Module):
         for lvl in (4, 3, 2, 1):
             ca, _, cb, _ = self._roles[f"dec{lvl}"]
             a, d = A[f"a{lvl}"], A[f"d{lvl}"]
-            unpool = None
-            if lvl in up_levels:
-                dd, unpool = dp[lvl], (A[f"pc{lvl}"], d.shape[1], d.shape[2])      # the pooled gradient stands for the un-pooled one
-            else:
-                dd = K.maxpool_bwd(d, dp[lvl], new_like(d), relu_mask=True, scale=ds if lvl == 4 else 1.0, codes=A.get(f"pc{lvl}"),
-                                   skip=skip_g.get(lvl))
+            dd = K.maxpool_bwd(d, dp[lvl], new_like(d), relu_mask=True, scale=ds if lvl == 4 else 1.0, codes=A.get(f"pc{lvl}"),
+                               skip=skip_g.get(lvl))
             stem = None
             if (lvl == 1 and need_dw and not need_dx and self.fuse_stem_wgrad and dt == torch.bfloat16 and side is None and
                     A["bn"].get("a1") is None and self._debug is None):
                 stem = (A["x"], self._gw(ca), self._gb(ca), gacc)       # the stem's dy has no other reader: see dct_conv_desc.stem_x
-            da = bn_back(f"a{lvl}", conv_bwd(cb, a, dd, new_like(a), mask=a, stem=stem, unpool=unpool))
+            da = bn_back(f"a{lvl}", conv_bwd(cb, a, dd, new_like(a), mask=a, stem=stem))
             if lvl > 1:
-                summed = not skip_fused or (lvl - 1) in up_levels          # dp[lvl - 1] already holds the skip connection's share
+                summed = not skip_fused          # dp[lvl - 1] already holds the skip connection's share
                 if not summed:
                     dp[lvl - 1] = new_like(A[f"p{lvl - 1}"])
                 conv_bwd(ca, A[f"p{lvl - 1}"], da, dp[lvl - 1], accumulate=summed)

@@ -571,13 +571,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void igemm2_kernel(IgemmPar
 // Variants of this tile that were measured and removed: a four-slot ring of 32-channel weight half-stages with
 // counted vmcnt and raw barriers (-15 %: twice the barriers for the same MFMAs), four waves of 64 x 64 instead of eight of
 // 32 x 64 (-8 %), three unrolled taps per loop trip (-13 %), an XCD-aware tile order (level), amdgpu_waves_per_eu(4) (-1 %).
-// UNPOOL (round 5): the input is an encoder block's un-pooled gradient that nobody has written: x = the gradient at the pooled tensor,
-// up_codes = the pooling's routing codes.  The 10 x 18 halo of a slice is 5 x 9 whole windows (patches start at multiples of
-// (8, 16) and the data gradient's padding is 2: even coordinates); an item = one window x 8 channels -- 16 bytes of gradient and 8
-// code bytes through registers, four 16-byte LDS writes -- takes the place of the halo's LDS-DMA pieces.  A window outside the pooled
-// tensor stages zeros (the data gradient's padding).  8.6 KB per halo instead of 22.5 KB, and the 130 MB un-pooled tensor of the
-// first level (with its producer launch) is gone.
-template <int BN, int NWM, int NWN, int ABUFS, bool UNPOOL>
+template <int BN, int NWM, int NWN, int ABUFS>
 __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, int tiles_x, int tiles_y) {
   constexpr int NW = NWM * NWN;
   constexpr int TH = 8, TW = 16, BM = TH * TW, HW = TW + 2, HROWS = (TH + 2) * HW;   // 180 halo rows of 128 B
@@ -624,49 +618,6 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
       if (piece < APIECES) {
         const char* src = aoff[i] >= 0 ? reinterpret_cast<const char*>(xb + aoff[i] + c0) : zero;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(buf + piece * 1024), 16, 0, 0);
-      }
-    }
-  };
-  // UNPOOL: this thread's windows of the halo.  The pooled gradient is DENSE (host-checked), so the element offset of an item's eight
-  // gradients is also the byte offset of its eight codes: one register per item (-1: no item, -2: an item that stages zeros).
-  constexpr int UITEMS = UNPOOL ? (45 * 8 + NW * 64 - 1) / (NW * 64) : 1;
-  int ugoff[UITEMS];
-  uint4 ug[UITEMS];
-  uint2 uc[UITEMS];
-  if constexpr (UNPOOL) {
-#pragma unroll
-    for (int i = 0; i < UITEMS; ++i) {
-      const int id = tid + i * NW * 64;
-      const int w = id >> 3, wy = w / 9, wx = w - wy * 9;
-      ugoff[i] = -1;
-      if (id < 45 * 8) {
-        const int py = (y0 - p.pad_h) / 2 + wy, px = (x0 - p.pad_w) / 2 + wx;       // (exact: even numerators)
-        ugoff[i] = ((unsigned)py < (unsigned)p.up_Hp && (unsigned)px < (unsigned)p.up_Wp)
-                       ? (int)(((long long)(img * p.up_Hp + py) * p.up_Wp + px) * p.Cin + (id & 7) * 8) : -2;
-      }
-    }
-  }
-  auto unpool_load = [&](int c0) {
-#pragma unroll
-    for (int i = 0; i < UITEMS; ++i) {
-      ug[i] = make_uint4(0u, 0u, 0u, 0u); uc[i] = make_uint2(0x08080808u, 0x08080808u);       // code 8: routed nowhere
-      if (ugoff[i] >= 0) {
-        ug[i] = *reinterpret_cast<const uint4*>(xb + ugoff[i] + c0);
-        uc[i] = *reinterpret_cast<const uint2*>(p.up_codes + ugoff[i] + c0);
-      }
-    }
-  };
-  auto unpool_store = [&](char* buf) {
-#pragma unroll
-    for (int i = 0; i < UITEMS; ++i) {
-      if (ugoff[i] == -1) continue;
-      const int id = tid + i * NW * 64;
-      const int w = id >> 3, c8 = id & 7, wy = w / 9, wx = w - wy * 9;
-      const int row0 = (2 * wy) * HW + 2 * wx;                   // halo row of the window's first position
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int row = row0 + (k >> 1) * HW + (k & 1);
-        *reinterpret_cast<uint4*>(buf + row * 128 + ((c8 ^ ((row >> 1) & 7)) * 16)) = dct_unpool_chunk8(ug[i], uc[i], (unsigned)k);
       }
     }
   };
@@ -721,11 +672,10 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
       }
     }
   }
-  if constexpr (UNPOOL) unpool_load(0); else stageA(Abuf, 0);
+  stageA(Abuf, 0);
   stageB(Bbuf, 0, 0);
   float* biasL = reinterpret_cast<float*>(smem + ABUFS * A_BYTES + 2 * B_BYTES);   // bias -> LDS now: no memory round trip in the epilogue
   if (tid < BN) biasL[tid] = p.bias ? p.bias[n0 + tid] : 0.f;
-  if constexpr (UNPOOL) unpool_store(Abuf);
   __syncthreads();
   // Fragment addresses with as little vector ALU work as the layout allows.  Weights: a lane's two sub-step addresses are
   // constants of the lane (+ the stage, a scalar); the wave's 16-row blocks are reached through the read's immediate offset.
@@ -746,12 +696,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
       const int sx = t % 3, rr = t / 3;
       if (t < 8) stageB(Bbuf + (bb ^ 1) * B_BYTES, t + 1, c * 64);
       else if (c + 1 < nch) stageB(Bbuf + (bb ^ 1) * B_BYTES, 0, (c + 1) * 64);
-      if constexpr (UNPOOL) {
-        // the next slice's windows: loads in flight over taps 3..8, expanded into the free halo stage in front of the slice's last barrier
-        if (ABUFS == 2 && t == 3 && c + 1 < nch) unpool_load((c + 1) * 64);
-      } else {
-        if (ABUFS == 2 && t == 0 && c + 1 < nch) stageA(Abuf + (ab ^ 1) * A_BYTES, (c + 1) * 64);
-      }
+      if (ABUFS == 2 && t == 0 && c + 1 < nch) stageA(Abuf + (ab ^ 1) * A_BYTES, (c + 1) * 64);
       if (wave_live) {
       const unsigned wa0 = Wb0 + bb * B_BYTES, wa1 = wa0 ^ 64u;
       unsigned rho_t = rho0;
@@ -780,9 +725,6 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
           for (int j = 0; j < PXB; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[k2][i], b[k2][j], acc[i][j], 0, 0, 0);
       }
-      }
-      if constexpr (UNPOOL) {
-        if (ABUFS == 2 && t == 8 && c + 1 < nch) unpool_store(Abuf + (ab ^ 1) * A_BYTES);
       }
       __syncthreads();
       bb ^= 1;
@@ -1325,22 +1267,17 @@ static void launch_v2(const IgemmParams& p, dim3 grid, hipStream_t st) {
   else launch_v2_k<BM, BN, WM, WN, BOUNDS, false>(p, grid, st);
 }
 
-template <int BN, int NWN, int ABUFS, bool UNPOOL>
-static void launch_v3u(const IgemmParams& p, int tiles_x, int tiles_y, int images, hipStream_t st) {
+template <int BN, int NWN, int ABUFS>
+static void launch_v3(const IgemmParams& p, int tiles_x, int tiles_y, int images, hipStream_t st) {
   constexpr size_t lds = ABUFS * (size_t)(23 * 1024) + 2 * (size_t)BN * 128 + (size_t)BN * 4;   // halo stage(s), two weight stages, bias
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm3m_kernel<BN, 4, NWN, ABUFS, UNPOOL>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm3m_kernel<BN, 4, NWN, ABUFS>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
   const dim3 grid((unsigned)(images * tiles_y * tiles_x), p.N / BN, 1);
-  DCT_LAUNCH_FAM(DCT_FAM_IGEMM3M, DCT_PROF_IGEMM, (igemm3m_kernel<BN, 4, NWN, ABUFS, UNPOOL>), grid, dim3(4 * NWN * 64), lds, st, p, tiles_x, tiles_y);
-}
-template <int BN, int NWN, int ABUFS>
-static void launch_v3(const IgemmParams& p, int tiles_x, int tiles_y, int images, hipStream_t st) {
-  if (p.up_codes) launch_v3u<BN, NWN, ABUFS, true>(p, tiles_x, tiles_y, images, st);
-  else launch_v3u<BN, NWN, ABUFS, false>(p, tiles_x, tiles_y, images, st);
+  DCT_LAUNCH_FAM(DCT_FAM_IGEMM3M, DCT_PROF_IGEMM, (igemm3m_kernel<BN, 4, NWN, ABUFS>), grid, dim3(4 * NWN * 64), lds, st, p, tiles_x, tiles_y);
 }
 
 // Packed-rows shared-halo kernel (igemm3p_kernel) for small images: geometry and split over channel slices.
@@ -1457,17 +1394,8 @@ void dct_relu_bits_launch(const void* y_bf16, unsigned char* bits, long long chu
   DCT_LAUNCH(DCT_PROF_POINTWISE, relu_bits_kernel, dim3(div_up(chunks, 256)), dim3(256), 0, st, (const bf16_t*)y_bf16, bits, chunks);
 }
 
-// the view the convolution arithmetic runs on: x itself, or (d->unpool_codes) the un-pooled tensor x stands for
-static dct_view conv_input_extent(const dct_view* x, const dct_conv_desc* d) {
-  dct_view v = *x;
-  if (d->unpool_codes) { v.h = d->unpool_h; v.w = d->unpool_w; }
-  return v;
-}
-
-extern "C" size_t dct_conv2d_workspace_bytes(const dct_view* x0, const dct_view* y, const dct_conv_desc* d, int dtype) {
-  if (!x0 || !y || !d) return 0;
-  const dct_view xe = conv_input_extent(x0, d);
-  const dct_view* x = &xe;
+extern "C" size_t dct_conv2d_workspace_bytes(const dct_view* x, const dct_view* y, const dct_conv_desc* d, int dtype) {
+  if (!x || !y || !d) return 0;
   const int Ho = d->scatter2x2 ? y->h / 2 : y->h, Wo = d->scatter2x2 ? y->w / 2 : y->w;
   const int M = y->n * Ho * Wo;
   const int N = d->scatter2x2 ? 4 * y->c : y->c;
@@ -1480,20 +1408,10 @@ extern "C" size_t dct_conv2d_workspace_bytes(const dct_view* x0, const dct_view*
   return need;
 }
 
-extern "C" int dct_conv2d(const dct_view* x0, const void* w_packed, const float* bias, const dct_view* mask,
+extern "C" int dct_conv2d(const dct_view* x, const void* w_packed, const float* bias, const dct_view* mask,
                           const dct_view* y, const dct_conv_desc* d, int dtype,
                           void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!view_ok(x0) || !view_ok(y) || !w_packed || !d) return DCT_ERR_BAD_ARG;
-  if (d->unpool_codes) {
-    // x0 is the gradient at the pooled tensor; the convolution runs on the un-pooled extent (strides stay x0's: the kernel indexes windows)
-    if (d->unpool_h < 1 || d->unpool_w < 1 || x0->h != (d->unpool_h + 1) / 2 || x0->w != (d->unpool_w + 1) / 2) return DCT_ERR_BAD_ARG;
-    if (dtype != DCT_BF16 || d->R != 3 || d->S != 3 || d->stride != 1 || d->dil != 1 || d->scatter2x2 || d->pad_h != 2 || d->pad_w != 2 ||
-        x0->c % 64 || ((uintptr_t)d->unpool_codes & 7) || x0->sw != x0->c || x0->sh != (long long)x0->w * x0->c ||
-        x0->sn != (long long)x0->h * x0->w * x0->c || (long long)x0->n * x0->sn >= (1ll << 31))
-      return DCT_ERR_UNSUPPORTED;
-  }
-  const dct_view xe = conv_input_extent(x0, d);
-  const dct_view* x = &xe;
+  if (!view_ok(x) || !view_ok(y) || !w_packed || !d) return DCT_ERR_BAD_ARG;
   if (dtype != DCT_F32 && dtype != DCT_BF16) return DCT_ERR_BAD_ARG;
   if (d->R < 1 || d->S < 1 || d->stride < 1 || d->dil < 1) return DCT_ERR_BAD_ARG;
   if (x->n != y->n) return DCT_ERR_BAD_ARG;
@@ -1549,7 +1467,6 @@ extern "C" int dct_conv2d(const dct_view* x0, const void* w_packed, const float*
   }
   p.stem_x = nullptr; p.stem_slab = nullptr;
   p.xcd_total = 0; p.xcd_gx = p.xcd_gy = 1;
-  p.up_codes = d->unpool_codes; p.up_Hp = x0->h; p.up_Wp = x0->w;
   if (d->stem_x) {
     if (!d->stem_dw || !d->stem_db || ((uintptr_t)d->stem_x & 3)) return DCT_ERR_BAD_ARG;
     if (dtype != DCT_BF16 || y->c != 64 || x->c != 64 || d->R != 3 || d->S != 3 || d->stride != 1 || d->dil != 1 || p.scatter || d->accumulate ||
@@ -1629,7 +1546,6 @@ extern "C" int dct_conv2d(const dct_view* x0, const void* w_packed, const float*
     }
   }
   if (d->stem_x) return DCT_ERR_UNSUPPORTED;      // only the shared-halo 64-channel tile can take the stem along
-  if (d->unpool_codes) return DCT_ERR_UNSUPPORTED;      // only the shared-halo kernels expand a pooled gradient while they stage (the caller un-pools first)
   if (pl.v2 && (!bias || !((uintptr_t)bias & 15))) {
     const PlanP pp = make_plan_p(x, y, d, dtype, p.N);
     if (pp.use) {

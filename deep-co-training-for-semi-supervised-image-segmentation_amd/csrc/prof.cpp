@@ -100,7 +100,7 @@ extern "C" int dct_stamp(unsigned long long* slot, unsigned ring, dct_stream str
   return hipGetLastError() == hipSuccess ? DCT_OK : DCT_ERR_LAUNCH;
 }
 
-extern "C" int dct_version(void) { return 100; }
+extern "C" int dct_version(void) { return DCT_VERSION; }
 
 extern "C" const char* dct_status_string(int status) {
   switch (status) {

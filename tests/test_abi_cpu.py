@@ -29,9 +29,20 @@ def test_binding_table_matches_header():
 def test_status_strings_and_version():
     from dct_amd import _lib
     lib = _lib.load()
-    assert lib.dct_version() >= 100
+    header = open(os.path.join(ROOT, "include", "dct.h")).read()
+    assert lib.dct_version() == _lib.ABI_VERSION == int(re.search(r"#define DCT_VERSION (\d+)", header).group(1)) == 101
     assert lib.dct_status_string(0) == b"ok"
     assert b"workspace" in lib.dct_status_string(-4)
+
+
+def test_load_refuses_a_library_of_another_abi_version(monkeypatch):
+    """A stale libdct_hip.so beside newer Python would be handed structs of another layout: load() must refuse it."""
+    import pytest
+    from dct_amd import _lib
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
+    with pytest.raises(ImportError, match="ABI version"):
+        _lib.load()
 
 
 def test_product_path_rejects_cpu_tensors():

@@ -30,8 +30,7 @@ with d/dx), and replayed on fresh data of the same geometry (`test_recorded_call
 (`test_*_plan_edges`) assert through dct_debug_last_plan that the intended kernel and split / chunk count ran; the Python mirrors of
 the planners (`igemm_plan`, `packed_plan`, `wgrad_plan`) predict them.  The 32-bit addressing guards (`test_*_guard`: lean x_bytes, igemm3m's x32 and
 y16, wgrad's fits32 / M and wgrad3's row offset) run one case just below and one just above a guard with data only in the first and
-last image (or row band).  Out of the recorded set: un-pooling on load (``unpool=``), off in the model by default (tests/test_kernels_gpu.py
-checks it bit for bit against the un-pooling launch)."""
+last image (or row band)."""
 import ctypes
 import math
 import re
@@ -517,7 +516,6 @@ def _replay_conv2d(K, D, a, kw, what):
         sdb = Buf(_T(sdb_d), filled(lambda s, t: ints(D.g, s, -8, 8, t)) if sacc else nan_fill)
         stem = (sx, sdw, sdb, sacc)
         kw["stem"] = (sx.t, sdw.t, sdb.t, sacc)
-    assert kw.get("unpool") is None
     K.conv2d(x.t, wb.t, bias.t if bias is not None else None, y.t, **kw)
     note = plan_note()
     torch.cuda.synchronize()
@@ -596,7 +594,6 @@ def _replay_conv2d_wgrad(K, D, a, kw, what):
     if kw.get("db") is not None:
         db = Buf(_T(kw["db"]), seedfill)
         kw["db"] = db.t
-    assert kw.get("unpool") is None
     K.conv2d_wgrad(p.t, q.t, dw.t, **kw)
     torch.cuda.synchronize()
     p64, q64 = p.t.double(), q.t.double()

@@ -8,7 +8,5 @@ for rnd in 1 2; do
     echo "$kv $(run $args)" >> $O/refine.txt
   done
   echo "default $(run)" >> $O/refine.txt
-  echo "unpool off $(run --net-attr unpool_on_load=0)" >> $O/refine.txt
-  echo "24=60 unpool off $(run --tune 24=60 --net-attr unpool_on_load=0)" >> $O/refine.txt
 done
 cat $O/refine.txt
