@@ -51,6 +51,16 @@ static inline View to_view(const dct_view* v) {
 static inline bool view_ok(const dct_view* v) {
   return v && v->ptr && v->n > 0 && v->h > 0 && v->w > 0 && v->c > 0 && v->sw >= v->c;
 }
+// elements from a view's first to one past its last (times the element size: the range of a buffer descriptor)
+static inline long long view_span(const dct_view* v) {
+  return (long long)(v->n - 1) * v->sn + (long long)(v->h - 1) * v->sh + (long long)(v->w - 1) * v->sw + v->c;
+}
+// out_h x out_w is what the convolution arithmetic of `d` makes of an in_h x in_w image.  (Ho-1)*stride + (R-1)*dil - 2*pad < Hi is
+// NOT required of the callers' shapes beyond this: out-of-range taps read zero.
+static inline bool conv_extent_ok(int in_h, int in_w, const dct_conv_desc* d, int out_h, int out_w) {
+  return (in_h + 2 * d->pad_h - d->dil * (d->R - 1) - 1) / d->stride + 1 == out_h &&
+         (in_w + 2 * d->pad_w - d->dil * (d->S - 1) - 1) / d->stride + 1 == out_w;
+}
 
 // wave-level sum (64 lanes)
 __device__ __forceinline__ float wave_sum(float v) {
@@ -119,6 +129,11 @@ extern thread_local char g_dct_last_plan[200];
 // Diagnostic (tools/ablate_step.py): launches of a kernel family can be SKIPPED -- results are garbage, timing tells what the family
 // costs the captured step (its serialized time minus what the other chain's kernels hide).  dct_tune_set(1100, mask); 0 = nothing skipped.
 extern int g_dct_skip_families;
+// dct_tune_set knobs of the diagnostic tools: not part of include/dct.h; the tools pass the numbers
+enum { DCT_DIAG_IGEMM_SPLIT_MAX_TILES = 1002, DCT_DIAG_IGEMM_SPLIT_MIN_KITERS = 1003,      // planner studies (tools/bench_conv.py --ab-knob)
+       DCT_DIAG_IGEMM_POOL = 1005,           // 0: a requested pooling always runs as its own launch behind the conv
+       DCT_DIAG_STEM_DGRAD_MFMA = 1008,      // 0: the stem's data gradient on the vector-ALU kernel for every shape
+       DCT_DIAG_SKIP_FAMILIES = 1100 };      // mask of the DCT_FAM_* below
 enum { DCT_FAM_IGEMM2 = 1, DCT_FAM_IGEMM3M = 2, DCT_FAM_IGEMM3P = 4, DCT_FAM_WGRAD2 = 8, DCT_FAM_WGRAD3 = 16, DCT_FAM_FOLDS = 32,
        DCT_FAM_ADAM = 64, DCT_FAM_POINTWISE = 128 };
 #define DCT_LAUNCH_FAM(fam, cls, kernel, grid, block, shmem, stream, ...)              \

@@ -1204,10 +1204,10 @@ int g_tune_igemm_halo_min_blocks = 400;
 int g_tune_igemm_pool = 1;      // diagnostic (1005): 0 = a requested pooling always runs as its own launch behind the conv
 int g_tune_igemm_halo = 1;      // 3x3 stride-1 layers with large images: shared-halo kernel (igemm3m_kernel); 0: always the per-tap kernel
 
+// the channel counts every route needs (dct_conv2d asks this among its argument checks, where the status codes have it)
+static bool tap_channels_ok(const dct_view* x, int N, int dtype) { return x->c % (dtype == DCT_BF16 ? 32 : 16) == 0 && N % 64 == 0; }
 static bool make_plan(const dct_view* x, const dct_view* y, const dct_conv_desc* d, int dtype, int M, int N, Plan& pl) {
-  const int bk0 = dtype == DCT_BF16 ? 32 : 16;
-  if (x->c % bk0 != 0) return false;
-  if (N % 64 != 0) return false;
+  if (!tap_channels_ok(x, N, dtype)) return false;
   pl.v2 = (dtype == DCT_BF16 && x->c % 64 == 0) ? 1 : 0;
   if (pl.v2) {
     pl.bk = 64;
@@ -1218,7 +1218,7 @@ static bool make_plan(const dct_view* x, const dct_view* y, const dct_conv_desc*
                         (Wo - 1) * d->stride + (d->S - 1) * d->dil < x->w;
     pl.bounds = inside ? 0 : 1;
   } else {
-    pl.bk = bk0;
+    pl.bk = dtype == DCT_BF16 ? 32 : 16;
     pl.bn = (N % 128 == 0) ? 128 : 64;
     pl.bm = 128;
     pl.bounds = 1;
@@ -1349,23 +1349,24 @@ static dim3 xcd_grid(IgemmParams& p, dim3 grid, bool per_tap) {
   p.xcd_gx = (int)grid.x; p.xcd_gy = (int)grid.y; p.xcd_total = (int)total;
   return dim3((unsigned)(((total + 7) / 8) * 8), 1, 1);
 }
+template <typename T>
+static void fold_splits(const IgemmParams& p, int splits, hipStream_t st) {      // split launches: the fixed-order sum of the fp32 slabs, then the epilogue
+  if (splits > 1)
+    DCT_LAUNCH_FAM(DCT_FAM_FOLDS, DCT_PROF_IGEMM, (splitk_epilogue_kernel<T>), dim3(div_up((long long)p.M * (p.N / 4), 256)), dim3(256), 0, st, p, splits);
+}
 static void launch_v3p(const IgemmParams& p0, const PlanP& pp, int images, hipStream_t st) {
   IgemmParams p = p0;
   const dim3 grid = xcd_grid(p, dim3((unsigned)(images * pp.tiles_per_img), p.N / 128, pp.splits), false);
   // lean loop: buffer descriptors need the activations and the packed weights under 2 GiB each
   if ((g_tune_lean & 2) && p.x_bytes < (1ll << 31) && p.w_bytes < (1ll << 31)) launch_v3p_k<true>(p, pp, grid, st);
   else launch_v3p_k<false>(p, pp, grid, st);
-  if (pp.splits > 1) {
-    const long long work = (long long)p.M * (p.N / 4);
-    DCT_LAUNCH_FAM(DCT_FAM_FOLDS, DCT_PROF_IGEMM, (splitk_epilogue_kernel<bf16_t>), dim3(div_up(work, 256)), dim3(256), 0, st, p, pp.splits);
-  }
+  fold_splits<bf16_t>(p, pp.splits, st);
 }
 
 template <typename T>
-static int launch(const IgemmParams& p0, const Plan& pl, hipStream_t st) {
+static void launch(const IgemmParams& p0, const Plan& pl, hipStream_t st) {
   IgemmParams p = p0;
   dim3 grid(div_up(p.M, pl.bm), p.N / pl.bn, pl.splits);
-  p.xcd_total = 0; p.xcd_gx = p.xcd_gy = 1;
   if (pl.v2) {
     grid = xcd_grid(p, grid, true);
     if (pl.bn == 128) {
@@ -1378,11 +1379,7 @@ static int launch(const IgemmParams& p0, const Plan& pl, hipStream_t st) {
   } else {
     DCT_LAUNCH(DCT_PROF_IGEMM, (igemm_kernel<T, 64, 128>), grid, dim3(256), 0, st, p);
   }
-  if (pl.splits > 1) {
-    const long long work = (long long)p.M * (p.N / 4);
-    DCT_LAUNCH_FAM(DCT_FAM_FOLDS, DCT_PROF_IGEMM, (splitk_epilogue_kernel<T>), dim3(div_up(work, 256)), dim3(256), 0, st, p, pl.splits);
-  }
-  return dct_check_launch();
+  fold_splits<T>(p, pl.splits, st);
 }
 
 }  // namespace
@@ -1394,58 +1391,104 @@ void dct_relu_bits_launch(const void* y_bf16, unsigned char* bits, long long chu
   DCT_LAUNCH(DCT_PROF_POINTWISE, relu_bits_kernel, dim3(div_up(chunks, 256)), dim3(256), 0, st, (const bf16_t*)y_bf16, bits, chunks);
 }
 
-extern "C" size_t dct_conv2d_workspace_bytes(const dct_view* x, const dct_view* y, const dct_conv_desc* d, int dtype) {
-  if (!x || !y || !d) return 0;
+// The route of a dct_conv2d call, in order of preference: plan_conv decides it once, dct_conv2d only executes it.
+enum Route { ROUTE_HALO, ROUTE_HALO_STEM, ROUTE_PACKED, ROUTE_TAP };
+struct ConvPlan {
+  Route route;
+  Plan tap;                   // per-tap tile and split-K: what ROUTE_TAP launches, and the K-step fields of IgemmParams on every route
+  PlanP packed;               // ROUTE_PACKED
+  int bn, tiles_x, tiles_y; long long blocks; double cover;   // ROUTE_HALO*: channel tile, 8 x 16 patches over an image, blocks, image part of the patches
+  int staged;                 // LDS-staged epilogue (16-byte row stores)
+  int fused_pool;             // the requested pooling happens in the epilogue; if not, the pooling kernel runs behind the conv
+  int bits_after;             // neither an epilogue nor a fold of this launch leaves the ReLU bits: relu_bits_kernel runs behind it
+  size_t workspace;           // bytes the route needs
+};
+// What the decision depends on besides the shapes: y, the mask and the bias can all be accessed the way the staged epilogues do it; the workspace (0: none)
+struct ConvPtrs { bool vec16; size_t workspace_bytes; };
+// 16-byte vectors at 32-bit element offsets over the first `channels` of a 16-bit view
+static bool vec16_ok(const dct_view* v, int channels) {
+  return !((uintptr_t)v->ptr & 15) && v->sw % 8 == 0 && v->sh % 8 == 0 && v->sn % 8 == 0 && channels % 8 == 0 && (long long)v->n * v->sn < (1ll << 31);
+}
+static bool bias16_ok(const float* bias) { return !bias || !((uintptr_t)bias & 15); }      // the staged epilogues read the bias as float4
+static size_t slab_bytes(int splits, int M, int N) { return splits > 1 ? (size_t)splits * M * N * sizeof(float) : 0; }      // fp32 split slabs
+
+// ptrs == nullptr (dct_conv2d_workspace_bytes: there are no pointers to look at) chooses no route: cp.workspace is then the largest
+// need of any route the shapes allow -- a stem request counted whether or not the layer can take it, as it always was.
+static int plan_conv(const dct_view* x, const dct_view* y, const dct_conv_desc* d, int dtype, const ConvPtrs* ptrs, ConvPlan& cp) {
   const int Ho = d->scatter2x2 ? y->h / 2 : y->h, Wo = d->scatter2x2 ? y->w / 2 : y->w;
-  const int M = y->n * Ho * Wo;
-  const int N = d->scatter2x2 ? 4 * y->c : y->c;
-  Plan pl;
-  if (!make_plan(x, y, d, dtype, M, N, pl)) return 0;
-  size_t need = pl.splits > 1 ? (size_t)pl.splits * M * N * sizeof(float) : 0;
-  const PlanP pp = make_plan_p(x, y, d, dtype, N);
-  if (pp.use && pp.splits > 1) need = std::max(need, (size_t)pp.splits * M * N * sizeof(float));
-  if (d->stem_x) need = std::max(need, (size_t)y->n * ((Ho + 7) / 8) * ((Wo + 15) / 16) * 640 * sizeof(float) + dct_split_dw_db_scratch(64, 9));
-  return need;
+  const int M = y->n * Ho * Wo, N = d->scatter2x2 ? 4 * y->c : y->c;
+  const Plan& pl = cp.tap;
+  if (!make_plan(x, y, d, dtype, M, N, cp.tap)) return DCT_ERR_UNSUPPORTED;
+  const size_t tap_need = slab_bytes(pl.splits, M, N);
+  // shared-halo kernel: 8 x 16 output patches; worth it when the patches cover the image well and fill the device
+  cp.tiles_y = (Ho + 7) / 8; cp.tiles_x = (Wo + 15) / 16; cp.bn = N % 128 == 0 ? 128 : 64;
+  const long long patches = (long long)y->n * cp.tiles_y * cp.tiles_x;
+  cp.blocks = patches * (N / cp.bn);
+  cp.cover = (double)Ho * Wo / ((double)cp.tiles_y * 8 * cp.tiles_x * 16);
+  // 32-bit addressing inside the kernel: x within 2^31 elements, a weight tile's rows within 2^32 bytes of its first
+  const bool x32 = (long long)x->n * x->sn < (1ll << 31) && (long long)cp.bn * 9 * x->c * 2 < (1ll << 32);
+  // measured (tools/bench_conv.py --ab): the 64-channel tile only pays with a single channel slice (four blocks per CU)
+  const bool halo = pl.v2 && pl.splits == 1 && g_tune_igemm_halo && d->R == 3 && d->S == 3 && d->stride == 1 && d->dil == 1 && !d->scatter2x2 &&
+                    x32 && cp.cover >= g_tune_igemm_halo_cover * 0.01 && cp.blocks >= g_tune_igemm_halo_min_blocks && (cp.bn == 128 || x->c == 64);
+  // the stem's weight gradient: one [64][10] fp32 record per patch (its layers have one channel tile) and the scratch of their fold
+  const size_t stem_need = d->stem_x ? (size_t)patches * 640 * sizeof(float) + dct_split_dw_db_scratch(64, 9) : 0;
+  cp.packed = make_plan_p(x, y, d, dtype, N);
+  const size_t packed_need = cp.packed.use ? slab_bytes(cp.packed.splits, M, N) : 0;
+  cp.staged = cp.fused_pool = cp.bits_after = 0;
+  if (!ptrs) { cp.workspace = std::max({tap_need, packed_need, stem_need}); return DCT_OK; }
+  if (ptrs->workspace_bytes < tap_need) return DCT_ERR_WORKSPACE;      // (whichever route the layer ends on)
+  cp.staged = (pl.v2 && pl.splits == 1 && !d->accumulate && ptrs->vec16) ? 1 : 0;
+  if (halo && ptrs->vec16) {
+    cp.route = d->stem_x ? ROUTE_HALO_STEM : ROUTE_HALO;
+    cp.fused_pool = (d->pool_out && g_tune_igemm_pool) ? 1 : 0;
+    cp.workspace = stem_need;
+    return ptrs->workspace_bytes < stem_need ? DCT_ERR_WORKSPACE : DCT_OK;
+  }
+  if (d->stem_x) return DCT_ERR_UNSUPPORTED;      // only the shared-halo 64-channel tile can take the stem along
+  if (cp.packed.use && ptrs->vec16 && ptrs->workspace_bytes >= packed_need) {      // (slabs that do not fit: the per-tap kernel)
+    cp.route = ROUTE_PACKED; cp.workspace = packed_need;
+    return DCT_OK;
+  }
+  cp.route = ROUTE_TAP; cp.workspace = tap_need;
+  cp.bits_after = (d->relu_bits_out && !cp.staged && pl.splits == 1) ? 1 : 0;      // (a split layer's fold writes the bits itself)
+  return DCT_OK;
+}
+
+extern "C" size_t dct_conv2d_workspace_bytes(const dct_view* x, const dct_view* y, const dct_conv_desc* d, int dtype) {
+  ConvPlan cp;
+  return x && y && d && plan_conv(x, y, d, dtype, nullptr, cp) == DCT_OK ? cp.workspace : 0;
 }
 
 extern "C" int dct_conv2d(const dct_view* x, const void* w_packed, const float* bias, const dct_view* mask,
                           const dct_view* y, const dct_conv_desc* d, int dtype,
                           void* workspace, size_t workspace_bytes, dct_stream stream) {
+  // ---- the arguments (and the fields of IgemmParams that are copies of them)
   if (!view_ok(x) || !view_ok(y) || !w_packed || !d) return DCT_ERR_BAD_ARG;
   if (dtype != DCT_F32 && dtype != DCT_BF16) return DCT_ERR_BAD_ARG;
   if (d->R < 1 || d->S < 1 || d->stride < 1 || d->dil < 1) return DCT_ERR_BAD_ARG;
   if (x->n != y->n) return DCT_ERR_BAD_ARG;
-  IgemmParams p;
+  IgemmParams p = {};      // every optional pointer null, every option off
   p.scatter = d->scatter2x2 ? 1 : 0;
   if (p.scatter && (y->h % 2 || y->w % 2 || d->R != 1 || d->S != 1)) return DCT_ERR_BAD_ARG;
   p.Ho = p.scatter ? y->h / 2 : y->h;
   p.Wo = p.scatter ? y->w / 2 : y->w;
   p.Hi = x->h; p.Wi = x->w;
-  // the output extent must be reachable: (Ho-1)*stride + (R-1)*dil - 2*pad < Hi is NOT required
-  // (out-of-range taps read zero), but shapes must match the conv arithmetic
-  {
-    const int eh = (x->h + 2 * d->pad_h - d->dil * (d->R - 1) - 1) / d->stride + 1;
-    const int ew = (x->w + 2 * d->pad_w - d->dil * (d->S - 1) - 1) / d->stride + 1;
-    if (eh != p.Ho || ew != p.Wo) return DCT_ERR_BAD_ARG;
-  }
+  if (!conv_extent_ok(x->h, x->w, d, p.Ho, p.Wo)) return DCT_ERR_BAD_ARG;
   p.M = y->n * p.Ho * p.Wo;
   p.cout = y->c;
   p.N = p.scatter ? 4 * y->c : y->c;
   p.Cin = x->c; p.R = d->R; p.S = d->S;
   p.stride = d->stride; p.dil = d->dil; p.pad_h = d->pad_h; p.pad_w = d->pad_w;
-  const int esz = dtype == DCT_BF16 ? 2 : 4;
-  const int epv = 16 / esz;
+  const int esz = dtype == DCT_BF16 ? 2 : 4, epv = 16 / esz;
   // 16-byte vector access requirements
   if (((uintptr_t)x->ptr & 15) || ((uintptr_t)w_packed & 15) || (x->sw % epv) || (x->sh % epv) || (x->sn % epv)) return DCT_ERR_UNSUPPORTED;
   if (((uintptr_t)y->ptr & (4 * esz - 1)) || (y->sw % 4) || (y->sh % 4) || (y->sn % 4) || (y->c % 4)) return DCT_ERR_UNSUPPORTED;
-  Plan pl;
-  if (!make_plan(x, y, d, dtype, p.M, p.N, pl)) return DCT_ERR_UNSUPPORTED;
+  if (!tap_channels_ok(x, p.N, dtype)) return DCT_ERR_UNSUPPORTED;
   if ((long long)p.M * p.N > (1ll << 40)) return DCT_ERR_UNSUPPORTED;
   p.x = (const char*)x->ptr; p.w = (const char*)w_packed; p.bias = bias; p.y = (char*)y->ptr;
   p.xsN = x->sn; p.xsH = x->sh; p.xsW = x->sw;
   p.ysN = y->sn; p.ysH = y->sh; p.ysW = y->sw;
-  p.mask = nullptr; p.msN = p.msH = p.msW = 0;
-  p.mask_channels = 0; p.mask_scale = 1.f;
+  p.mask_scale = 1.f;
   if (mask) {
     if (!view_ok(mask) || mask->n != y->n || mask->h != y->h || mask->w != y->w) return DCT_ERR_BAD_ARG;
     if (((uintptr_t)mask->ptr & (4 * esz - 1)) || (mask->sw % 4) || (mask->sh % 4) || (mask->sn % 4)) return DCT_ERR_UNSUPPORTED;
@@ -1454,7 +1497,6 @@ extern "C" int dct_conv2d(const dct_view* x, const void* w_packed, const float* 
     if (p.mask_channels % 4) return DCT_ERR_UNSUPPORTED;
     p.mask_scale = d->mask_scale;
   }
-  p.mask_bits = nullptr; p.bits_out = nullptr;
   const auto dense = [](const dct_view* v) { return v->sw == v->c && v->sh == (long long)v->w * v->c && v->sn == (long long)v->h * v->w * v->c; };
   if (d->mask_bits) {
     // a one-bit image of `mask` (which stays the source for the paths without a staged epilogue)
@@ -1465,112 +1507,69 @@ extern "C" int dct_conv2d(const dct_view* x, const void* w_packed, const float* 
     if (dtype != DCT_BF16 || !dense(y) || y->c % 8 || p.scatter || ((uintptr_t)y->ptr & 15)) return DCT_ERR_BAD_ARG;
     p.bits_out = d->relu_bits_out;
   }
-  p.stem_x = nullptr; p.stem_slab = nullptr;
-  p.xcd_total = 0; p.xcd_gx = p.xcd_gy = 1;
   if (d->stem_x) {
     if (!d->stem_dw || !d->stem_db || ((uintptr_t)d->stem_x & 3)) return DCT_ERR_BAD_ARG;
     if (dtype != DCT_BF16 || y->c != 64 || x->c != 64 || d->R != 3 || d->S != 3 || d->stride != 1 || d->dil != 1 || p.scatter || d->accumulate ||
         d->relu || bias || !d->mask_bits || d->mask_scale != 1.f || d->pool_out || d->relu_bits_out || !g_tune_igemm_halo)
       return DCT_ERR_UNSUPPORTED;
   }
-  p.pool_y = nullptr; p.pool_codes = nullptr; p.Hp = (y->h + 1) / 2; p.Wp = (y->w + 1) / 2; p.pool_only = 0;
   if (d->pool_only && (!d->pool_out || d->relu_bits_out)) return DCT_ERR_BAD_ARG;
   if (d->pool_codes && !d->pool_out) return DCT_ERR_BAD_ARG;
   if (d->pool_out) {
     if (p.scatter || d->accumulate || mask || d->mask_bits || ((uintptr_t)d->pool_out & 15) || ((uintptr_t)d->pool_codes & 7) || y->c % 8) return DCT_ERR_BAD_ARG;
   }
+  // ---- the plan, and the fields that follow from it
+  const ConvPtrs ptrs = {vec16_ok(y, y->c) && (!mask || vec16_ok(mask, p.mask_channels)) && bias16_ok(bias), workspace ? workspace_bytes : 0};
+  ConvPlan cp;
+  const int rc = plan_conv(x, y, d, dtype, &ptrs, cp);
+  if (rc != DCT_OK) return rc;
+  p.relu = d->relu; p.accumulate = d->accumulate;
+  p.kiters = cp.tap.kiters; p.kiters_per_split = cp.tap.kiters_per_split;
+  p.cin_iters = x->c / cp.tap.bk;
+  p.staged = cp.staged;
+  p.x_bytes = view_span(x) * esz;
+  p.w_bytes = (long long)p.N * d->R * d->S * x->c * esz;
+  p.xcd_gx = p.xcd_gy = 1;
+  p.Hp = (y->h + 1) / 2; p.Wp = (y->w + 1) / 2;
   hipStream_t st = (hipStream_t)stream;
-  const auto pool_after = [&]() -> int {   // the launch just issued did not pool its tile: the pooling kernel behind it
-    if (!d->pool_out) return DCT_OK;
+  switch (cp.route) {
+    case ROUTE_HALO_STEM:
+      p.stem_x = d->stem_x; p.stem_slab = (float*)workspace;
+      launch_v3<64, 1, 1>(p, cp.tiles_x, cp.tiles_y, y->n, st);
+      dct_split_dw_db_launch(p.stem_slab, p.stem_slab + cp.blocks * 640, d->stem_dw, d->stem_db, 64, 9, (int)cp.blocks, d->stem_accumulate, st);
+      DCT_PLAN_NOTE("igemm3m shared-halo 8x16 patches x 64 ch: %lld blocks, stem weight gradient from the tile, y not stored", cp.blocks);
+      break;
+    case ROUTE_HALO:
+      if (cp.fused_pool) { p.pool_y = (char*)d->pool_out; p.pool_codes = d->pool_codes; p.pool_only = d->pool_only ? 1 : 0; }
+      if (cp.bn == 128) {
+        if (x->c == 64) launch_v3<128, 2, 1>(p, cp.tiles_x, cp.tiles_y, y->n, st); else launch_v3<128, 2, 2>(p, cp.tiles_x, cp.tiles_y, y->n, st);
+      } else launch_v3<64, 1, 1>(p, cp.tiles_x, cp.tiles_y, y->n, st);
+      DCT_PLAN_NOTE("igemm3m shared-halo 8x16 patches x %d ch: %lld blocks, cover %.0f %%, %d K-steps%s", cp.bn, cp.blocks, cp.cover * 100, 9 * x->c / 64,
+                    p.pool_y ? (p.pool_only ? ", pooled in the epilogue, y not stored" : ", pooled in the epilogue") : "");
+      break;
+    case ROUTE_PACKED:
+      if (cp.packed.splits > 1) p.partial = (float*)workspace;
+      launch_v3p(p, cp.packed, y->n, st);
+      DCT_PLAN_NOTE("igemm3p packed rows (%d rows of %d px per 128-px tile): %d x %d blocks x %d channel-slice splits", cp.packed.PR, p.Wo,
+                    y->n * cp.packed.tiles_per_img, p.N / 128, cp.packed.splits);
+      break;
+    case ROUTE_TAP:
+      if (cp.tap.splits > 1) p.partial = (float*)workspace;
+      if (dtype == DCT_BF16) launch<bf16_t>(p, cp.tap, st); else launch<float>(p, cp.tap, st);
+      DCT_PLAN_NOTE("%s per-tap %d x %d tile%s: %lld tiles x %d splits, %d K-steps each%s", cp.tap.v2 ? "igemm2" : "igemm", cp.tap.bm, cp.tap.bn,
+                    cp.tap.bounds ? " (bounds)" : "", cp.tap.tiles, cp.tap.splits, cp.tap.kiters_per_split, p.staged ? ", staged epilogue" : "");
+      break;
+  }
+  // ---- what the launch still owes
+  if (cp.bits_after) dct_relu_bits_launch(y->ptr, p.bits_out, (long long)y->n * y->h * y->w * (y->c / 8), st);
+  if (d->pool_out && !cp.fused_pool) {
     dct_view pv;
     pv.ptr = d->pool_out; pv.n = y->n; pv.h = p.Hp; pv.w = p.Wp; pv.c = y->c;
     pv.sw = y->c; pv.sh = (long long)p.Wp * y->c; pv.sn = (long long)p.Hp * p.Wp * y->c;
-    return d->pool_codes ? dct_maxpool2x2_fwd_codes(y, &pv, d->pool_codes, dtype, stream) : dct_maxpool2x2_fwd(y, &pv, dtype, stream);
-  };
-  const auto bits_after = [&]() {      // the launch just issued did not write the bits in its epilogue
-    if (!p.bits_out) return;
-    dct_relu_bits_launch(y->ptr, p.bits_out, (long long)y->n * y->h * y->w * (y->c / 8), st);
-  };
-  p.relu = d->relu; p.accumulate = d->accumulate;
-  p.kiters = pl.kiters; p.kiters_per_split = pl.kiters_per_split;
-  p.cin_iters = x->c / pl.bk;
-  p.partial = nullptr;
-  p.staged = 0;
-  p.x_bytes = ((long long)(x->n - 1) * x->sn + (long long)(x->h - 1) * x->sh + (long long)(x->w - 1) * x->sw + x->c) * esz;
-  p.w_bytes = (long long)p.N * d->R * d->S * x->c * esz;
-  if (pl.v2 && pl.splits == 1 && !d->accumulate) {
-    const bool y16 = !((uintptr_t)y->ptr & 15) && y->sw % 8 == 0 && y->sh % 8 == 0 && y->sn % 8 == 0 && y->c % 8 == 0 &&
-                     (long long)y->n * y->sn < (1ll << 31);
-    const bool m16 = !mask || (!((uintptr_t)mask->ptr & 15) && mask->sw % 8 == 0 && mask->sh % 8 == 0 && mask->sn % 8 == 0 &&
-                               p.mask_channels % 8 == 0 && (long long)mask->n * mask->sn < (1ll << 31));
-    const bool b16 = !bias || !((uintptr_t)bias & 15);      // the staged epilogues read the bias as float4
-    p.staged = (y16 && m16 && b16) ? 1 : 0;
+    const int rp = d->pool_codes ? dct_maxpool2x2_fwd_codes(y, &pv, d->pool_codes, dtype, stream) : dct_maxpool2x2_fwd(y, &pv, dtype, stream);
+    if (rp != DCT_OK) return rp;
   }
-  if (pl.splits > 1) {
-    const size_t need = (size_t)pl.splits * p.M * p.N * sizeof(float);
-    if (!workspace || workspace_bytes < need) return DCT_ERR_WORKSPACE;
-    p.partial = (float*)workspace;
-  }
-  if (pl.v2 && pl.splits == 1 && g_tune_igemm_halo && (!bias || !((uintptr_t)bias & 15)) && d->R == 3 && d->S == 3 && d->stride == 1 &&
-      d->dil == 1 && !p.scatter) {
-    // shared-halo kernel: 8 x 16 output patches; worth it when the patches cover the image well and fill the device
-    const bool y16 = !((uintptr_t)y->ptr & 15) && y->sw % 8 == 0 && y->sh % 8 == 0 && y->sn % 8 == 0 && y->c % 8 == 0 &&
-                     (long long)y->n * y->sn < (1ll << 31);
-    const bool m16 = !mask || (!((uintptr_t)mask->ptr & 15) && mask->sw % 8 == 0 && mask->sh % 8 == 0 && mask->sn % 8 == 0 &&
-                               p.mask_channels % 8 == 0 && (long long)mask->n * mask->sn < (1ll << 31));
-    const int tiles_y = (p.Ho + 7) / 8, tiles_x = (p.Wo + 15) / 16;
-    const int bn = p.N % 128 == 0 ? 128 : 64;
-    const long long blocks = (long long)y->n * tiles_y * tiles_x * (p.N / bn);
-    const double cover = (double)p.Ho * p.Wo / ((double)tiles_y * 8 * tiles_x * 16);
-    // measured (tools/bench_conv.py --ab): the 64-channel tile only pays with a single channel slice (four blocks per CU)
-    // 32-bit addressing inside the kernel: x within 2^31 elements, a weight tile's rows within 2^32 bytes of its first
-    const bool x32 = (long long)x->n * x->sn < (1ll << 31) && (long long)bn * 9 * x->c * 2 < (1ll << 32);
-    if (y16 && m16 && x32 && cover >= g_tune_igemm_halo_cover * 0.01 && blocks >= g_tune_igemm_halo_min_blocks && (bn == 128 || x->c == 64)) {
-      if (d->pool_out && g_tune_igemm_pool) { p.pool_y = (char*)d->pool_out; p.pool_codes = d->pool_codes; p.pool_only = d->pool_only ? 1 : 0; }
-      if (d->stem_x) {
-        const size_t need = (size_t)blocks * 640 * sizeof(float) + dct_split_dw_db_scratch(64, 9);
-        if (!workspace || workspace_bytes < need) return DCT_ERR_WORKSPACE;
-        p.stem_x = d->stem_x; p.stem_slab = (float*)workspace;
-        launch_v3<64, 1, 1>(p, tiles_x, tiles_y, y->n, st);
-        dct_split_dw_db_launch((const float*)workspace, (float*)workspace + blocks * 640, d->stem_dw, d->stem_db, 64, 9, (int)blocks, d->stem_accumulate, st);
-        DCT_PLAN_NOTE("igemm3m shared-halo 8x16 patches x 64 ch: %lld blocks, stem weight gradient from the tile, y not stored", blocks);
-        return dct_check_launch();
-      }
-      if (bn == 128) {
-        if (x->c == 64) launch_v3<128, 2, 1>(p, tiles_x, tiles_y, y->n, st); else launch_v3<128, 2, 2>(p, tiles_x, tiles_y, y->n, st);
-      } else launch_v3<64, 1, 1>(p, tiles_x, tiles_y, y->n, st);
-      DCT_PLAN_NOTE("igemm3m shared-halo 8x16 patches x %d ch: %lld blocks, cover %.0f %%, %d K-steps%s", bn, blocks, cover * 100, 9 * x->c / 64,
-                    p.pool_y ? (p.pool_only ? ", pooled in the epilogue, y not stored" : ", pooled in the epilogue") : "");
-      if (!p.pool_y) { const int rp = pool_after(); if (rp != DCT_OK) return rp; }
-      return dct_check_launch();
-    }
-  }
-  if (d->stem_x) return DCT_ERR_UNSUPPORTED;      // only the shared-halo 64-channel tile can take the stem along
-  if (pl.v2 && (!bias || !((uintptr_t)bias & 15))) {
-    const PlanP pp = make_plan_p(x, y, d, dtype, p.N);
-    if (pp.use) {
-      const bool y16 = !((uintptr_t)y->ptr & 15) && y->sw % 8 == 0 && y->sh % 8 == 0 && y->sn % 8 == 0 && y->c % 8 == 0 &&
-                       (long long)y->n * y->sn < (1ll << 31);
-      const bool m16 = !mask || (!((uintptr_t)mask->ptr & 15) && mask->sw % 8 == 0 && mask->sh % 8 == 0 && mask->sn % 8 == 0 &&
-                                 p.mask_channels % 8 == 0 && (long long)mask->n * mask->sn < (1ll << 31));
-      const size_t need = pp.splits > 1 ? (size_t)pp.splits * p.M * p.N * sizeof(float) : 0;
-      if (y16 && m16 && (!need || (workspace && workspace_bytes >= need))) {
-        IgemmParams q = p;
-        q.partial = pp.splits > 1 ? (float*)workspace : nullptr;
-        launch_v3p(q, pp, y->n, st);
-        { const int rp = pool_after(); if (rp != DCT_OK) return rp; }
-        DCT_PLAN_NOTE("igemm3p packed rows (%d rows of %d px per 128-px tile): %d x %d blocks x %d channel-slice splits", pp.PR, p.Wo,
-                      y->n * pp.tiles_per_img, p.N / 128, pp.splits);
-        return dct_check_launch();
-      }
-    }
-  }
-  const int rc = dtype == DCT_BF16 ? launch<bf16_t>(p, pl, st) : launch<float>(p, pl, st);
-  DCT_PLAN_NOTE("%s per-tap %d x %d tile%s: %lld tiles x %d splits, %d K-steps each%s", pl.v2 ? "igemm2" : "igemm", pl.bm, pl.bn,
-                pl.bounds ? " (bounds)" : "", pl.tiles, pl.splits, pl.kiters_per_split, p.staged ? ", staged epilogue" : "");
-  if (rc == DCT_OK && !p.staged && pl.splits == 1) bits_after();      // (a split layer's fold writes the bits itself)
-  if (rc == DCT_OK) { const int rp = pool_after(); if (rp != DCT_OK) return rp; }
-  return rc == DCT_OK ? dct_check_launch() : rc;
+  return dct_check_launch();
 }
 
 
@@ -1593,11 +1592,11 @@ extern "C" int dct_tune_set(int knob, int value) {
     case DCT_TUNE_IGEMM_PACKED_SPLIT: if (value < 1) return DCT_ERR_BAD_ARG; g_tune_igemm_packed_split = value; return DCT_OK;
     case DCT_TUNE_IGEMM_PACKED_FILL: if (value < 1 || value > 100) return DCT_ERR_BAD_ARG; g_tune_igemm_packed_fill = value; return DCT_OK;
     case DCT_TUNE_IGEMM_XCD: if (value < 0 || value > 2) return DCT_ERR_BAD_ARG; g_tune_igemm_xcd = value; return DCT_OK;
-    case 1100: g_dct_skip_families = value; return DCT_OK;      // diagnostic: skip kernel families (tools/ablate_step.py)
-    case 1005: g_tune_igemm_pool = value ? 1 : 0; return DCT_OK;
-    case 1008: g_stem_dgrad_mfma = value ? 1 : 0; return DCT_OK;
-    case 1002: g_tune_igemm_split_max_tiles = value; return DCT_OK;     // planner studies (tools/bench_conv.py --ab-knob)
-    case 1003: g_tune_igemm_split_min_kiters = value; return DCT_OK;
+    case DCT_DIAG_SKIP_FAMILIES: g_dct_skip_families = value; return DCT_OK;      // diagnostic: skip kernel families (tools/ablate_step.py)
+    case DCT_DIAG_IGEMM_POOL: g_tune_igemm_pool = value ? 1 : 0; return DCT_OK;
+    case DCT_DIAG_STEM_DGRAD_MFMA: g_stem_dgrad_mfma = value ? 1 : 0; return DCT_OK;
+    case DCT_DIAG_IGEMM_SPLIT_MAX_TILES: g_tune_igemm_split_max_tiles = value; return DCT_OK;     // planner studies (tools/bench_conv.py --ab-knob)
+    case DCT_DIAG_IGEMM_SPLIT_MIN_KITERS: g_tune_igemm_split_min_kiters = value; return DCT_OK;
     case DCT_TUNE_ENET_WGRAD_BLOCKS: if (value < 1 || value > 1024) return DCT_ERR_BAD_ARG; g_enet_wgrad_max_blocks = value; return DCT_OK;
     default: return dct_tune_set_wgrad(knob, value);
   }

@@ -1262,11 +1262,7 @@ extern "C" int dct_conv2d_wgrad_bias(const dct_view* p, const dct_view* q, float
   if (!view_ok(p) || !view_ok(q) || !dw || !d) return DCT_ERR_BAD_ARG;
   if (dtype != DCT_F32 && dtype != DCT_BF16) return DCT_ERR_BAD_ARG;
   if (p->n != q->n) return DCT_ERR_BAD_ARG;
-  {
-    const int eh = (q->h + 2 * d->pad_h - d->dil * (d->R - 1) - 1) / d->stride + 1;
-    const int ew = (q->w + 2 * d->pad_w - d->dil * (d->S - 1) - 1) / d->stride + 1;
-    if (eh != p->h || ew != p->w) return DCT_ERR_BAD_ARG;
-  }
+  if (!conv_extent_ok(q->h, q->w, d, p->h, p->w)) return DCT_ERR_BAD_ARG;
   const int esz = dtype == DCT_BF16 ? 2 : 4, epv = 16 / esz;
   if (((uintptr_t)p->ptr & 15) || ((uintptr_t)q->ptr & 15) || (p->sw % epv) || (p->sh % epv) || (p->sn % epv) ||
       (q->sw % epv) || (q->sh % epv) || (q->sn % epv) || ((uintptr_t)dw & 15))
@@ -1294,8 +1290,8 @@ extern "C" int dct_conv2d_wgrad_bias(const dct_view* p, const dct_view* q, float
     pr.direct = pl.direct; pr.accumulate = d->accumulate;
     pr.bias = db; pr.with_bias = db ? 1 : 0; pr.slab_stride = slab_stride;
     pr.skip_empty = (g_tune_lean & 16) ? 1 : 0;
-    pr.p_bytes = ((long long)(p->n - 1) * p->sn + (long long)(p->h - 1) * p->sh + (long long)(p->w - 1) * p->sw + p->c) * 2;
-    pr.q_bytes = ((long long)(q->n - 1) * q->sn + (long long)(q->h - 1) * q->sh + (long long)(q->w - 1) * q->sw + q->c) * 2;
+    pr.p_bytes = view_span(p) * 2;
+    pr.q_bytes = view_span(q) * 2;
     pr.stamps = g_w3_stamps;
     launch_w3(pr, pl, st);
   } else if (pl.v2) {
@@ -1305,8 +1301,8 @@ extern "C" int dct_conv2d_wgrad_bias(const dct_view* p, const dct_view* q, float
     pr.dw_.d = p->w; pr.dw_.rcp = 1.0f / (float)pr.dw_.d;
     pr.direct = pl.direct; pr.accumulate = d->accumulate;
     pr.bias = db; pr.with_bias = db ? 1 : 0; pr.slab_stride = slab_stride;
-    pr.p_bytes = ((long long)(p->n - 1) * p->sn + (long long)(p->h - 1) * p->sh + (long long)(p->w - 1) * p->sw + p->c) * 2;
-    pr.q_bytes = ((long long)(q->n - 1) * q->sn + (long long)(q->h - 1) * q->sh + (long long)(q->w - 1) * q->sw + q->c) * 2;
+    pr.p_bytes = view_span(p) * 2;
+    pr.q_bytes = view_span(q) * 2;
     launch_w2(pr, pl, st);
   } else if (dtype == DCT_BF16) launch_w<bf16_t>(wp, pl, st);
   else launch_w<float>(wp, pl, st);

@@ -192,15 +192,11 @@ def conv2d(x, w_packed, bias, y, *, R=3, S=3, stride=1, dil=1, pad_h=0, pad_w=0,
     need = lib.dct_conv2d_workspace_bytes(C.byref(vx), C.byref(vy), C.byref(d), dt)
     ws = _ws(need, x.device)
     vm = view(mask) if mask is not None else None
-    if stem is not None:
-        rc = getattr(lib, "dct_conv2d")(C.byref(vx), ptr(w_packed), ptr(bias), C.byref(vm) if vm is not None else None,
-                                        C.byref(vy), C.byref(d), dt, ptr(ws), ws.numel(), stream())
-        if rc == _lib.ERR_UNSUPPORTED:
-            raise StemFusionUnsupported()
-        _lib.check(rc, "dct_conv2d")
-        return y
-    call("dct_conv2d", C.byref(vx), ptr(w_packed), ptr(bias), C.byref(vm) if vm is not None else None,
-         C.byref(vy), C.byref(d), dt, ptr(ws), ws.numel(), stream())
+    rc = lib.dct_conv2d(C.byref(vx), ptr(w_packed), ptr(bias), C.byref(vm) if vm is not None else None,
+                        C.byref(vy), C.byref(d), dt, ptr(ws), ws.numel(), stream())
+    if stem is not None and rc == _lib.ERR_UNSUPPORTED:
+        raise StemFusionUnsupported()
+    _lib.check(rc, "dct_conv2d")
     return y
 
 

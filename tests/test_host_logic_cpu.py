@@ -416,3 +416,96 @@ def test_bench_dump_outputs_writes_the_step_arrays(tmp_path):
     assert u.size == man["unlab_probs_1"]["elements"] < 4 * 3 * 64 * 64 and np.isin(u, out["unlab_probs"][1].numpy()).all()
     for p in cut[0].glob("*.npy"):
         assert np.array_equal(np.load(p), np.load(cut[1] / p.name))
+
+
+# dct_conv2d_workspace_bytes for (B, Cin, H, W of the input, Cout), descriptor fields / planner knobs -> bytes.  The numbers were read from the
+# library as it stood before dct_conv2d got its one planner (plan_conv, csrc/igemm.hip), whose largest need over the routes this query returns.
+_CONV_WS_KNOBS = {"IGEMM_SPLIT": (1, -1), "IGEMM_HALO": (7, 1), "IGEMM_PACKED": (10, 1), "IGEMM_SPLIT_TARGET": (16, 450), "IGEMM_PACKED_SPLIT": (23, 160),
+                  "IGEMM_PACKED_FILL": (24, 50), "SPLIT_MAX_TILES": (1002, 96), "SPLIT_MIN_KITERS": (1003, 4)}      # name -> (knob, shipped value)
+_CONV_WS_TABLE = [
+    # per-tap, bf16: the split-K edges (tile-count threshold, K-step floor, forced factors, 2x2 stride 2)
+    ((2, 320, 12, 12, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0), 819200),
+    ((2, 320, 12, 12, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, IGEMM_SPLIT=2), 204800),
+    ((2, 320, 12, 12, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, IGEMM_SPLIT=4), 409600),
+    ((2, 320, 12, 12, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, IGEMM_SPLIT=7), 716800),
+    ((1, 192, 14, 14, 64), dict(IGEMM_HALO=0, IGEMM_PACKED=0, pad=1, IGEMM_SPLIT=5), 250880),
+    ((1, 64, 97, 130, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0), 12451840),
+    ((1, 64, 98, 130, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0), 0),
+    ((1, 64, 97, 130, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, SPLIT_MAX_TILES=95), 0),
+    ((1, 64, 98, 130, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, SPLIT_MAX_TILES=97), 12582912),
+    ((1, 192, 10, 10, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, R=1), 0),
+    ((1, 448, 10, 10, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, R=1), 0),
+    ((1, 512, 10, 10, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, R=1), 102400),
+    ((1, 448, 10, 10, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, R=1, SPLIT_MIN_KITERS=1), 0),
+    ((1, 512, 10, 10, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, R=1, SPLIT_MIN_KITERS=9), 0),
+    ((2, 128, 20, 18, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, R=2, stride=2, IGEMM_SPLIT=3), 276480),
+    ((2, 320, 12, 12, 128), dict(IGEMM_HALO=0, IGEMM_PACKED=0, IGEMM_SPLIT_TARGET=256), 819200),
+    # per-tap, fp32
+    ((1, 272, 12, 12, 64), dict(dtype=0), 409600),
+    ((1, 256, 12, 12, 128), dict(dtype=0), 819200),
+    ((1, 144, 12, 12, 64), dict(dtype=0), 358400),
+    ((2, 64, 40, 40, 128), dict(dtype=0), 13307904),
+    ((2, 32, 30, 30, 64), dict(dtype=0, IGEMM_SPLIT=11), 3612672),
+    ((2, 64, 258, 258, 64), dict(dtype=0), 0),
+    # shared halo: no workspace; with the stem's weight gradient one record per patch and the fold's scratch -- also where the layer
+    # cannot take it (the call then fails before it looks at the workspace)
+    ((8, 64, 254, 254, 64), dict(), 0),
+    ((4, 128, 83, 147, 128), dict(), 0),
+    ((3, 192, 98, 130, 256), dict(), 0),
+    ((16, 64, 258, 258, 64), dict(), 0),
+    ((8, 64, 254, 254, 64), dict(pad=2, stem=1), 10813440),
+    ((8, 64, 198, 198, 64), dict(pad=2, stem=1), 6983680),
+    ((4, 128, 83, 147, 128), dict(stem=1), 1454080),
+    ((2, 64, 12, 12, 64), dict(stem=1), 337920),
+    ((2, 64, 12, 12, 64), dict(stem=1, dtype=0), 460800),
+    # packed rows: channel-slice splits, beside a split or an unsplit per-tap plan (the larger need counts), and the knobs that move them
+    ((100, 576, 13, 13, 128), dict(), 30976000),
+    ((60, 896, 13, 13, 128), dict(), 29736960),
+    ((40, 1024, 13, 13, 256), dict(), 29736960),
+    ((20, 704, 27, 27, 128), dict(), 12800000),
+    ((16, 1024, 11, 11, 1024), dict(), 26542080),
+    ((16, 1024, 11, 11, 1024), dict(IGEMM_PACKED=0), 26542080),
+    ((16, 1024, 11, 11, 1024), dict(IGEMM_HALO=0), 26542080),
+    ((8, 512, 29, 29, 512), dict(), 0),
+    ((8, 512, 29, 29, 512), dict(IGEMM_PACKED_SPLIT=400), 23887872),
+    ((8, 512, 29, 29, 512), dict(IGEMM_PACKED_SPLIT=100), 0),
+    ((8, 1024, 11, 11, 1024), dict(), 21233664),
+    ((8, 1024, 11, 11, 1024), dict(IGEMM_PACKED_FILL=76), 21233664),
+    ((8, 1024, 11, 11, 1024), dict(IGEMM_SPLIT=2), 10616832),
+    ((2, 320, 12, 12, 128), dict(), 819200),
+    ((8, 256, 61, 61, 256), dict(), 0),
+    ((8, 256, 61, 61, 256), dict(IGEMM_PACKED_FILL=100), 0),
+    # the up-convolutions (2x2 scatter) and their data gradients
+    ((8, 1024, 9, 9, 512), dict(R=1, scatter=1), 0),
+    ((8, 128, 84, 84, 64), dict(R=1, scatter=1), 0),
+    ((8, 512, 18, 18, 1024), dict(R=2, stride=2), 21233664),
+    # channel counts no tile takes
+    ((2, 16, 12, 12, 64), dict(), 0),
+    ((2, 64, 12, 12, 32), dict(), 0),
+    ((2, 8, 12, 12, 64), dict(dtype=0), 0),
+]
+
+
+def test_conv2d_workspace_bytes_table():
+    """The planner's workspace size on every route and on both sides of the split edges.  The query reads shapes only: the views carry
+    made-up pointers, and dct_conv2d itself is never called with them."""
+    import ctypes as C
+    from dct_amd import _lib
+    lib = _lib.load()
+
+    def ws(B, Cin, H, W, Cout, R=3, stride=1, pad=0, dtype=_lib.BF16, scatter=0, stem=0, **knobs):
+        Ho, Wo = (2 * H, 2 * W) if scatter else ((H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1)
+        x = _lib.View(4096, B, H, W, Cin, H * W * Cin, W * Cin, Cin)
+        y = _lib.View(4096, B, Ho, Wo, Cout, Ho * Wo * Cout, Wo * Cout, Cout)
+        d = _lib.ConvDesc(R, R, stride, 1, pad, pad, 0, scatter, 0, 0, 1.0, None, None, None, None, 0, 4096 if stem else None, None, None, 0)
+        try:
+            for k, v in knobs.items():
+                assert lib.dct_tune_set(_CONV_WS_KNOBS[k][0], v) == 0, (k, v)
+            return lib.dct_conv2d_workspace_bytes(C.byref(x), C.byref(y), C.byref(d), dtype)
+        finally:
+            for k in knobs:
+                lib.dct_tune_set(*_CONV_WS_KNOBS[k])
+
+    got = [(shape, kw, ws(*shape, **kw)) for shape, kw, _ in _CONV_WS_TABLE]
+    assert got == _CONV_WS_TABLE, [(g, w[2]) for g, w in zip(got, _CONV_WS_TABLE) if g != w]
+    assert sum(1 for _, _, n in _CONV_WS_TABLE if n) >= 30 and sum(1 for _, _, n in _CONV_WS_TABLE if not n) >= 15
