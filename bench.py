@@ -3,13 +3,17 @@
 (BASELINE.json configs[1]: CE + JSD consistency, bs 8+8 per GPU, bf16), synthetic data.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N ranks through torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   (the same, then every leg behind the timed regions)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N --config cfg4 --global-batch 64+64   (fixed global batch split over the ranks: "scaling": "strong")
 
 A "step" is one pass of the hot path (CoTrainer._run_step) over one batch: 2 supervised
 forwards + CE, 2 unlabeled forwards + JSD, one backward through all four graphs, gradient
 all-reduce (N>1), fused Adam on both models.  Inputs are resident in HBM before the timed
-region.  Rank 0 prints ONE JSON line (contract in the task statement), including
+region.  Rank 0 prints ONE JSON line.  A plain run does what the headline figure needs and
+nothing else: set-up, W warm-up steps, the timed regions, `--dump-outputs`, the line.  `--full` then runs the legs that take
+steps or time of their own (shader clock beside the step, in-step meters, operand statistics, per-launch HIP events, the CPU
+oracle) and adds their figures to the line, among them
 
   roofline     : dominant conv kernel class -- algorithmic FLOPs / time in
                  that class measured with HIP events around every launch on its stream
@@ -331,7 +335,7 @@ class DryLegs:
 
 
 def measure(args, tr, one_step, legs, rank, world, ddp_on, meters_leg=None, operand_leg=None, enter_event_leg=None, last_step=None):
-    """W warm-up steps, the timed regions, and every leg behind them.  ONE rule keeps `--gpus N` from hanging: a leg that runs
+    """W warm-up steps, the timed regions, and (`--full`) every leg behind them.  ONE rule keeps `--gpus N` from hanging: a leg that runs
     `one_step` (which issues the gradient all-reduces when N > 1) is executed by EVERY rank; what is rank-conditional is only
     who records or prints.  (Round 4 ran the HIP-event leg on rank 0 alone while the other ranks went on to the barrier:
     mismatched collectives on one communicator.)  `--dry-launch` drives this same function on CPU with a collective counter per
@@ -381,6 +385,10 @@ def measure(args, tr, one_step, legs, rank, world, ddp_on, meters_leg=None, oper
                            "wire_dtype": "bf16" if args.grad_compress == "bf16" else "f32",
                            "mode": "captured graph segments around the eager all-reduces" if graphs is not None and graphs.captures
                            else "eager launches, bucketed all-reduce from inside the backward pass"}
+    if not args.full:                   # a plain run: the headline figure needs nothing below
+        if ddp_on:
+            dist.barrier()
+        return res
     base = args.warmup + args.steps * reps
     # The shader clock UNDER this load: the K steps once more (every rank: their all-reduces must meet) with one sleeping probe wave
     # beside them on rank 0, alive for ~80 % of the time the K steps take (the back-to-back single-layer loops of round 3's clock
@@ -466,7 +474,7 @@ def dry_launch(args, rank: int, world: int) -> None:
                                             "global_batch": f"{world}+{world}", "parallelism": f"dp{world}"},
             "losses_last_step": {"sup": [float(v) for v in out["sup"]], "jsd": float(out["jsd"])},
             "collectives": {"per_rank": [len(s) for s in sequences], "same_sequence_on_every_rank": all(s == sequences[0] for s in sequences),
-                            "behind_the_timed_region_legs": ["meters (world 1 only)", "operand stats (rank 0, no step)", "per-launch events"],
+                            "behind_the_timed_region_legs": ["meters (world 1 only)", "operand stats (rank 0, no step)", "per-launch events"] if args.full else [],
                             "event_leg_ran": res["prof"] is not None or rank != 0}}
     if ddp_on:
         dist.barrier()
@@ -489,17 +497,21 @@ def main():
     ap.add_argument("--net-attr", action="append", default=[], metavar="NAME=0|1", help="boolean switch of every network (relu_bits, pool_codes, ...) (A/B)")
     ap.add_argument("--force-ddp", action="store_true",
                     help="run the N > 1 code path (RCCL process group, gradient exchange, its report) even with one rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions, run every leg that takes steps or time of its own (shader clock, in-step meters, "
+                         "operand statistics, per-launch HIP events -> roofline, CPU oracle -> cpu_baseline) and report it in the line; "
+                         "off by default: a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU oracle's step")
     ap.add_argument("--train-steps", type=int, default=0,
                     help="extra (untimed) training steps before the warm-up: the timed network is then that many Adam steps old "
                          "(operand statistics of a trained net; profiles/r03_cfg2_after_300_steps.json)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket launches with HIP events")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: do not bracket launches with HIP events")
     ap.add_argument("--data", default="blob", choices=["blob", "iid"],
                     help="synthetic inputs: blob-structured slices the nets learn (default: the timed network then carries a training net's "
                          "operand statistics), or iid = torch.rand images + torch.randint labels as SURVEY.md 8d words it")
     ap.add_argument("--allow-nan", action="store_true",
                     help="diagnostic runs that skip kernel families (--tune 1100=MASK: garbage results, timing only): do not insist on finite losses")
-    ap.add_argument("--no-clock-probe", action="store_true", help="do not sample the shader clock beside the replayed step")
+    ap.add_argument("--no-clock-probe", action="store_true", help="--full: do not sample the shader clock beside the replayed step")
     ap.add_argument("--wgrad-stream", action="store_true", help="weight gradients on a second stream per model (eager only)")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from the host instead of replaying the captured step")
     ap.add_argument("--single-stream", action="store_true",
@@ -751,7 +763,7 @@ def main():
                 "step_level": {"achieved": alg_bytes / (ms_per_step * 1e-3) / 1e9, "unit": "GB/s",
                                "frac": alg_bytes / (ms_per_step * 1e-3) / 1e9 / 8000.0},
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(cfg)
     if ddp_on:
         # RCCL writes a version banner to stdout when a rank tears down: tear down first, then rank 0 prints the JSON line,

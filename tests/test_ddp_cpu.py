@@ -242,13 +242,13 @@ def _dry_bench(extra, timeout=850):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "2"
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch", "--steps", "1", "--warmup", "0"] + extra,
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch", "--full", "--steps", "1", "--warmup", "0"] + extra,
                           env=env, capture_output=True, text=True, timeout=timeout)
 
 
 @pytest.mark.timeout(900)
 def test_bench_launches_its_own_ranks(tmp_path):
-    """`python bench.py --gpus 2` (no launcher, WORLD_SIZE unset) must start its two ranks itself and leave ONE JSON line with
+    """`python bench.py --gpus 2 --full` (no launcher, WORLD_SIZE unset) must start its two ranks itself and leave ONE JSON line with
     n_gpus = 2 as the last line of its output: --dry-launch runs that path on CPU (gloo, oracle-injected networks) through the
     SAME `bench.measure()` the MI355X run uses -- warm-up, timed regions and every leg behind them (the per-launch event leg
     included, with a CPU stand-in for the profiler) -- and counts the collectives each rank issues: the sequences must agree."""

@@ -418,6 +418,27 @@ def test_bench_dump_outputs_writes_the_step_arrays(tmp_path):
         assert np.array_equal(np.load(p), np.load(cut[1] / p.name))
 
 
+def test_bench_plain_run_takes_no_step_behind_the_timed_regions():
+    """bench.py without --full: measure() runs the W warm-up steps and the timed regions over the same step indices as with --full, hands the
+    last timed step's outputs to --dump-outputs, and takes no further step, meter or profiler leg; --full runs them all after that."""
+    import argparse
+    import bench
+
+    def run(full):
+        calls, legs_run = [], []
+        args = argparse.Namespace(warmup=2, steps=3, repeats=3, full=full, no_clock_probe=False, no_kernel_events=False)
+        res = bench.measure(args, None, lambda i: calls.append(i) or {"i": i}, bench.DryLegs(), 0, 1, False,
+                            meters_leg=lambda base: legs_run.append("meters") or 1.0, operand_leg=lambda: legs_run.append("operand") or {},
+                            enter_event_leg=lambda: legs_run.append("events"), last_step=lambda out: legs_run.append(("dump", out["i"], len(calls))))
+        return calls, legs_run, res
+    calls, legs_run, res = run(False)
+    assert calls == list(range(2 + 3 * 3)) and legs_run == [("dump", 10, 11)] and res["out"] == {"i": 10}
+    assert res["prof"] is None and res["clock"] is None and res["meters_ms"] is None and res["operand_stats"] is None
+    fcalls, flegs, fres = run(True)
+    assert fcalls[:11] == calls and len(fcalls) == 11 + 3 + 3           # the clock leg's and the event leg's K steps
+    assert flegs == [("dump", 10, 11), "meters", "operand", "events"] and fres["prof"] is not None and fres["out"] == {"i": 10}
+
+
 # dct_conv2d_workspace_bytes for (B, Cin, H, W of the input, Cout), descriptor fields / planner knobs -> bytes.  The numbers were read from the
 # library as it stood before dct_conv2d got its one planner (plan_conv, csrc/igemm.hip), whose largest need over the routes this query returns.
 _CONV_WS_KNOBS = {"IGEMM_SPLIT": (1, -1), "IGEMM_HALO": (7, 1), "IGEMM_PACKED": (10, 1), "IGEMM_SPLIT_TARGET": (16, 450), "IGEMM_PACKED_SPLIT": (23, 160),

@@ -13,7 +13,7 @@ for rnd in $(seq 1 $R); do
       order) export DCT_LIB_PATH=$P/libdct_hip_ref.so; A="";;
       cur)   unset DCT_LIB_PATH; A="";;
     esac
-    timeout 600 python bench.py --config $C --steps 30 --warmup 10 --no-cpu-baseline $A 2>/dev/null | tail -1 | python -c "
+    timeout 600 python bench.py --config $C --steps 30 --warmup 10 --full --no-cpu-baseline $A 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$which round $rnd:', round(d['ms_per_step'],4), 'ms/step', d['roofline'].get('per_class_ms_per_step'))"
   done
 done

@@ -8,7 +8,8 @@ ROOT=$PWD
 for rnd in $(seq 1 $R); do
   for which in ref cur; do
     if [ $which = ref ]; then cd $ROOT/_ab_ref; else cd $ROOT; fi
-    timeout 600 python bench.py --config $C --steps 30 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+    F=$(grep -q -- '"--full"' bench.py && echo --full)       # (an export of a commit from before that option runs every leg without it)
+    timeout 600 python bench.py --config $C --steps 30 --warmup 10 $F --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$which round $rnd:', round(d['ms_per_step'],4), 'ms/step', d['roofline'].get('per_class_ms_per_step'))"
   done
 done

@@ -17,11 +17,11 @@ for c in cfg2; do
   python3 tools/pmc_mfma.py "$(find $O/m_$c -name "*counter_collection.csv" | head -1)" "$(find $O/m_$c -name "*kernel_trace.csv" | head -1)" > $O/${c}_pmc_mfma_busy.txt
 done
 timeout 600 python tools/bench_conv.py --batch 16 > $O/bench_conv_per_layer.txt 2>&1
-timeout 600 python bench.py --steps 30 --warmup 10 > $O/cfg2_bench.json 2> $O/bench.err
-timeout 600 python bench.py --config cfg3 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg3_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --config cfg4 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg4_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --config cfg5 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg5_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --config cfg5 --dtype f16 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg5_f16_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --config cfg4 --global-batch 64+64 --steps 20 --warmup 5 --no-cpu-baseline > $O/cfg4_global_batch_64_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --steps 30 --warmup 10 > $O/cfg2_bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --config cfg3 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg3_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --config cfg4 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg4_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --config cfg5 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg5_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --config cfg5 --dtype f16 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg5_f16_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --config cfg4 --global-batch 64+64 --steps 20 --warmup 5 --no-cpu-baseline > $O/cfg4_global_batch_64_bench.json 2>> $O/bench.err
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete; find $O -name "*.csv" -size +200k -delete
 ls $O

@@ -17,12 +17,12 @@ for c in cfg2 cfg3; do
   python3 tools/pmc_mfma.py "$(find $O/m_$c -name "*counter_collection.csv" | head -1)" > $O/${c}_pmc_mfma_busy.txt
 done
 timeout 600 python tools/bench_conv.py --batch 16 --plan > $O/bench_conv_per_layer.txt 2>&1
-timeout 600 python bench.py --steps 30 --warmup 10 > $O/cfg2_bench.json 2> $O/bench.err
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/cfg2_driver_command_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --steps 30 --warmup 10 --data iid --no-cpu-baseline > $O/cfg2_iid_inputs_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --config cfg3 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg3_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --config cfg4 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg4_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --config cfg4u --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg4_unet_200_bench.json 2>> $O/bench.err
-timeout 600 python bench.py --config cfg5 --dtype f16 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg5_f16_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --steps 30 --warmup 10 > $O/cfg2_bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/cfg2_driver_command_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --steps 30 --warmup 10 --data iid --no-cpu-baseline > $O/cfg2_iid_inputs_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --config cfg3 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg3_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --config cfg4 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg4_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --config cfg4u --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg4_unet_200_bench.json 2>> $O/bench.err
+timeout 600 python bench.py --full --config cfg5 --dtype f16 --steps 30 --warmup 10 --no-cpu-baseline > $O/cfg5_f16_bench.json 2>> $O/bench.err
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete; find $O -name "*.csv" -size +200k -delete
 ls $O
