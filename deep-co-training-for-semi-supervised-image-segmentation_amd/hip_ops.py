@@ -620,6 +620,24 @@ def dice_update(inter, psum, gsum, method3d, axes_mask, smooth, acc):
     return dice
 
 
+def hausdorff(logits_bhwc, gt_bhw, method3d=False, spacing=(1., 1., 1.)):
+    """logits [B, H, W, C] fp32 dense, gt [B, H, W] int64, spacing (sz, sy, sx) -> SQUARED Hausdorff distance fp32 [rows, C]
+    (rows = 1 for the batch as a volume, else B), NaN where the class is absent from the prediction or from gt (include/dct.h)."""
+    B, H, W, C_ = logits_bhwc.shape
+    # the kernels read 16 bytes at a time: a dense view that starts inside its storage (a slice of a larger batch) gets a copy of its own
+    if logits_bhwc.data_ptr() % 16:
+        logits_bhwc = logits_bhwc.clone()
+    if gt_bhw.data_ptr() % 16:
+        gt_bhw = gt_bhw.clone()
+    sz, sy, sx = (float(s) for s in spacing)
+    need = _lib.load().dct_hausdorff_workspace_bytes(B, H, W, C_, int(bool(method3d)))
+    ws = _ws(need, logits_bhwc.device)
+    hd2 = torch.empty(1 if method3d else B, C_, dtype=torch.float32, device=logits_bhwc.device)
+    call("dct_hausdorff", ptr(logits_bhwc), ptr(gt_bhw), B, H, W, C_, int(bool(method3d)), sz, sy, sx, ptr(hd2), ptr(ws), ws.numel(),
+         stream())
+    return hd2
+
+
 # ------------------------------------------------------------------------------ Enet family
 class Tf(object):
     """Producer transform act(scale*x + shift) applied by consumers on load (include/dct.h dct_enet_tf)."""

@@ -1,6 +1,7 @@
 """Meters used inside the step (reference: generalframework/metrics/dice_meter.py:12-83,
 averagemeter.py:3-48), kept on the device: ``add`` launches one counting kernel and never
-synchronises; ``value`` is where the (tiny) results are read."""
+synchronises; ``value`` is where the (tiny) results are read.  ``HausdorffMeter`` is the second column of the reference's
+result tables (Summary.py:70-252), which takes it from an external package: here ``dct_hausdorff`` (include/dct.h)."""
 from __future__ import annotations
 
 import math
@@ -9,7 +10,7 @@ import torch
 
 from .. import hip_ops as K
 
-__all__ = ["DiceMeter", "AverageValueMeter"]
+__all__ = ["DiceMeter", "HausdorffMeter", "AverageValueMeter"]
 
 
 class DiceMeter(object):
@@ -93,6 +94,88 @@ class DiceMeter(object):
     def summary(self) -> dict:
         (means, var), (_, _) = self.value()
         return {'mDSC': means.item(), 'mVars': var.item()}
+
+
+class HausdorffMeter(object):
+    """Hausdorff distance per class between the argmax of the prediction and gt (``dct_hausdorff``: medpy's ``hd`` rule),
+    '2d' = one row per slice, '3d' = one row for the batch taken as a volume; ``spacing`` = (sz, sy, sx).  A class that is
+    absent from the prediction or from gt has no distance: its entry is NaN in ``log``, is left out of every statistic and is
+    not counted in ``defined``.  Same layout as ``DiceMeter``."""
+
+    def __init__(self, method='2d', report_axises='all', C=4, spacing=(1., 1., 1.)) -> None:
+        assert method in ('2d', '3d')
+        assert report_axises == 'all' or isinstance(report_axises, list)
+        assert len(spacing) == 3 and all(float(s) > 0 for s in spacing), spacing
+        self.method = method
+        self.report_axis = report_axises
+        self.C = C
+        self.spacing = tuple(float(s) for s in spacing)
+        self.reset()
+
+    def reset(self):
+        self.hdLog = []
+        self._cache = None
+
+    def add(self, pred_logit: torch.Tensor, gt: torch.Tensor):
+        """pred_logit [B,C,H,W] (logits or probabilities: only the argmax matters), gt [B,1,H,W] integer."""
+        if not pred_logit.is_cuda or not gt.is_cuda:
+            raise RuntimeError("dct_amd HausdorffMeter measures on the HIP device only (no CPU fallback)")
+        B, H, W = pred_logit.shape[0], pred_logit.shape[2], pred_logit.shape[3]
+        lp = pred_logit.detach().permute(0, 2, 3, 1)
+        if lp.dtype != torch.float32 or not lp.is_contiguous():
+            lp = lp.to(torch.float32).contiguous()
+        g = gt.reshape(B, H, W)
+        if g.dtype != torch.int64 or not g.is_contiguous():
+            g = g.to(torch.int64).contiguous()
+        hd2 = K.hausdorff(lp, g, self.method == '3d', self.spacing)
+        self.hdLog.append(hd2.sqrt())           # NaN stays NaN; nothing here waits for the device
+        self._cache = None
+
+    @property
+    def log(self):
+        if self.hdLog:
+            return torch.cat(self.hdLog)
+        return torch.full((1, self.C), float('nan'))
+
+    def _stats(self):
+        # ONE device->host copy of the log per reading (cached until the next add); the NaN-aware moments are host arithmetic on
+        # rows x C numbers
+        if self._cache is None:
+            log = self.log.cpu().double()
+            axes = list(range(log.shape[1])) if self.report_axis == 'all' else list(self.report_axis)
+
+            def moments(v):         # over the defined entries of each column of v [n, k]
+                ok = ~torch.isnan(v)
+                n = ok.sum(0)
+                z = torch.where(ok, v, torch.zeros_like(v))
+                nan = torch.full((v.shape[1],), float('nan'), dtype=v.dtype)
+                mean = torch.where(n > 0, z.sum(0) / n.clamp_min(1), nan)
+                dev = torch.where(ok, v - mean, torch.zeros_like(v))
+                std = torch.where(n > 1, ((dev * dev).sum(0) / (n - 1).clamp_min(1)).sqrt(), nan)
+                return mean.float(), std.float(), n
+
+            mean, std, n = moments(log)
+            rep, _, _ = moments(log[:, axes].t().contiguous())      # a row's report value: the mean over its defined report axes
+            rmean, rstd, _ = moments(rep.double().unsqueeze(1))
+            self._cache = ((rmean[0], rstd[0]), (mean, std), n)
+        return self._cache
+
+    @property
+    def defined(self):
+        """Number of defined (non-NaN) entries per class."""
+        return self._stats()[2]
+
+    def value(self, **kwargs):
+        s = self._stats()
+        return s[0], s[1]
+
+    def detailed_summary(self) -> dict:
+        _, (means, _) = self.value()
+        return {f'HD{i}': means[i].item() for i in range(len(means))}
+
+    def summary(self) -> dict:
+        (means, var), (_, _) = self.value()
+        return {'mHD': means.item(), 'mVars': var.item()}
 
 
 class AverageValueMeter(object):

@@ -2,10 +2,12 @@
 
 ``load_model`` / ``load_models`` rebuild ``Segmentator``s from ``best_{i}.pth`` checkpoints exactly as Summary.py:70-79 does;
 ``Ensembleway`` is the soft / hard voting of :92-126; ``summarize`` is the evaluation loop of :148-172 + the result tables of
-:176-205 for the Dice part (2-D per slice and 3-D per patient batch, per model and for the ensemble).  Hausdorff distance
-(needs the external ``deepclustering`` package, absent from the reference tree) and the kappa table are out of scope.
+:176-205: Dice and, on request, Hausdorff distance (2-D per slice and 3-D per patient batch, per model and for the ensemble).
+The reference takes the Hausdorff distance from the external ``deepclustering`` package, absent from its tree; here it is
+medpy's ``metric.binary.hd`` rule as include/dct.h states it (``dct_hausdorff``).  The kappa table is out of scope.
 
-Predictions come from the HIP networks; voting and the Dice counting run on the device (``dct_dice_counts``)."""
+Predictions come from the HIP networks; voting, the Dice counting (``dct_dice_counts``) and the distance transform behind the
+Hausdorff distance (``dct_hausdorff``) run on the device."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -13,7 +15,7 @@ from typing import Dict, List, Optional
 import torch
 from torch import Tensor
 
-from .metrics import DiceMeter
+from .metrics import DiceMeter, HausdorffMeter
 from .models import Segmentator
 
 
@@ -60,8 +62,11 @@ class Ensembleway(object):
 
 @torch.no_grad()
 def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method: str = 'soft',
-              report_axises: Optional[List[int]] = None) -> Dict[str, dict]:
-    """Per-model and ensemble 2-D / 3-D Dice over a validation loader (batches ``[(img, gt), meta, names]``)."""
+              report_axises: Optional[List[int]] = None, hausdorff: bool = False, spacing=None) -> Dict[str, dict]:
+    """Per-model and ensemble 2-D / 3-D Dice over a validation loader (batches ``[(img, gt), meta, names]``): tables ``'2d'`` and
+    ``'3d'`` with keys ``DSC{j}``.  ``hausdorff=True`` adds the tables ``'hd_2d'`` and ``'hd_3d'`` with keys ``HD{j}``: mean (and
+    for the ensemble the std) of the Hausdorff distance over the slices / patient batches where class j is in both the
+    prediction and gt, NaN where it never is; ``spacing`` = (sz, sy, sx) of a voxel, default 1, 1, 1."""
     device = torch.device(device)
     C = models[0].arch_params['num_classes']
     axes = report_axises if report_axises is not None else list(range(C))
@@ -72,24 +77,29 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
     d2 = [DiceMeter(method='2d', report_axises=axes, C=C) for _ in models]
     d3 = [DiceMeter(method='3d', report_axises=axes, C=C) for _ in models]
     e2, e3 = DiceMeter(method='2d', report_axises=axes, C=C), DiceMeter(method='3d', report_axises=axes, C=C)
+    groups = [(d2, e2), (d3, e3)]
+    if hausdorff:
+        sp = tuple(spacing) if spacing is not None else (1., 1., 1.)
+        for method in ('2d', '3d'):
+            groups.append(([HausdorffMeter(method=method, report_axises=axes, C=C, spacing=sp) for _ in models],
+                           HausdorffMeter(method=method, report_axises=axes, C=C, spacing=sp)))
     for (img, gt), _, _ in val_dataloader:
         img, gt = img.to(device), gt.to(device)
         preds = [m.predict(img, logit=False) for m in models]
-        for j, p in enumerate(preds):
-            d2[j].add(p, gt)
-            d3[j].add(p, gt)
         v = ens(preds)
-        e2.add(v, gt)
-        e3.add(v, gt)
+        for per_model, ensemble in groups:
+            for j, p in enumerate(preds):
+                per_model[j].add(p, gt)
+            ensemble.add(v, gt)
 
-    def table(meter):
+    def table(meter, key):
         (_, _), (means, stds) = meter.value()
-        return {f'DSC{j}': float(means[j]) for j in range(C)}, {f'DSC{j}': float(stds[j]) for j in range(C)}
+        return {f'{key}{j}': float(means[j]) for j in range(C)}, {f'{key}{j}': float(stds[j]) for j in range(C)}
 
     out: Dict[str, dict] = {}
-    for name, meters in (("2d", (d2, e2)), ("3d", (d3, e3))):
-        res = {f'model_{i}': table(m)[0] for i, m in enumerate(meters[0])}
-        res['ensemble'] = table(meters[1])[0]
-        res['ensemble_std'] = table(meters[1])[1]
+    for name, key, meters in zip(("2d", "3d", "hd_2d", "hd_3d"), ("DSC", "DSC", "HD", "HD"), groups):
+        res = {f'model_{i}': table(m, key)[0] for i, m in enumerate(meters[0])}
+        res['ensemble'] = table(meters[1], key)[0]
+        res['ensemble_std'] = table(meters[1], key)[1]
         out[name] = res
     return out

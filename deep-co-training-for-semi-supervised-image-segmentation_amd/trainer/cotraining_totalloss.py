@@ -33,7 +33,7 @@ from torch import Tensor, nn
 
 from .. import ModelMode
 from .. import scheduler
-from ..metrics import AverageValueMeter, DiceMeter
+from ..metrics import AverageValueMeter, DiceMeter, HausdorffMeter
 from ..models import Segmentator
 from ..utils import iterator_, map_, dict_merge, tqdm_
 from ..utils.AEGenerator import FSGMGenerator
@@ -130,8 +130,13 @@ class CoTrainer(Trainer):
                  use_tqdm: bool = True,
                  whole_config=None,
                  steps_per_epoch: int = 300,
-                 grad_sync=None) -> None:
+                 grad_sync=None,
+                 val_hausdorff: bool = False,
+                 val_spacing=(1., 1., 1.)) -> None:
         self.max_epoch = max_epoch
+        # opt-in: _eval_loop also measures the 3-D Hausdorff distance per model (voxel spacing (sz, sy, sx)) and uploads it as 'val_hd'
+        self.val_hausdorff = bool(val_hausdorff)
+        self.val_spacing = tuple(val_spacing)
         self.segmentators = segmentators
         self.labeled_dataloaders = labeled_dataloaders
         self.unlabeled_dataloader = unlabeled_dataloader
@@ -1157,6 +1162,8 @@ class CoTrainer(Trainer):
         coefdiceMeters = [DiceMeter(report_axises=self.axises, method='2d', C=self.C) for _ in range(S)]
         batchdiceMeters = [DiceMeter(report_axises=self.axises, method='3d', C=self.C) for _ in range(S)]
         vallossMeters = [AverageValueMeter() for _ in range(S)]
+        hdMeters = [HausdorffMeter(report_axises=self.axises, method='3d', C=self.C, spacing=self.val_spacing)
+                    for _ in range(S)] if self.val_hausdorff else []
         val_iter = tqdm_(val_dataloader) if self.use_tqdm else val_dataloader
         for batch_num, [(img, gt), _, path] in enumerate(val_iter):
             img, gt = img.to(self.device), gt.to(self.device)
@@ -1166,10 +1173,15 @@ class CoTrainer(Trainer):
                 coefdiceMeters[i].add(preds[i], gt)
                 batchdiceMeters[i].add(preds[i], gt)
                 vallossMeters[i].add(loss[i].detach())
+                if hdMeters:
+                    hdMeters[i].add(preds[i], gt)
                 if save:
                     self._save_images(preds[i].max(1)[1], path, 'eval', epoch, str(i))
         dsc_dict = self._dsc_dict(batchdiceMeters)
         self.upload_dicts('val_data', dsc_dict, epoch)
+        if hdMeters:
+            vals = [m.value() for m in hdMeters]
+            self.upload_dicts('val_hd', {f"S{i}": {f"HD{n}": float(vals[i][1][0][n]) for n in self.axises} for i in range(S)}, epoch)
         nice_dict = self._report_dict(batchdiceMeters)
         if self._is_main():
             print(f"{desc} " + ', '.join([f'{k}_{k_}: {v[k_]:.2f}' for k, v in nice_dict.items() for k_ in v.keys()]))

@@ -464,6 +464,25 @@ int dct_dice_counts(const float* logits, const int64_t* gt, int B, int64_t pixel
 int dct_dice_update(const int32_t* inter, const int32_t* psum, const int32_t* gsum, int B, int C, int method3d,
                     uint32_t axes_mask, float smooth, float* dice, double* acc, dct_stream stream);
 
+/* ---- Hausdorff distance on device (the HD column of the result tables of Summary.py:70-252) -------------------
+ * The reference takes it from the external `deepclustering` package; the rule here is medpy's metric.binary.hd, per class c and
+ * per "row" (2-D: one slice; method3d: the whole batch as a volume):
+ *   P = pixels whose argmax is c (first maximum, as dct_argmax / dct_dice_counts); G = pixels with gt == c.  A gt value outside
+ *   [0, C) belongs to no class.
+ *   Surface of a mask = its pixels with a background neighbour among the 4 in-plane (2-D) / 6 (3-D) neighbours; everything outside
+ *   the array is background (a mask that fills the image has its frame as surface).
+ *   d2(p, q) = (sz dz)^2 + (sy dy)^2 + (sx dx)^2 (2-D ignores sz);  hd2 = max( max_{p in dP} min_{q in dG} d2, max_{q in dG} min_{p in dP} d2 ).
+ * hd2[rows][C] (rows = method3d ? 1 : B) receives the SQUARED distance, NaN where P or G is empty (medpy raises there).
+ * Exact separable distance transform (csrc/surface.hip): the cost does not depend on the masks.  fp32 on squared distances: with
+ * unit spacing every intermediate is an integer below 2^24 and the result is exact; it is bit-identical from run to run.
+ * logits, gt and workspace 16-byte aligned; the workspace needs no clearing by the caller.  DCT_ERR_BAD_ARG: null pointer, size < 1,
+ * spacing <= 0; DCT_ERR_UNSUPPORTED: C > 8, H or W > 1024, B > 256 in 3-D (B > 65535 in 2-D); DCT_ERR_WORKSPACE: workspace too
+ * small.  dct_hausdorff_workspace_bytes returns 0 for a shape dct_hausdorff refuses. */
+size_t dct_hausdorff_workspace_bytes(int B, int H, int W, int C, int method3d);
+int dct_hausdorff(const float* logits /*[B][H][W][C]*/, const int64_t* gt /*[B][H][W]*/,
+                  int B, int H, int W, int C, int method3d, float sz, float sy, float sx,
+                  float* hd2 /*[rows][C]*/, void* workspace, size_t workspace_bytes, dct_stream stream);
+
 /* ---- per-kernel-class timing (bench.py roofline leg) --------------------------------------
  * When enabled every launch made through this library is bracketed by hipEvents on its stream;
  * dct_prof_read synchronises and returns accumulated milliseconds and launch counts per class. */

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Where the in-step meters' time goes (diagnostic): DiceMeter.add / value on bench-shaped predictions, host and device time."""
+"""Where the in-step meters' time goes (diagnostic): DiceMeter.add / value on bench-shaped predictions, host and device time; then
+one HausdorffMeter.add (2-D and 3-D) beside one DiceMeter.add on the same 16 x 4 x 256 x 256 batch, device time between events."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
-from dct_amd.metrics import DiceMeter
+from dct_amd.metrics import DiceMeter, HausdorffMeter
 dev = "cuda:0"
 B, C, H = 8, 4, 256
 pred = torch.randn(B, H, H, C, device=dev).permute(0, 3, 1, 2)
@@ -33,3 +34,40 @@ for what, fn in (("synchronize()", lambda: torch.cuda.synchronize()), (".item()"
         x.add_(1.0)
         fn()
     print(f"{what}: {1e6 * (time.perf_counter() - t0) / 50:.1f} us per (tiny kernel + call)")
+
+
+# ---- one add in isolation, device time (events around each call, warm-up first, median of 20) ----------------------------------
+def blobs(B, C, H, seed):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    f = torch.randn(B, C, H, H, device=dev, generator=g)
+    for _ in range(8):          # smoothed noise: the argmax is a map of blobs
+        f = torch.nn.functional.avg_pool2d(f, 5, stride=1, padding=2, count_include_pad=False)
+    return f
+
+
+def event_us(fn, warm=5, reps=20):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(1e3 * a.elapsed_time(b))
+    ts.sort()
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+B, C, H = 16, 4, 256
+for name, pred, gt in (("blobs", blobs(B, C, H, 1), blobs(B, C, H, 2).max(1, keepdim=True)[1]),
+                       ("noise", torch.randn(B, C, H, H, device=dev), torch.randint(0, C, (B, 1, H, H), device=dev))):
+    legs = [("DiceMeter.add 2d", DiceMeter(method="2d", report_axises=[1, 2, 3], C=C)),
+            ("HausdorffMeter.add 2d", HausdorffMeter(method="2d", report_axises=[1, 2, 3], C=C)),
+            ("HausdorffMeter.add 3d", HausdorffMeter(method="3d", report_axises=[1, 2, 3], C=C))]
+    for what, meter in legs:
+        med, lo, hi = event_us(lambda: meter.add(pred, gt))
+        meter.reset()
+        print(f"{B}x{C}x{H}x{H} {name}: {what}: median {med:.1f} us (min {lo:.1f}, max {hi:.1f}; 20 calls, events, after 5 warm-up calls)")
