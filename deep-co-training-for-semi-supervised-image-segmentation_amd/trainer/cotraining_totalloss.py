@@ -37,6 +37,8 @@ from ..metrics import AverageValueMeter, DiceMeter, HausdorffMeter
 from ..models import Segmentator
 from ..utils import iterator_, map_, dict_merge, tqdm_
 from ..utils.AEGenerator import FSGMGenerator
+from . import step_route
+from .step_route import NetFacts, StepFacts, plan_execution, plan_step
 from .stream_sched import EagerSchedule, StreamDealer, own_stream
 from .trainer import Trainer
 
@@ -87,8 +89,9 @@ def _make_writer(save_dir):
 @dataclasses.dataclass
 class ExecutionPlan:
     """Layout switches of the fused step (none changes a result bit; each is an A/B handle whose default is the measured optimum --
-    DESIGN.md 4.3).  ``CoTrainer.<name>`` reads and writes the field of the same name (``tr.model_streams = False`` still works)."""
-    batch_lab_unlab: bool = True        # one B_l+B_u pass per batch-independent net (see _run_step_fused)
+    DESIGN.md 4.3).  ``CoTrainer.<name>`` reads and writes the field of the same name (``tr.model_streams = False`` still works).
+    They are read where the step is routed (trainer/step_route.py) and by the stream pools, nowhere else."""
+    batch_lab_unlab: bool = True        # one B_l+B_u pass per batch-independent net (see _run_step_sequential)
     model_streams: bool = True          # one HIP stream per model in the fused step (see _streams)
     spread_streams: bool = True         # deal the model / pass streams over different hardware queues (stream_sched.queue_groups)
     pass_streams: bool = True           # nets that support it (Enet): the backward passes of one model run on separate streams
@@ -97,6 +100,8 @@ class ExecutionPlan:
     group_passes: bool = True           # ... and issue the 2S co-training passes as grouped launches where the networks can (Enet)
     wide_forward: bool = True           # networks with deferred running statistics: lay the step out on four hardware queues (_run_step_wide)
     adv_chain_layout: bool = True       # two batch-independent networks (UNet) with FGSM: see _run_step_adv_chain
+    fgsm_shares_encoder: bool = True    # ... the FGSM generator's forward pass takes the encoder of b's joint pass from its tape
+    adv_chain_late_b: int = 2           # ... model b's backward pass behind the JSD (0), the adversarial batch (1), model a's adversarial forward pass (2)
     early_backward: bool = True         # start the labeled / unlabeled backward passes right after the JSD, beside the adversarial block
     grad_overwrite: bool = True         # nets that support it: first backward pass of a step writes the gradients (no zero fill)
     segmented_graphs: Optional[bool] = None   # capture the step as one graph per stream segment (different hardware queues) instead of one
@@ -105,6 +110,30 @@ class ExecutionPlan:
     use_hip_graph: bool = True          # replay the fused step from a captured HIP graph (trainer/step_graph.py)
     ddp_segmented_graph: bool = True    # data parallelism: replay the step as graph segments around the eager all-reduces
     force_loss_scale: Optional[float] = None  # tests: a power of two applied to every loss gradient and divided out by the optimizers
+
+
+class _StepContext(object):
+    """What one issue of the step carries from its forward passes to its optimizers; dropped when the step returns (the join closure
+    holds this step's streams, the pass buffers' owners its tapes)."""
+    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore")
+
+    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None):
+        self.sched, self.route = sched, route
+        # the gradient exchange as far as it is issued from inside the step (between two graphs it is the replay's business)
+        self.sync = grad_sync if any(e in ("model", "buckets") for e in route.exchange) else None
+        self.join = None                    # every stream of the layout joins the origin stream
+        self.early, self.pending = {}, {}   # model -> (flat parameters, pass buffers): queued before / awaiting the sum in _finish_step
+        gs = self.loss_scale = route.loss_scale
+        self.grad_unscale = 1.0 / gs
+        self.lam_cot, self.lam_adv = lam
+        # captured steps read the loss weights on the device (``lam_dev``: float32[2] holding lambda_cot, lambda_adv)
+        self.g_cot = dict(gscale=lam_dev[0:1], gmul=gs) if lam_dev is not None else dict(gmul=lam[0] * gs)
+        self.g_adv = dict(gscale=lam_dev[1:2], gmul=gs) if lam_dev is not None else dict(gmul=lam[1] * gs)
+        self.ignore = ignore
+
+    def on(self, streams, i):
+        """Model i's stream of ``streams`` as the current one (no-op without streams, or for the joint backward of the generic step)."""
+        return self.sched.on(streams[i]) if streams is not None and i is not None else contextlib.nullcontext()
 
 
 def _plan_property(name):
@@ -187,12 +216,10 @@ class CoTrainer(Trainer):
         self._pass_pool = None
         self._pass_bufs = {}
         self._qstreams = None
-        self._step_hint_adv_chain = False
-        self._overwrite_models = set()
-        self._pass_early = {}
+        self._group_max = None
         self._step_graphs = None
         self.last_step = None
-        self._defer_optimizer = False       # segmented capture: _finish_step stops after the backward passes (see _optimizer_phase)
+        self.last_route = None              # the StepRoute of the last step issued (trainer/step_route.py)
 
     def to(self, device: torch.device):
         [segmentator.to(device) for segmentator in self.segmentators]
@@ -243,14 +270,47 @@ class CoTrainer(Trainer):
                       index_label="epoch")
 
     # ------------------------------------------------------------------------------ the step
+    def _step_facts(self, lab=(), unl=None, train_jsd=False, train_adv=False, adv_choice=None) -> StepFacts:
+        """Everything the route of a step depends on (trainer/step_route.py), read once."""
+        def net_facts(net):
+            flat = getattr(net, "flat_params", None)
+            return NetFacts(plan_net=flat is not None and hasattr(net, "plan_forward"), grad_buckets=hasattr(net, "grad_bucket_ranges"),
+                            grads_attached=bool(flat is not None and flat.grads_attached()),
+                            dropout_masks_set=getattr(net, "external_dropout_masks", None) is not None,
+                            fp16=getattr(net, "compute_dtype", None) == torch.float16,
+                            **{f: bool(getattr(net, f, False)) for f in step_route.NET_ATTRS})
+        nets = tuple(net_facts(s.torchnet) for s in self.segmentators)
+        gpu = self.device.type == 'cuda'
+        fused_criteria = False
+        if gpu:
+            from ..loss.loss import CrossEntropyLoss2d, JSD_2D
+            fused_criteria = type(self.criterions['sup']) is CrossEntropyLoss2d and type(self.criterions['jsd']) is JSD_2D
+        if self._group_max is None and gpu and all(n.plan_net and n.supports_pass_groups for n in nets):
+            from .. import hip_ops as K
+            self._group_max = K.group_max()
+        shapes = [tuple(b[0].shape) for b in lab]
+        return StepFacts(
+            S=len(nets), nets=nets, train_jsd=bool(train_jsd), train_adv=bool(train_adv),
+            adv_choice=tuple(adv_choice) if adv_choice is not None else None, unlabeled=unl is not None,
+            labeled_shapes_equal=len(set(shapes)) <= 1,
+            labeled_equals_unlabeled=bool(shapes) and unl is not None and shapes[0] == tuple(unl[0].shape),
+            labeled_pixels=shapes[0][0] * shapes[0][2] * shapes[0][3] if shapes and len(shapes[0]) == 4 else 0,
+            lam_cot_zero=float(self.cot_scheduler.value) == 0.0, lam_adv_zero=float(self.adv_scheduler.value) == 0.0,
+            gpu=gpu, fused_criteria=fused_criteria, ddp=self.grad_sync is not None,
+            # replay needs every per-step scalar on the device: only the fused Adam keeps its step count / lr there
+            optimizers_graphable=all(hasattr(s.optimizer, "refresh_lr") and hasattr(s.optimizer, "_steps") for s in self.segmentators),
+            group_max=self._group_max or 0)
+
     def _fused_ok(self) -> bool:
-        from ..loss.loss import CrossEntropyLoss2d, JSD_2D
-        if self.device.type != 'cuda':
-            return False
-        if type(self.criterions['sup']) is not CrossEntropyLoss2d or type(self.criterions['jsd']) is not JSD_2D:
-            return False
-        return all(hasattr(s.torchnet, "flat_params") and hasattr(s.torchnet, "plan_forward")
-                   for s in self.segmentators) and len(self.segmentators) <= 8
+        return step_route.fused(self._step_facts())
+
+    def _four_queues(self) -> bool:
+        return self._queue_streams() is not None
+
+    # what the last step was routed by (bench.py and the tests read these)
+    _step_hint_adv_chain = property(lambda self: bool(self.last_route is not None and self.last_route.adv_chain_eligible))
+    _loss_scale = property(lambda self: self.last_route.loss_scale if self.last_route is not None else 1.0)
+    _grad_unscale = property(lambda self: 1.0 / self._loss_scale)
 
     def _draw_adv_choice(self) -> Tuple[int, int]:
         S = len(self.segmentators)
@@ -281,32 +341,23 @@ class CoTrainer(Trainer):
         unl = None
         if unlab_batch is not None and (train_jsd or train_adv):
             unl = (_img(unlab_batch[0]), _gt(unlab_batch[1]) if unlab_batch[1] is not None else None)
-        self._step_hint_adv_chain = bool(
-            self.adv_chain_layout and train_jsd and train_adv and unl is not None and adv_choice is not None and
-            len(self.segmentators) == 2 and adv_choice[0] != adv_choice[1] and self.batch_lab_unlab and self.model_streams and
-            self.grad_sync is None and
-            all(getattr(s.torchnet, "batch_independent", False) and getattr(s.torchnet, "supports_grad_overwrite", False) and
-                getattr(s.torchnet, "external_dropout_masks", None) is None for s in self.segmentators))
-        if self._fused_ok():
-            # replay needs every per-step scalar on the device: only the fused Adam keeps its step count / lr there
-            graphable = all(hasattr(s.optimizer, "refresh_lr") and hasattr(s.optimizer, "_steps") for s in self.segmentators)
-            # data parallelism: the RCCL all-reduces are not captured.  The step is recorded as a program of graph segments
-            # (trainer/stream_sched.py) in which every gradient exchange -- UNet's buckets handed out from inside the backward
-            # pass, Enet's one buffer per model -- is a host callback between two segments
-            segmented = self.grad_sync is not None and self.ddp_segmented_graph
-            if self.use_hip_graph and graphable and (self.grad_sync is None or segmented) and \
-                    all(s.torchnet.training for s in self.segmentators):
-                if self._step_graphs is None:
-                    from .step_graph import StepGraphCache
-                    self._step_graphs = StepGraphCache(self)
-                out = self._step_graphs.run(lab, unl, train_jsd, train_adv, adv_choice)
-            else:
-                out = self._run_step_fused(lab, unl, train_jsd, train_adv, adv_choice)
+        # the route: how the step is replayed, and what one issue of it under that mode does (trainer/step_route.py)
+        facts = self._step_facts(lab, unl, train_jsd, train_adv, adv_choice)
+        execution = plan_execution(self.plan, facts)
+        self.last_route = route = plan_step(self.plan, facts, "eager" if execution == "generic" else execution, self._four_queues)
+        if execution == "generic":
+            out = self._run_step_generic(lab, unl, train_jsd, train_adv, adv_choice, route)
+        elif execution == "eager":
+            out = self._run_step_fused(lab, unl, train_jsd, train_adv, adv_choice, route)
         else:
-            out = self._run_step_generic(lab, unl, train_jsd, train_adv, adv_choice)
+            if self._step_graphs is None:
+                from .step_graph import StepGraphCache
+                self._step_graphs = StepGraphCache(self)
+            out = self._step_graphs.run(lab, unl, train_jsd, train_adv, adv_choice, facts, execution, route)
         self.last_step = out
         return out
 
+    # ---- stream pools
     def _streams(self):
         """One HIP stream per model for the fused step, or None.  The S networks are independent between the
         points where the losses couple them (JSD, the FGSM hand-over), and many of their launches cannot fill
@@ -320,13 +371,9 @@ class CoTrainer(Trainer):
         return self._stream_pool
 
     def _use_segments(self) -> bool:
-        if self.segmented_graphs is not None:
-            return bool(self.segmented_graphs)
-        if self._step_hint_adv_chain:
-            return True         # two batch-independent nets + FGSM: the adversarial chain gets a hardware queue (_run_step_adv_chain)
-        if self.grad_sync is not None and self.ddp_segmented_graph:
-            return True         # data parallelism: the gradient exchanges are host callbacks BETWEEN graph segments
-        return any(getattr(seg.torchnet, "prefers_segmented_graphs", False) for seg in self.segmentators)
+        # (the stream pools ask between steps: the adversarial-chain hint is the LAST step's, as it always was -- the one decision still
+        #  read back from trainer state)
+        return step_route.segmented(self.plan, self._step_facts(), self._step_hint_adv_chain)
 
     def _stream_dealer(self):
         if not self.spread_streams or self.device.type != 'cuda' or not self._use_segments():
@@ -335,10 +382,6 @@ class CoTrainer(Trainer):
             self._dealer = StreamDealer(self.device)
         return self._dealer
 
-    def _pass_parallel_ok(self, net, model_passes, streams) -> bool:
-        return bool(self.pass_streams and streams is not None and 1 < len(model_passes) <= 3 and
-                    getattr(net, "supports_pass_streams", False))
-
     def _pass_streams_for(self, i, n):
         if self._pass_pool is None:
             self._pass_pool = {}
@@ -346,6 +389,14 @@ class CoTrainer(Trainer):
         while len(pool) < n:
             pool.append(_pooled_stream(self.device, "pass", i, len(pool), dealer=self._stream_dealer()))
         return pool[:n]
+
+    def _queue_streams(self):
+        """One stream per hardware queue (stream_sched.queue_groups), or None when the probe found fewer than four."""
+        if self._qstreams is None:
+            from .stream_sched import queue_groups
+            groups = queue_groups(self.device)
+            self._qstreams = [g[0] for g in groups][:4] if len(groups) >= 4 else False
+        return self._qstreams or None
 
     def _pass_buffer(self, i, k, fp):
         """Flat gradient buffer of backward pass k of model i (eager steps reuse it; a capture takes it from the graph's pool)."""
@@ -358,24 +409,75 @@ class CoTrainer(Trainer):
                 self._pass_bufs[key] = buf
         return buf
 
-    def _start_passes(self, i, net, model_passes, side_streams, bufs):
+    # ---- launch fragments every layout shares
+    def _start_passes(self, ctx, i, net, model_passes, side_streams, bufs):
         """Queue backward passes of model i on ``side_streams`` (which already wait for the passes' inputs), each into its own
         gradient buffer appended to ``bufs``.  -> (flat parameters, bufs)."""
         fp = net.flat_params
         for (tape, dl), st in zip(model_passes, side_streams):
             buf = self._pass_buffer(i, len(bufs), fp)
             bufs.append(buf)
-            with self._sched.on(st):
+            with ctx.sched.on(st):
                 buf.zero_()
                 net.plan_backward(tape, dl, need_dx=False, need_dw=True, grad_buffer=buf)
         return fp, bufs
+
+    def _ce(self, ctx, lp, gt, dl):
+        """Cross entropy of the labeled logits: loss value + count and the logit gradient into ``dl`` (two launches).  -> (value, NCHW logits)."""
+        from .. import hip_ops as K
+        from ..loss.loss import _nchw
+        out = K.ce_step(lp, gt.reshape(-1), self.C, dl, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
+        return out[0], _nchw(lp)
+
+    def _forward_ce(self, ctx, net, x, gt, B_l=None, **fwd):
+        """Forward pass over ``x`` and the cross entropy of its labeled rows (the first ``B_l``; all of them when None).
+        -> (tape, logits, logit gradients [the labeled rows filled], loss value, NCHW labeled logits)."""
+        lp_all, tape = net.plan_forward(x, True, **fwd)
+        dl_all = torch.empty_like(lp_all)
+        lp, dl = (lp_all, dl_all) if B_l is None else (lp_all[:B_l], dl_all[:B_l])
+        sup, pred = self._ce(ctx, lp, gt, dl)
+        return tape, lp_all, dl_all, sup, pred
+
+    def _jsd(self, ctx, lps, dl_outs):
+        """Value, the S softmax maps and the S logit gradients in ONE pass over the logits (dct_jsd_logits_step: bit for bit the five
+        separate launches).  -> (value, NCHW softmax maps)."""
+        from .. import hip_ops as K
+        from ..loss.loss import _nchw
+        jsd1, probs = K.jsd_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot)
+        return jsd1[0], [_nchw(p_) for p_ in probs]
+
+    def _adv_forward_kl(self, ctx, net, x_adv, lp_real, **fwd):
+        """Model a's forward pass on the perturbed batch and KL against the detached clean logits of model b.
+        -> (value, tape, logit gradient or None when lambda_adv is 0)."""
+        from .. import hip_ops as K
+        lp_adv, tape = net.plan_forward(x_adv, True, **fwd)
+        adv = K.kl_logits_fwd(lp_adv, lp_real, self.C)[0]
+        da = K.kl_logits_bwd(lp_adv, lp_real, self.C, torch.empty_like(lp_adv), **ctx.g_adv) if ctx.lam_adv != 0.0 else None
+        return adv, tape, da
+
+    def _fgsm_fused(self, ctx, net, x, gt, **fwd):
+        """FSGMGenerator (AEGenerator.py:16-51) on the fused kernels: forward, pseudo-label the
+        unlabeled tail, CE, backward to the input only, x + eps*sign(g).  Returns the physical
+        NHWC logits of the clean pass (their softmax is the detached KL target) and the tape."""
+        from .. import hip_ops as K
+        C = self.C
+        eps = float(self.adv_training_dict.get('eplision', 0.05))
+        lp, tape = net.plan_forward(x, True, **fwd)
+        t = gt.reshape(-1)
+        if x.shape[0] > gt.shape[0]:
+            pseudo = K.argmax(lp, C)
+            t = torch.cat((t, pseudo[t.numel():]))
+        # only the sign of the input gradient is used: the (power-of-two) scale keeps it out of half's subnormals
+        dl = torch.empty_like(lp)
+        K.ce_step(lp, t, C, dl, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
+        gx = net.plan_backward(tape, dl, need_dx=True, need_dw=False)
+        x_adv, noise = K.fgsm_step(x.detach().contiguous(), gx.contiguous(), eps)
+        return x_adv, noise, lp, tape
 
     # Diagnostic (tools/phase_stamps.py): with ``self.phase_stamps`` = a zeroed int64 device tensor [S, 4, 1 + PHASE_RING], one-thread stamp
     # launches date the phases of the step on each model's stream (site k = 0 forward starts, 1 forward + loss done, 2 backward done,
     # 3 optimizer done) into a ring per site.  They are kernel nodes: a captured step replays them, so pipelined replays leave a timeline.
     phase_stamps = None
-    fgsm_shares_encoder = True         # three-queue adversarial step: the FGSM generator's forward pass takes the encoder of b's joint pass from its tape
-    adv_chain_late_b = 2            # three-queue adversarial step: model b's backward pass behind the JSD (0), the adversarial batch (1), model a's adversarial forward pass (2)
     PHASE_RING = 64
 
     def _stamp(self, model: int, k: int):
@@ -385,32 +487,34 @@ class CoTrainer(Trainer):
         from .. import _lib
         _lib.check(_lib.load().dct_stamp(buf[model, k].data_ptr(), self.PHASE_RING, torch.cuda.current_stream(self.device).cuda_stream), "dct_stamp")
 
-    def _finish_step(self, backward_calls, streams=None):
+    def _finish_step(self, ctx, backward_calls, streams=None):
         """zero_grad (after the forwards, :245) -> backward (:246-247) -> [gradient all-reduce] -> step (:248).
         ``backward_calls``: list of (model index or None, callable).  With data parallelism each
         model's all-reduce starts as soon as its backward is enqueued and overlaps the next one.
         With ``streams`` model i's zero_grad / backward / all-reduce / Adam are all queued on streams[i]."""
+        sched, sync = ctx.sched, ctx.sync
+
         def on(i):
-            return self._sched.on(streams[i]) if streams is not None and i is not None else contextlib.nullcontext()
+            return ctx.on(streams, i)
         for i, seg in enumerate(self.segmentators):
-            if i in self._overwrite_models:      # the first backward pass of this model writes every gradient element
+            if ctx.route.overwrite[i] != "none":      # the backward passes of this model write every gradient element
                 continue
             with on(i):
                 seg.optimizer.zero_grad()
-        self._pass_pending = dict(getattr(self, "_pass_early", None) or {})      # passes already queued beside the adversarial block
+        ctx.pending = dict(ctx.early)                 # passes already queued beside the adversarial block
         for idx, call in backward_calls:
             with on(idx):
                 call()
                 if idx is not None:
                     self._stamp(idx, 2)
-                if self.grad_sync is not None and idx is not None and idx not in self._pass_pending:
-                    self._sched.call(lambda idx=idx: self.grad_sync.begin(idx))
-        if self._pass_pending:
+                if sync is not None and idx is not None and idx not in ctx.pending:
+                    sched.call(lambda idx=idx: sync.begin(idx))
+        if ctx.pending:
             # some backward passes ran on their own streams into their own gradient buffers: every stream joins the origin
-            # stream (never a forked one: see _run_step_fused), the buffers are added there in pass order, and what follows
+            # stream (never a forked one: see _run_step_sequential), the buffers are added there in pass order, and what follows
             # (gradient exchange, optimizers) is queued on the origin stream
-            self._pass_join()
-            for idx, (flat, bufs) in sorted(self._pass_pending.items()):
+            ctx.join()
+            for idx, (flat, bufs) in sorted(ctx.pending.items()):
                 from .. import hip_ops as K
                 if len(bufs) == 1:
                     flat.gflat.copy_(bufs[0])
@@ -420,38 +524,40 @@ class CoTrainer(Trainer):
                     torch.add(bufs[0], bufs[1], out=flat.gflat)
                     for buf in bufs[2:]:
                         flat.gflat.add_(buf)
-                if self.grad_sync is not None:
-                    self._sched.call(lambda idx=idx: self.grad_sync.begin(idx))
+                if sync is not None:
+                    sched.call(lambda idx=idx: sync.begin(idx))
             streams = None
-            self._pass_pending = {}
-        if self._defer_optimizer:
+            ctx.pending = {}
+        if ctx.route.defer_optimizer:                 # the first of two graphs ends here (see _optimizer_phase)
             return
-        if self.grad_sync is not None and any(idx is None for idx, _ in backward_calls):
-            self._sched.call(lambda: self.grad_sync.all_reduce())
-        self._optimizer_phase(streams)
+        if sync is not None and any(idx is None for idx, _ in backward_calls):
+            sched.call(lambda: sync.all_reduce())
+        self._optimizer_phase(ctx, streams)
 
-    def _optimizer_phase(self, streams=None):
+    def _optimizer_graph_phase(self, route):
+        """The second of two graphs: the optimizer steps alone (the exchange between the two is the replay's business)."""
+        self._optimizer_phase(_StepContext(self._sched, route))
+
+    def _optimizer_phase(self, ctx, streams=None):
         """[wait for model i's gradient exchange] -> optimizer step (:248), per model on its stream."""
-        def on(i):
-            return self._sched.on(streams[i]) if streams is not None else contextlib.nullcontext()
-        unscale = getattr(self, "_grad_unscale", 1.0)
-        sync = self.grad_sync if self.grad_sync is not None else getattr(self, "_opt_phase_sync", None)
+        sched, sync = ctx.sched, ctx.sync
         for i, seg in enumerate(self.segmentators):
-            with on(i):
-                if self.grad_sync is not None:
-                    self._sched.call(lambda i=i: self.grad_sync.finish(i))     # model i's all-reduce only: later ones overlap this Adam launch
+            with ctx.on(streams, i):
+                if sync is not None:
+                    sched.call(lambda i=i: sync.finish(i))     # model i's all-reduce only: later ones overlap this Adam launch
                 if hasattr(seg.optimizer, "grad_scale"):
-                    # fused Adam: the inverse loss scale and, under data parallelism, the 1/world of the gradient average
-                    # (the exchange is a SUM: ddp.py) are folded into the update
-                    seg.optimizer.grad_scale = unscale * (sync.optimizer_scale(i) if hasattr(sync, "optimizer_scale") else 1.0)
-                elif unscale != 1.0:
+                    # fused Adam: the inverse loss scale and, under data parallelism (an exchange between two graphs included), the
+                    # 1/world of the gradient average (the exchange is a SUM: ddp.py) are folded into the update
+                    scaler = self.grad_sync if ctx.route.exchange[i] != "none" else None
+                    seg.optimizer.grad_scale = ctx.grad_unscale * (scaler.optimizer_scale(i) if hasattr(scaler, "optimizer_scale") else 1.0)
+                elif ctx.grad_unscale != 1.0:
                     flat = getattr(seg.torchnet, "flat_params", None)
                     if flat is not None and flat.grads_attached():
-                        flat.gflat.mul_(unscale)
+                        flat.gflat.mul_(ctx.grad_unscale)
                 seg.optimizer.step()
                 self._stamp(i, 3)
 
-    def _run_step_generic(self, lab, unl, train_jsd, train_adv, adv_choice) -> dict:
+    def _run_step_generic(self, lab, unl, train_jsd, train_adv, adv_choice, route=None) -> dict:
         S = len(self.segmentators)
         supervisedLoss, jsdLoss, advLoss = 0, 0, 0
         sup, preds, unlab_preds = [], [], []
@@ -470,89 +576,72 @@ class CoTrainer(Trainer):
             advLoss = self._adv_from_batches((self.segmentators[a], self.segmentators[b]), lab[b], unl[0],
                                              **self.adv_training_dict)
         totalLoss = supervisedLoss + self.cot_scheduler.value * jsdLoss + self.adv_scheduler.value * advLoss
-        self._grad_unscale = 1.0
-        self._finish_step([(None, totalLoss.backward)])
+        route = route or plan_step(self.plan, self._step_facts(lab, unl, train_jsd, train_adv, adv_choice), "eager", self._four_queues)
+        ctx = _StepContext(self._sched, route, self.grad_sync)
+        self._finish_step(ctx, [(None, totalLoss.backward)])
         return dict(sup=sup, jsd=jsdLoss.detach() if train_jsd else 0, adv=advLoss.detach() if train_adv else 0,
                     preds=preds, unlab_probs=[p.detach() for p in unlab_preds])
 
-    def _run_step_fused(self, lab, unl, train_jsd, train_adv, adv_choice, lam_dev=None) -> dict:
+    def _run_step_fused(self, lab, unl, train_jsd, train_adv, adv_choice, route, lam_dev=None) -> dict:
         """The step as one launch sequence over the networks' execution plans (plan_forward / plan_backward: no
-        autograd graph), the fused loss kernels and the flat Adam.  ``lam_dev`` (float32[2] device tensor holding
-        lambda_cot, lambda_adv): the loss weights are then read on the device, as a captured graph needs."""
-        from .. import hip_ops as K
-        from ..loss.loss import _nchw
-        S, C = len(self.segmentators), self.C
+        autograd graph), the fused loss kernels and the flat Adam, laid out as ``route`` says (trainer/step_route.py).
+        ``lam_dev`` (float32[2] device tensor holding lambda_cot, lambda_adv): the loss weights are then read on the
+        device, as a captured graph needs."""
         nets = [s.torchnet for s in self.segmentators]
-        ignore = self.criterions['sup'].ignore_index
-        lam_cot, lam_adv = float(self.cot_scheduler.value), float(self.adv_scheduler.value)
-        # fp16 networks: per-pixel gradients of a mean over ~1e6 pixels sit in half's subnormal range, so every loss
-        # gradient is scaled by a power of two (>= the pixel count of a labeled batch) and the optimizers divide it out again
-        # (include/dct.h, DCT_F16).  1.0 -- and bit-identical arithmetic -- for bf16 / fp32 networks.
-        gs = 1.0
-        if self.force_loss_scale is not None:
-            gs = float(self.force_loss_scale)
-        elif any(getattr(n, "compute_dtype", None) == torch.float16 for n in nets):
-            gs = float(2 ** min(24, max(10, (lab[0][0].shape[0] * lab[0][0].shape[2] * lab[0][0].shape[3] - 1).bit_length())))
-        g_cot = dict(gscale=lam_dev[0:1], gmul=gs) if lam_dev is not None else dict(gmul=lam_cot * gs)
-        g_adv = dict(gscale=lam_dev[1:2], gmul=gs) if lam_dev is not None else dict(gmul=lam_adv * gs)
-        self._grad_unscale, self._loss_scale = 1.0 / gs, gs
+        ctx = _StepContext(self._sched, route, self.grad_sync, (float(self.cot_scheduler.value), float(self.adv_scheduler.value)),
+                           lam_dev, self.criterions['sup'].ignore_index)
+        streams = self._streams() if route.model_streams else None
+        if route.kind in ("wide", "wide_grouped"):
+            return self._run_step_wide(ctx, lab, unl, train_adv, adv_choice, nets)
+        if route.kind == "adv_chain":
+            return self._run_step_adv_chain(ctx, lab, unl, adv_choice, nets)
+        return self._run_step_sequential(ctx, lab, unl, train_jsd, train_adv, adv_choice, nets, streams)
+
+    def _run_step_sequential(self, ctx, lab, unl, train_jsd, train_adv, adv_choice, nets, streams) -> dict:
+        """Forwards, JSD, adversarial block, backward passes, optimizers: each model on its stream, joined where the losses couple them."""
+        S, route, sched = len(nets), ctx.route, ctx.sched
+        main = torch.cuda.current_stream(self.device)
         passes: List[List[Tuple[object, Tensor]]] = [[] for _ in range(S)]     # per model: (tape, dlogits) to back-propagate
         sup, preds = [], []
         # Networks whose samples do not interact (UNet: no BatchNorm) run the labeled and the
         # unlabeled batch as ONE pass of B_l + B_u images: same per-pixel results, twice the GEMM
         # rows per launch and half the launches.  Nets with batch statistics keep separate passes
         # (three separate BN-statistics batches per model per step, SURVEY.md 3.3).
-        fuse = bool(train_jsd and unl is not None and self.batch_lab_unlab and
-                    all(getattr(n, "batch_independent", False) and
-                        getattr(n, "external_dropout_masks", None) is None for n in nets))
-        streams = self._streams()
-        main = torch.cuda.current_stream(self.device)
-        if self._wide_ok(nets, streams, train_jsd, unl, fuse):
-            return self._run_step_wide(lab, unl, train_adv, adv_choice, nets, gs, g_cot, g_adv, lam_cot, lam_adv, ignore)
-        if fuse and self._adv_chain_ok(nets, streams, train_jsd, train_adv, adv_choice, unl):
-            return self._run_step_adv_chain(lab, unl, adv_choice, nets, gs, g_cot, g_adv, lam_cot, lam_adv, ignore)
+        fuse = route.joint_pass
 
         def on(i):
-            return self._sched.on(streams[i]) if streams is not None else contextlib.nullcontext()
+            return ctx.on(streams, i)
 
         # backward-pass streams (two per model that supports them): like the model streams they enter a capture only through a
         # wait on the origin stream -- a fork nested inside a forked stream crashes hipStreamEndCapture on ROCm 7.2 -- so they
         # are forked and joined together with the model streams and idle until the backward passes are queued
         side = []
-        if streams is not None and self.pass_streams:
-            for i in range(S):
-                if getattr(nets[i], "supports_pass_streams", False):
-                    side += self._pass_streams_for(i, 2)
+        for i in range(S):
+            if route.pass_streams[i]:
+                side += self._pass_streams_for(i, 2)
 
         def fork():
             if streams is not None:
-                self._sched.wait([(st, main) for st in list(streams) + side])
+                sched.wait([(st, main) for st in list(streams) + side])
 
         def join():
             if streams is not None:
-                self._sched.wait([(main, st) for st in list(streams) + side])
+                sched.wait([(main, st) for st in list(streams) + side])
         fork()
-        joined_after_forwards = False       # becomes True at the JSD join: labeled / unlabeled pass inputs are then final on main
-        self._pass_join = join
+        ctx.join = join
         full = []                                                              # fuse: (tape, logits, dlogits) of the joint pass
         for i in range(S):                                                     # :208-218
             with on(i):
                 self._stamp(i, 0)
                 img, gt = lab[i]
-                B_l = img.shape[0]
                 if fuse:
-                    lp_all, tape = nets[i].plan_forward(torch.cat((img, unl[0]), dim=0), True)
-                    dl_all = torch.empty_like(lp_all)
+                    tape, lp_all, dl_all, s_, p_ = self._forward_ce(ctx, nets[i], torch.cat((img, unl[0]), dim=0), gt, img.shape[0])
                     full.append((tape, lp_all, dl_all))
-                    lp, dl_out = lp_all[:B_l], dl_all[:B_l]
                 else:
-                    lp, tape = nets[i].plan_forward(img, True)
-                    dl_out = torch.empty_like(lp)
+                    tape, _, dl_out, s_, p_ = self._forward_ce(ctx, nets[i], img, gt)
                     passes[i].append((tape, dl_out))
-                t = gt.reshape(-1)
-                out = K.ce_step(lp, t, C, dl_out, gmul=gs, ignore_index=ignore)       # loss value + count and the logit gradient: two launches
-                sup.append(out[0])
-                preds.append(_nchw(lp))
+                sup.append(s_)
+                preds.append(p_)
                 self._stamp(i, 1)
         jsd, unlab_probs = 0, []
         if train_jsd:                                                          # :219-227
@@ -568,13 +657,9 @@ class CoTrainer(Trainer):
                         lps.append(lp_u)
                         utapes.append(tape)
                         dl_outs.append(torch.empty_like(lp_u))
-            joined_after_forwards = True
             join()                                  # the JSD couples all S models: main stream, then fork again
-            # value, the S softmax maps and the S logit gradients in ONE pass over the logits (dct_jsd_logits_step: bit for bit the five separate launches)
-            jsd1, probs = K.jsd_logits_step(lps, C, dl_outs if lam_cot != 0.0 else None, True, **g_cot)
-            jsd = jsd1[0]
-            unlab_probs = [_nchw(p_) for p_ in probs]
-            if lam_cot != 0.0:
+            jsd, unlab_probs = self._jsd(ctx, lps, dl_outs)
+            if ctx.lam_cot != 0.0:
                 if not fuse:
                     for i in range(S):
                         passes[i].append((utapes[i], dl_outs[i]))
@@ -592,34 +677,28 @@ class CoTrainer(Trainer):
         # saved tensors and BatchNorm batch statistics are per pass, running statistics are only touched by forwards).  The
         # sum order of the pass buffers, ((lab + unl) + adv), is unchanged.  The tapes stay referenced until the step ends:
         # they were allocated on the model's stream, which keeps allocating while the pass streams still read them.
-        self._pass_early = {}
         keep_alive = []
         adv = 0
         if train_adv:                                                          # :233-244 -> :371-392
             a, b = adv_choice
-            eps = float(self.adv_training_dict.get('eplision', 0.05))
             img_b, gt_b = lab[b]
             with on(b):
                 x = torch.cat((img_b, unl[0]), dim=0)
-                x_adv, noise, lp_real, _ = self._fgsm_fused(nets[b], x, gt_b, eps, ignore)
+                x_adv, noise, lp_real, _ = self._fgsm_fused(ctx, nets[b], x, gt_b)
             # (queued after the FGSM chain and its completion mark, and before model a's wait for that mark: streams that share
             # a hardware queue run in issue order -- the critical chain goes first, its mark must not land behind another
             # stream's segment, and nothing may be parked behind model a's blocked wait)
-            fgsm_done = self._sched.record(streams[b]) if streams is not None and a != b else None
-            if train_adv and self.early_backward and joined_after_forwards and streams is not None and self.pass_streams:
-                for i in range(S):
-                    if (1 <= len(passes[i]) <= 2 and getattr(nets[i], "supports_pass_streams", False) and
-                            nets[i].flat_params.grads_attached() and (self.grad_sync is None or not hasattr(nets[i], "grad_bucket_ranges"))):
-                        self._pass_early[i] = self._start_passes(i, nets[i], passes[i], self._pass_streams_for(i, 2), [])
-                        keep_alive.append(list(passes[i]))
-                        passes[i].clear()
+            fgsm_done = sched.record(streams[b]) if streams is not None and a != b else None
+            for i in range(S):
+                if route.early_backward[i]:
+                    ctx.early[i] = self._start_passes(ctx, i, nets[i], passes[i], self._pass_streams_for(i, 2), [])
+                    keep_alive.append(list(passes[i]))
+                    passes[i].clear()
             if fgsm_done is not None:
-                self._sched.wait_event(streams[a], fgsm_done)  # the adversarial images and the detached target come from model b
+                sched.wait_event(streams[a], fgsm_done)  # the adversarial images and the detached target come from model b
             with on(a):
-                lp_adv, tape = nets[a].plan_forward(x_adv, True)
-                adv = K.kl_logits_fwd(lp_adv, lp_real, C)[0]
-                if lam_adv != 0.0:
-                    da = K.kl_logits_bwd(lp_adv, lp_real, C, torch.empty_like(lp_adv), **g_adv)
+                adv, tape, da = self._adv_forward_kl(ctx, nets[a], x_adv, lp_real)
+                if da is not None:
                     passes[a].append((tape, da))
 
         def pass_parallel(i):
@@ -630,36 +709,37 @@ class CoTrainer(Trainer):
             in-place accumulation of sequential passes produces."""
             net, fp = nets[i], nets[i].flat_params
             cur = torch.cuda.current_stream(self.device)
-            started = self._pass_early.get(i)
+            started = ctx.early.get(i)
             bufs = list(started[1]) if started is not None else []
             extra = self._pass_streams_for(i, 2)[len(bufs):]
             side_passes, last = (passes[i][:-1], passes[i][-1]) if passes[i] else ([], None)
             if side_passes:
-                if not joined_after_forwards:      # the passes' inputs were produced on the model stream after the last fork
-                    self._sched.wait([(extra[k], cur) for k in range(len(side_passes))])
-                _, bufs = self._start_passes(i, net, side_passes, extra, bufs)
+                if not train_jsd:                  # the passes' inputs were produced on the model stream after the last fork
+                    sched.wait([(extra[k], cur) for k in range(len(side_passes))])
+                _, bufs = self._start_passes(ctx, i, net, side_passes, extra, bufs)
             if last is not None:
                 buf = self._pass_buffer(i, len(bufs), fp)
                 bufs.append(buf)
                 buf.zero_()
                 net.plan_backward(last[0], last[1], need_dx=False, need_dw=True, grad_buffer=buf)
-            self._pass_pending[i] = (fp, bufs)
+            ctx.pending[i] = (fp, bufs)
             passes[i].clear()
 
         def backward_of(i):
             def run():
-                if i in self._pass_early or (self._pass_parallel_ok(nets[i], passes[i], streams) and
-                                             nets[i].flat_params.grads_attached()):
+                if route.overwrite[i] == "buffers":
                     return pass_parallel(i)
                 # data parallelism: during the LAST backward pass of a model its gradient buckets go out as they
                 # complete (earlier passes only accumulate)
-                ranges = nets[i].grad_bucket_ranges() if (self.grad_sync is not None and hasattr(nets[i], "grad_bucket_ranges")) else None
+                ranges = nets[i].grad_bucket_ranges() if route.exchange[i] == "buckets" else None
                 for k, (tape, dl) in enumerate(passes[i]):
                     if ranges is not None and k == len(passes[i]) - 1:
-                        nets[i]._grad_hook = lambda b, i=i, r=ranges: self._sched.call(
-                            lambda: self.grad_sync.begin_bucket(i, r[b][0], r[b][1]))
+                        nets[i]._grad_hook = lambda b, i=i, r=ranges: sched.call(
+                            lambda: ctx.sync.begin_bucket(i, r[b][0], r[b][1]))
                     try:
-                        if i in self._overwrite_models:
+                        # nets whose every parameter gets a gradient in every pass, with the flat gradient buffer already attached: the first
+                        # pass overwrites instead of zero_grad + accumulate (the reference's zero_grad at :245 has the same effect)
+                        if route.overwrite[i] == "first":
                             nets[i].plan_backward(tape, dl, need_dx=False, need_dw=True, overwrite=(k == 0))
                         else:
                             nets[i].plan_backward(tape, dl, need_dx=False, need_dw=True)
@@ -668,46 +748,13 @@ class CoTrainer(Trainer):
                             nets[i]._grad_hook = None
                 passes[i].clear()
             return run
-        # nets whose every parameter gets a gradient in every pass, with the flat gradient buffer already attached:
-        # the first pass overwrites instead of zero_grad + accumulate (the reference's zero_grad at :245 has the same effect)
-        self._overwrite_models = {i for i in range(S) if self.grad_overwrite and passes[i] and
-                                  getattr(nets[i], "supports_grad_overwrite", False) and nets[i].flat_params.grads_attached()}
-        # (pass-parallel models write the whole gradient buffer as the sum of their pass buffers: no zero fill either)
-        self._overwrite_models |= {i for i in range(S) if self._pass_parallel_ok(nets[i], passes[i], streams) and
-                                   nets[i].flat_params.grads_attached()}
-        self._overwrite_models |= set(self._pass_early)
-        try:
-            self._finish_step([(i, backward_of(i)) for i in range(S)], streams)
-        finally:
-            self._overwrite_models = set()
-            self._pass_early = {}
-            self._pass_join = None          # (a closure over this step's tapes and streams: not kept past the step)
+        self._finish_step(ctx, [(i, backward_of(i)) for i in range(S)], streams)
         join()
         del keep_alive
         return dict(sup=sup, jsd=jsd, adv=adv, preds=preds, unlab_probs=unlab_probs)
 
     # ------------------------------------------------------------------------------ the step on four hardware queues
-    def _wide_ok(self, nets, streams, train_jsd, unl, fuse) -> bool:
-        """Every network defers its running statistics and writes per-pass gradient buffers, the gradient buffers exist, and the
-        device has four distinguishable hardware queues."""
-        if not (self.wide_forward and streams is not None and self.pass_streams and train_jsd and unl is not None and not fuse):
-            return False
-        if torch.cuda.is_current_stream_capturing() and not self._sched.capturing:
-            return False        # ONE graph being captured: the JSD's join into a forked stream crashes hipStreamEndCapture (ROCm 7.2)
-        if not all(getattr(n, "supports_deferred_running_stats", False) and getattr(n, "supports_pass_streams", False) and
-                   n.training and n.flat_params.grads_attached() for n in nets):
-            return False
-        return self._queue_streams() is not None
-
-    def _queue_streams(self):
-        """One stream per hardware queue (stream_sched.queue_groups), or None when the probe found fewer than four."""
-        if self._qstreams is None:
-            from .stream_sched import queue_groups
-            groups = queue_groups(self.device)
-            self._qstreams = [g[0] for g in groups][:4] if len(groups) >= 4 else False
-        return self._qstreams or None
-
-    def _run_step_wide(self, lab, unl, train_adv, adv_choice, nets, gs, g_cot, g_adv, lam_cot, lam_adv, ignore) -> dict:
+    def _run_step_wide(self, ctx, lab, unl, train_adv, adv_choice, nets) -> dict:
         """The step laid out on the device's four hardware queues (JSD on, networks with deferred running statistics).
 
         With the running-statistics updates taken out of the forward passes (arch/enet.py::plan_forward(defer_running=True); they
@@ -722,9 +769,7 @@ class CoTrainer(Trainer):
         'stream' here IS a queue: one per group of stream_sched.queue_groups.  Results are bit for bit those of the sequential
         step: same kernels on the same operands, gradient buffers summed in pass order ((lab + unl) + adv)."""
         from .. import hip_ops as K
-        from ..loss.loss import _nchw
-        S, C = len(nets), self.C
-        sched = self._sched
+        S, route, sched = len(nets), ctx.route, ctx.sched
         main = torch.cuda.current_stream(self.device)
         Q = self._queue_streams()
         adv_q = Q[3] if train_adv else None
@@ -732,7 +777,7 @@ class CoTrainer(Trainer):
         lab_q = [free[i % len(free)] for i in range(S)]
         unl_q = [free[(S + i) % len(free)] for i in range(S)]
         sched.wait([(st, main) for st in Q])
-        self._pass_join = lambda: sched.wait([(main, st) for st in Q])
+        ctx.join = lambda: sched.wait([(main, st) for st in Q])
         bufs = [[None, None, None] for _ in range(S)]          # per model: gradient buffers of the (lab, unl, adv) passes
         tapes = [[] for _ in range(S)]                         # per model: tapes in the reference's forward order
         fp = [n.flat_params for n in nets]
@@ -742,51 +787,42 @@ class CoTrainer(Trainer):
             buf.zero_()
             nets[i].plan_backward(tape, dl, need_dx=False, need_dw=True, grad_buffer=buf)
 
-        adv, adv_tapes = 0, {}
-        grouped = self._group_passes_ok(nets, lab, unl)
+        adv, adv_tapes = 0, []
         leaf_keep = None
         if train_adv:                                                          # :233-244 -> :371-392
             a, b = adv_choice
-            eps = float(self.adv_training_dict.get('eplision', 0.05))
             with sched.on(adv_q):
                 x = torch.cat((lab[b][0], unl[0]), dim=0)
-                x_adv, noise, lp_real, ftape = self._fgsm_fused(nets[b], x, lab[b][1], eps, ignore, defer_running=True)
-                lp_adv, atape = nets[a].plan_forward(x_adv, True, defer_running=True)
-                adv = K.kl_logits_fwd(lp_adv, lp_real, C)[0]
-                if lam_adv != 0.0:
-                    da = K.kl_logits_bwd(lp_adv, lp_real, C, torch.empty_like(lp_adv), **g_adv)
-                    if grouped and self.leaf_offload:
-                        # the chain ends with model a's backward pass: its weight gradients (a third of its launches, leaves of
-                        # the data-gradient chain) go to the queue the grouped co-training passes leave idle, a few blocks at a time
-                        side_q = free[2]
-                        buf = bufs[a][2] = self._pass_buffer(a, 2, fp[a])
-                        buf.zero_()
-                        with K.LeafSide() as side:
-                            def leaves_out():
-                                ev = sched.record(adv_q)
-                                sched.wait_event(side_q, ev)
-                                with sched.on(side_q):
-                                    side.flush()
-                            nets[a].plan_backward(atape, da, need_dx=False, need_dw=True, grad_buffer=buf, leaf_hook=leaves_out)
-                            leaves_out()
-                        leaf_keep = side.kept          # referenced until the queues are joined (end of this function)
-                    else:
-                        backward(a, 2, atape, da)
-            adv_tapes = {"fgsm": (b, ftape), "adv": (a, atape)}
-        if grouped:
-            out = self._wide_grouped_tail(lab, unl, train_adv, nets, gs, g_cot, lam_cot, ignore, free, bufs, tapes, fp, adv, adv_tapes)
+                x_adv, noise, lp_real, ftape = self._fgsm_fused(ctx, nets[b], x, lab[b][1], defer_running=True)
+                adv, atape, da = self._adv_forward_kl(ctx, nets[a], x_adv, lp_real, defer_running=True)
+                if da is not None and route.leaf_offload:
+                    # the chain ends with model a's backward pass: its weight gradients (a third of its launches, leaves of
+                    # the data-gradient chain) go to the queue the grouped co-training passes leave idle, a few blocks at a time
+                    side_q = free[2]
+                    buf = bufs[a][2] = self._pass_buffer(a, 2, fp[a])
+                    buf.zero_()
+                    with K.LeafSide() as side:
+                        def leaves_out():
+                            ev = sched.record(adv_q)
+                            sched.wait_event(side_q, ev)
+                            with sched.on(side_q):
+                                side.flush()
+                        nets[a].plan_backward(atape, da, need_dx=False, need_dw=True, grad_buffer=buf, leaf_hook=leaves_out)
+                        leaves_out()
+                    leaf_keep = side.kept          # referenced until the queues are joined (end of this function)
+                elif da is not None:
+                    backward(a, 2, atape, da)
+            adv_tapes = [(b, ftape), (a, atape)]
+        if route.kind == "wide_grouped":
+            out = self._wide_grouped_tail(ctx, lab, unl, nets, free, bufs, tapes, adv, adv_tapes)
             del leaf_keep
             return out
         sup, preds, lab_pass = [], [], []
         for i in range(S):                                                     # :208-218
             with sched.on(lab_q[i]):
-                img, gt = lab[i]
-                lp, tape = nets[i].plan_forward(img, True, defer_running=True)
-                dl = torch.empty_like(lp)
-                t = gt.reshape(-1)
-                out = K.ce_step(lp, t, C, dl, gmul=gs, ignore_index=ignore)       # loss value + count and the logit gradient: two launches
-                sup.append(out[0])
-                preds.append(_nchw(lp))
+                tape, _, dl, s_, p_ = self._forward_ce(ctx, nets[i], lab[i][0], lab[i][1], defer_running=True)
+                sup.append(s_)
+                preds.append(p_)
                 lab_pass.append((tape, dl))
                 tapes[i].append(tape)
         lps, dl_outs, utapes = [], [], []
@@ -802,53 +838,37 @@ class CoTrainer(Trainer):
         jq = free[0]
         sched.wait([(jq, st) for st in free[1:]])
         with sched.on(jq):
-            # value, the S softmax maps and the S logit gradients in ONE pass over the logits (dct_jsd_logits_step: bit for bit the five separate launches)
-            jsd1, probs = K.jsd_logits_step(lps, C, dl_outs if lam_cot != 0.0 else None, True, **g_cot)
-            jsd = jsd1[0]
-            unlab_probs = [_nchw(p_) for p_ in probs]
+            jsd, unlab_probs = self._jsd(ctx, lps, dl_outs)
         sched.wait([(st, jq) for st in free[1:]])
         for i in range(S):
             with sched.on(lab_q[i]):
                 backward(i, 0, *lab_pass[i])
-        if lam_cot != 0.0:
+        if ctx.lam_cot != 0.0:
             for i in range(S):
                 with sched.on(unl_q[i]):
                     backward(i, 1, utapes[i], dl_outs[i])
-        if train_adv:
-            tapes[adv_tapes["fgsm"][0]].append(adv_tapes["fgsm"][1])
-            tapes[adv_tapes["adv"][0]].append(adv_tapes["adv"][1])
-        self._pass_early = {i: (fp[i], [bf for bf in bufs[i] if bf is not None]) for i in range(S)}
-        self._overwrite_models = set(range(S))
-        try:
-            self._finish_step([], None)             # join, sum the pass buffers in order, [gradient exchange], optimizers
-        finally:
-            self._overwrite_models = set()
-            self._pass_early = {}
-            self._pass_join = None
-        for i in range(S):                          # running statistics: labeled, unlabeled, FGSM, adversarial (reference order)
-            nets[i].apply_running_updates(tapes[i])
+        self._close_pass_step(ctx, nets, bufs, tapes, adv_tapes)
         return dict(sup=sup, jsd=jsd, adv=adv, preds=preds, unlab_probs=unlab_probs)
 
-    def _group_passes_ok(self, nets, lab, unl) -> bool:
-        """The 2S co-training passes as grouped launches (include/dct.h "grouped passes"): networks whose plan records into a
-        K.PassGroup, equal labeled batch shapes, and no more members per group than the library packs into one launch."""
-        from .. import hip_ops as K
-        if not (self.group_passes and all(getattr(n, "supports_pass_groups", False) for n in nets)):
-            return False
-        if len({tuple(b[0].shape) for b in lab}) != 1:
-            return False
-        return len(nets) <= K.group_max()
+    def _close_pass_step(self, ctx, nets, bufs, tapes, adv_tapes):
+        """End of a step whose every backward pass wrote its own buffer: join, sum the pass buffers in order, [gradient exchange],
+        optimizers; then the deferred running statistics in the reference's order (labeled, unlabeled, FGSM, adversarial)."""
+        for i, tape in adv_tapes:
+            tapes[i].append(tape)
+        ctx.early = {i: (n.flat_params, [bf for bf in bufs[i] if bf is not None]) for i, n in enumerate(nets)}
+        self._finish_step(ctx, [], None)
+        for i, n in enumerate(nets):
+            n.apply_running_updates(tapes[i])
 
-    def _wide_grouped_tail(self, lab, unl, train_adv, nets, gs, g_cot, lam_cot, ignore, free, bufs, tapes, fp, adv, adv_tapes) -> dict:
-        """Co-training half of `_run_step_wide` with the 2S passes grouped: the S labeled and the S unlabeled forward passes (one
-        group of 2S when the two batch shapes agree, else two groups of S on two queues) are ONE chain of ~210 launches instead
-        of 2S chains sharing three queues, and so are the 2S backward passes (~530 launches).  Same kernel bodies on the same
-        operands, same per-pass gradient buffers summed in the same order: bit-identical to the ungrouped layout."""
+    def _wide_grouped_tail(self, ctx, lab, unl, nets, free, bufs, tapes, adv, adv_tapes) -> dict:
+        """Co-training half of `_run_step_wide` with the 2S passes as grouped launches (include/dct.h "grouped passes"): the S labeled
+        and the S unlabeled forward passes (one group of 2S when the two batch shapes agree, else two groups of S on two queues) are
+        ONE chain of ~210 launches instead of 2S chains sharing three queues, and so are the 2S backward passes (~530 launches).
+        Same kernel bodies on the same operands, same per-pass gradient buffers summed in the same order: bit-identical to the
+        ungrouped layout."""
         from .. import hip_ops as K
-        from ..loss.loss import _nchw
-        S, C = len(nets), self.C
-        sched = self._sched
-        one = self.group_one and tuple(lab[0][0].shape) == tuple(unl[0].shape) and 2 * S <= K.group_max()
+        S, sched = len(nets), ctx.sched
+        one = ctx.route.group_one
         q_lab, q_unl = free[0], (free[0] if one else free[1])
         for n in nets:
             n.flat_params.ensure()
@@ -878,26 +898,21 @@ class CoTrainer(Trainer):
         sup, preds, dls = [], [], []
         with sched.on(q_lab):                                                  # :208-218
             for i in range(S):
-                lp, gt = lab_out[i][0], lab[i][1]
-                dl = torch.empty_like(lp)
-                t = gt.reshape(-1)
-                out = K.ce_step(lp, t, C, dl, gmul=gs, ignore_index=ignore)       # loss value + count and the logit gradient: two launches
-                sup.append(out[0])
-                preds.append(_nchw(lp))
+                dl = torch.empty_like(lab_out[i][0])
+                s_, p_ = self._ce(ctx, lab_out[i][0], lab[i][1], dl)
+                sup.append(s_)
+                preds.append(p_)
                 dls.append(dl)
         lps = [unl_out[i][0] for i in range(S)]
         dl_outs = [torch.empty_like(lp) for lp in lps]
         with sched.on(q_unl):                                                  # :219-227
-            # value, the S softmax maps and the S logit gradients in ONE pass over the logits (dct_jsd_logits_step: bit for bit the five separate launches)
-            jsd1, probs = K.jsd_logits_step(lps, C, dl_outs if lam_cot != 0.0 else None, True, **g_cot)
-            jsd = jsd1[0]
-            unlab_probs = [_nchw(p_) for p_ in probs]
+            jsd, unlab_probs = self._jsd(ctx, lps, dl_outs)
 
         def backward_group(members):
             # what does not record (zero fill of the pass buffers, the cast of the loss gradients) goes first
             prepared = []
             for i, kind in members:
-                buf = bufs[i][kind] = self._pass_buffer(i, kind, fp[i])
+                buf = bufs[i][kind] = self._pass_buffer(i, kind, nets[i].flat_params)
                 buf.zero_()
                 dl = dls[i] if kind == 0 else dl_outs[i]
                 cd = nets[i].compute_dtype
@@ -910,7 +925,7 @@ class CoTrainer(Trainer):
                     tape = (lab_out if kind == 0 else unl_out)[i][1]
                     nets[i].plan_backward(tape, dl, need_dx=False, need_dw=True, grad_buffer=buf)
 
-        unl_bwd = unl_members if lam_cot != 0.0 else []
+        unl_bwd = unl_members if ctx.lam_cot != 0.0 else []
         if one:
             with sched.on(q_lab):
                 backward_group(lab_members + unl_bwd)
@@ -920,31 +935,10 @@ class CoTrainer(Trainer):
             if unl_bwd:
                 with sched.on(q_unl):
                     backward_group(unl_bwd)
-        if train_adv:
-            tapes[adv_tapes["fgsm"][0]].append(adv_tapes["fgsm"][1])
-            tapes[adv_tapes["adv"][0]].append(adv_tapes["adv"][1])
-        self._pass_early = {i: (fp[i], [bf for bf in bufs[i] if bf is not None]) for i in range(S)}
-        self._overwrite_models = set(range(S))
-        try:
-            self._finish_step([], None)             # join, sum the pass buffers in order, [gradient exchange], optimizers
-        finally:
-            self._overwrite_models = set()
-            self._pass_early = {}
-            self._pass_join = None
-        for i in range(S):                          # running statistics: labeled, unlabeled, FGSM, adversarial (reference order)
-            nets[i].apply_running_updates(tapes[i])
+        self._close_pass_step(ctx, nets, bufs, tapes, adv_tapes)
         return dict(sup=sup, jsd=jsd, adv=adv, preds=preds, unlab_probs=unlab_probs)
 
-    def _adv_chain_ok(self, nets, streams, train_jsd, train_adv, adv_choice, unl) -> bool:
-        if not (self._step_hint_adv_chain and streams is not None and self.grad_overwrite):
-            return False
-        if torch.cuda.is_current_stream_capturing() and not self._sched.capturing:
-            return False        # ONE graph being captured: joins into forked streams crash hipStreamEndCapture (ROCm 7.2)
-        if not all(n.training and n.flat_params.grads_attached() for n in nets):
-            return False
-        return self._queue_streams() is not None
-
-    def _run_step_adv_chain(self, lab, unl, adv_choice, nets, gs, g_cot, g_adv, lam_cot, lam_adv, ignore) -> dict:
+    def _run_step_adv_chain(self, ctx, lab, unl, adv_choice, nets) -> dict:
         """Two batch-independent networks (UNet), CE + JSD + FGSM, on three hardware queues.
 
         In the sequential layout the adversarial block is a tail of its own: both joint forwards -> JSD -> FGSM forward + input
@@ -955,11 +949,8 @@ class CoTrainer(Trainer):
         its backward, then -- once the adversarial forward has arrived -- the adversarial backward, accumulating as before.
         Per network the order of forward passes (dropout counter) and of gradient accumulation is the sequential one, so the
         results are bit for bit the same.  Optimizers: model b's waits for the adversarial chain (the last reader of b's weights)."""
-        from .. import hip_ops as K
-        from ..loss.loss import _nchw
-        C = self.C
         a, b = adv_choice
-        sched = self._sched
+        route, sched = ctx.route, ctx.sched
         main = torch.cuda.current_stream(self.device)
         Q = self._queue_streams()
         qa, qb, qj = Q[0], Q[1], Q[2]
@@ -971,7 +962,6 @@ class CoTrainer(Trainer):
         # The FGSM generator's clean forward pass of model b runs over the batch of b's joint pass with the same weights: everything in front of the
         # first dropout -- stem + eight encoder convolutions, half of a forward pass, on the chain that gates the rest of the step -- is taken from
         # the joint pass's tape instead of computed again (UNet.plan_forward(reuse=...); same kernels' outputs, so the same bits).
-        share_encoder = bool(self.fgsm_shares_encoder and getattr(nets[b], "supports_forward_reuse", False) and nets[b].training)
         joint_x_b = None
         # (tools/phase_stamps.py --config cfg3: row a = forward starts / forward + loss done / backward done / optimizer done (behind the adversarial
         #  backward pass), row b = forward starts / adversarial batch ready / adversarial forward done / optimizer done (third queue, behind b's backward))
@@ -980,53 +970,40 @@ class CoTrainer(Trainer):
                 self._stamp(0 if i == a else 1, 0)
                 img, gt = lab[i]
                 xj = torch.cat((img, unl[0]), dim=0)
-                if i == b and share_encoder:
+                keep = i == b and route.share_fgsm_encoder
+                if keep:
                     joint_x_b = xj
-                    lp_all, tape = nets[i].plan_forward(xj, True, keep_predrop=True)
-                else:
-                    lp_all, tape = nets[i].plan_forward(xj, True)
-                dl_all = torch.empty_like(lp_all)
+                tape, lp_all, dl_all, sup[i], preds[i] = self._forward_ce(ctx, nets[i], xj, gt, B_l, **(dict(keep_predrop=True) if keep else {}))
                 full[i] = (tape, lp_all, dl_all)
-                lp, t = lp_all[:B_l], gt.reshape(-1)
-                out = K.ce_step(lp, t, C, dl_all[:B_l], gmul=gs, ignore_index=ignore)       # loss value + count and the logit gradient: two launches
-                sup[i] = out[0]
-                preds[i] = _nchw(lp)
                 if i == a:
                     self._stamp(0, 1)
             fwd_done[i] = sched.record(q_of[i])
-        eps = float(self.adv_training_dict.get('eplision', 0.05))              # :233-244 -> :371-392
-        with sched.on(qb):
-            x = joint_x_b if joint_x_b is not None else torch.cat((lab[b][0], unl[0]), dim=0)
-            x_adv, noise, lp_real, _ = self._fgsm_fused(nets[b], x, lab[b][1], eps, ignore, reuse=full[b][0] if joint_x_b is not None else None)
+        with sched.on(qb):                                                     # :233-244 -> :371-392
+            if joint_x_b is not None:
+                x_adv, noise, lp_real, _ = self._fgsm_fused(ctx, nets[b], joint_x_b, lab[b][1], reuse=full[b][0])
+            else:
+                x_adv, noise, lp_real, _ = self._fgsm_fused(ctx, nets[b], torch.cat((lab[b][0], unl[0]), dim=0), lab[b][1])
             self._stamp(1, 1)
         fgsm_done = sched.record(qb)
         sched.wait_event(qb, fwd_done[a])           # model a's passes keep their order (dropout counter, weight packs)
-        da = None
         with sched.on(qb):
-            lp_adv, atape = nets[a].plan_forward(x_adv, True)
-            adv = K.kl_logits_fwd(lp_adv, lp_real, C)[0]
-            if lam_adv != 0.0:
-                da = K.kl_logits_bwd(lp_adv, lp_real, C, torch.empty_like(lp_adv), **g_adv)
+            adv, atape, da = self._adv_forward_kl(ctx, nets[a], x_adv, lp_real)
             self._stamp(1, 2)
         adv_done = sched.record(qb)
         sched.wait_event(qj, fwd_done[a])
         sched.wait_event(qj, fwd_done[b])
         with sched.on(qj):
-            lps = [full[i][1][B_l:] for i in range(2)]
             dl_outs = [full[i][2][B_l:] for i in range(2)]
-            # value, the S softmax maps and the S logit gradients in ONE pass over the logits (dct_jsd_logits_step: bit for bit the five separate launches)
-            jsd1, probs = K.jsd_logits_step(lps, C, dl_outs if lam_cot != 0.0 else None, True, **g_cot)
-            jsd = jsd1[0]
-            unlab_probs = [_nchw(p_) for p_ in probs]
-            if lam_cot == 0.0:
+            jsd, unlab_probs = self._jsd(ctx, [full[i][1][B_l:] for i in range(2)], dl_outs)
+            if ctx.lam_cot == 0.0:
                 for d in dl_outs:
                     d.zero_()
         jsd_done = sched.record(qj)
-        if int(self.adv_chain_late_b) == 2:
+        if route.late_b == 2:
             # (behind model a's adversarial FORWARD pass: with the FGSM chain shortened by the shared encoder this is another 0.5 % ahead -- 8.92 against
             #  8.97 ms, three rounds; behind the JSD: 9.19)
             sched.wait_event(qj, adv_done)
-        elif self.adv_chain_late_b:
+        elif route.late_b:
             # Model b's backward pass waits for the adversarial BATCH: until then the FGSM chain shares the device with model a's backward pass only and
             # delivers sooner; behind it, model a's adversarial forward + backward -- 3.1 ms that used to run alone (tools/phase_stamps.py --config
             # cfg3: 37 % of the step at depth 1) -- have model b's backward pass beside them.  Same launches, same order per network: same bits.
@@ -1046,30 +1023,9 @@ class CoTrainer(Trainer):
         sched.wait_event(qj, adv_done)              # the adversarial chain read model b's weights
         opt_streams = [None, None]
         opt_streams[a], opt_streams[b] = qa, qj
-        self._optimizer_phase(opt_streams)
+        self._optimizer_phase(ctx, opt_streams)
         sched.wait([(main, st) for st in used])
         return dict(sup=sup, jsd=jsd, adv=adv, preds=preds, unlab_probs=unlab_probs)
-
-    def _fgsm_fused(self, net, x, gt, eps, ignore, defer_running=False, reuse=None):
-        """FSGMGenerator (AEGenerator.py:16-51) on the fused kernels: forward, pseudo-label the
-        unlabeled tail, CE, backward to the input only, x + eps*sign(g).  Returns the physical
-        NHWC logits of the clean pass (their softmax is the detached KL target) and the tape."""
-        from .. import hip_ops as K
-        C = self.C
-        if reuse is not None:
-            lp, tape = net.plan_forward(x, True, reuse=reuse)
-        else:
-            lp, tape = net.plan_forward(x, True, defer_running=True) if defer_running else net.plan_forward(x, True)
-        t = gt.reshape(-1)
-        if x.shape[0] > gt.shape[0]:
-            pseudo = K.argmax(lp, C)
-            t = torch.cat((t, pseudo[t.numel():]))
-        # only the sign of the input gradient is used: the (power-of-two) scale keeps it out of half's subnormals
-        dl = torch.empty_like(lp)
-        K.ce_step(lp, t, C, dl, gmul=getattr(self, "_loss_scale", 1.0), ignore_index=ignore)
-        gx = net.plan_backward(tape, dl, need_dx=True, need_dw=False)
-        x_adv, noise = K.fgsm_step(x.detach().contiguous(), gx.contiguous(), eps)
-        return x_adv, noise, lp, tape
 
     # ------------------------------------------------------------------------------ loops
     def _train_loop(self, labeled_dataloaders: List, unlabeled_dataloader, epoch: int, mode: ModelMode, save: bool,

@@ -20,9 +20,9 @@ A signature is captured after WARMUP eager steps (which are ordinary training st
 Anything that re-allocates the weights, gradients or moments (load_state_dict, .to()) changes the signature and
 leads to a new capture.
 
-Two capture forms (CoTrainer._use_segments):
-  * ONE graph (UNet): the per-model streams fork and join inside the capture; only the model streams -- pass streams are
-    switched off for such a capture (their cross-stream marks have crashed hipStreamEndCapture / hipGraphLaunch on ROCm 7.2);
+Two capture forms (step_route.plan_execution chooses; the step is then routed for that mode by step_route.plan_step):
+  * ONE graph (UNet): the per-model streams fork and join inside the capture; only the model streams -- such a step is routed
+    without pass streams (their cross-stream marks have crashed hipStreamEndCapture / hipGraphLaunch on ROCm 7.2);
   * a PROGRAM of per-stream graphs (trainer/stream_sched.py; Enet, 2 x UNet + FGSM, every data-parallel step): one hipGraphLaunch
     feeds one hardware queue, so chains that should overlap are captured as separate graphs and launched on their own streams,
     with the cross-stream waits and the host callbacks (gradient exchange) replayed between them.
@@ -37,6 +37,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from .step_route import plan_step
 
 
 def _is_refused_capture(err: BaseException) -> bool:
@@ -67,12 +68,12 @@ class StepGraphCache(object):
         self.captures = 0
 
     # ------------------------------------------------------------------------------ signature
-    def _signature(self, lab, unl, train_jsd, train_adv, adv_choice, lam) -> tuple:
+    def _signature(self, lab, unl, train_jsd, train_adv, adv_choice, lam, execution, route) -> tuple:
+        """What a capture is valid for: the route (every layout decision: a frozen dataclass, compared field by field), what the step
+        computes, the batch shapes and the identity of every buffer the launches point into."""
         tr = self.tr
-        sig: List = [bool(train_jsd), bool(train_adv), tuple(adv_choice) if adv_choice is not None else None,
-                     lam[0] != 0.0, lam[1] != 0.0, bool(tr.model_streams), bool(tr.batch_lab_unlab), tr.grad_sync is not None,
-                     bool(tr._use_segments()), bool(tr.pass_streams), bool(tr.early_backward), bool(tr.wide_forward),
-                     bool(tr.adv_chain_layout)]
+        sig: List = [execution, route, bool(train_jsd), bool(train_adv), tuple(adv_choice) if adv_choice is not None else None,
+                     lam[0] != 0.0, lam[1] != 0.0]
         for img, gt in lab:
             sig.append((tuple(img.shape), img.dtype, tuple(gt.shape), gt.dtype))
         if unl is not None:
@@ -109,22 +110,28 @@ class StepGraphCache(object):
         return out
 
     # ------------------------------------------------------------------------------ run
-    def run(self, lab, unl, train_jsd, train_adv, adv_choice) -> dict:
+    def run(self, lab, unl, train_jsd, train_adv, adv_choice, facts, execution, route) -> dict:
+        """``route``: the step routed for ``execution`` (one_graph | program | ddp_two_graphs), which a capture issues and a replay
+        repeats.  Warm-up steps (and shapes that stay uncaptured) are ordinary eager steps, routed as such."""
         tr = self.tr
+
+        def eager():
+            tr.last_route = plan_step(tr.plan, facts, "eager", tr._four_queues)
+            return tr._run_step_fused(lab, unl, train_jsd, train_adv, adv_choice, tr.last_route, lam_dev=lam_dev)
         lam_dev = self._lam()
         for seg in tr.segmentators:
             if hasattr(seg.optimizer, "refresh_lr"):
                 seg.optimizer.refresh_lr()
-        sig = self._signature(lab, unl, train_jsd, train_adv, adv_choice, self._lam_host)
+        sig = self._signature(lab, unl, train_jsd, train_adv, adv_choice, self._lam_host, execution, route)
         cap = self._graphs.get(sig)
         if cap is None:
             n = self._seen.get(sig, 0)
             self._seen[sig] = n + 1
             if n < self.WARMUP or len(self._graphs) >= self.MAX_GRAPHS:
-                return tr._run_step_fused(lab, unl, train_jsd, train_adv, adv_choice, lam_dev=lam_dev)
-            cap = self._capture(sig, lab, unl, train_jsd, train_adv, adv_choice, lam_dev)
+                return eager()
+            cap = self._capture(sig, lab, unl, train_jsd, train_adv, adv_choice, lam_dev, execution, route)
             if cap is None:
-                return tr._run_step_fused(lab, unl, train_jsd, train_adv, adv_choice, lam_dev=lam_dev)
+                return eager()
             first = True
         else:
             first = False
@@ -163,7 +170,7 @@ class StepGraphCache(object):
                     adv=next(rest) if torch.is_tensor(o["adv"]) else o["adv"],
                     preds=o["preds"], unlab_probs=o["unlab_probs"])
 
-    def _capture(self, sig, lab, unl, train_jsd, train_adv, adv_choice, lam_dev) -> Optional[_Captured]:
+    def _capture(self, sig, lab, unl, train_jsd, train_adv, adv_choice, lam_dev, execution, route) -> Optional[_Captured]:
         tr = self.tr
         cap = _Captured()
         cap.lab = [(torch.empty_like(img), torch.empty_like(gt)) for img, gt in lab]
@@ -175,7 +182,6 @@ class StepGraphCache(object):
                 seg.torchnet.wgrad_side_stream = False
         torch.cuda.synchronize(tr.device)
         graph = torch.cuda.CUDAGraph()
-        sync = tr.grad_sync
         cap.graph_opt = None
         cap.program = None
         # no garbage collection while a capture is open: a collected object of an earlier trainer (streams, events, graphs)
@@ -185,13 +191,13 @@ class StepGraphCache(object):
         gc.collect()
         gc.disable()
         try:
-            if tr._use_segments():
+            if execution == "program":
                 from .stream_sched import EagerSchedule, SegmentRecorder
                 rec = SegmentRecorder(tr.device)
                 tr._sched = rec
                 try:
                     rec.start()
-                    cap.out = tr._run_step_fused(cap.lab, cap.unl, train_jsd, train_adv, adv_choice, lam_dev=lam_dev)
+                    cap.out = tr._run_step_fused(cap.lab, cap.unl, train_jsd, train_adv, adv_choice, route, lam_dev=lam_dev)
                     cap.program = rec.finish()
                 except RuntimeError as e:
                     # a capture the runtime refuses must not take the training down: nothing was launched while recording, the
@@ -215,32 +221,17 @@ class StepGraphCache(object):
                 finally:
                     tr._sched = EagerSchedule()
                 graph = None
-            elif sync is None:
-                # ONE graph: only the model streams fork inside it (the layout captured since round 1).  Pass streams add forks whose
-                # marks are waited for by other forked streams; hipStreamEndCapture / hipGraphLaunch of such captures have crashed
-                # on ROCm 7.2, and the sequential accumulation they replace is bit-identical (tests/test_stream_sched_gpu.py)
-                keep_pass, tr.pass_streams = tr.pass_streams, False
-                try:
-                    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                        cap.out = tr._run_step_fused(cap.lab, cap.unl, train_jsd, train_adv, adv_choice, lam_dev=lam_dev)
-                finally:
-                    tr.pass_streams = keep_pass
             else:
-                # no collective inside a capture: graph 1 ends after the backward passes, graph 2 holds the optimizer steps
-                tr.grad_sync, tr._defer_optimizer = None, True
-                keep_pass, tr.pass_streams = tr.pass_streams, False
-                try:
-                    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                        cap.out = tr._run_step_fused(cap.lab, cap.unl, train_jsd, train_adv, adv_choice, lam_dev=lam_dev)
-                    tr._defer_optimizer = False
+                # ONE graph: only the model streams fork inside it (the layout captured since round 1; the route for this mode has no
+                # pass streams and no multi-queue layout: step_route.plan_step)
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    cap.out = tr._run_step_fused(cap.lab, cap.unl, train_jsd, train_adv, adv_choice, route, lam_dev=lam_dev)
+                if execution == "ddp_two_graphs":
+                    # no collective inside a capture: graph 1 ended after the backward passes (route.defer_optimizer), graph 2 holds the
+                    # optimizer steps -- S small launches on the capture stream; the exchange between them leaves a SUM, the update folds its 1/world in
                     cap.graph_opt = torch.cuda.CUDAGraph()
-                    tr._opt_phase_sync = sync          # (the exchange leaves a SUM: the update folds its 1/world in)
                     with torch.cuda.graph(cap.graph_opt, capture_error_mode="thread_local"):
-                        tr._optimizer_phase(None)      # S small launches on the capture stream
-                finally:
-                    tr._opt_phase_sync = None
-                    tr.grad_sync, tr._defer_optimizer = sync, False
-                    tr.pass_streams = keep_pass
+                        tr._optimizer_graph_phase(route)
         finally:
             if gc_was_on:
                 gc.enable()
@@ -253,7 +244,7 @@ class StepGraphCache(object):
             if n == "_drop_calls" and d % 2:       # the device counter's two words are used in turn (dct_dropout_fwd_dev): replays must stay in turn
                 raise RuntimeError("dct_amd: a captured step must hold an even number of dropout launches per network")
         # a re-allocation during the capture (first gradient buffer, moments) would have changed the signature
-        if self._signature(lab, unl, train_jsd, train_adv, adv_choice, self._lam_host) != sig:
+        if self._signature(lab, unl, train_jsd, train_adv, adv_choice, self._lam_host, execution, route) != sig:
             raise RuntimeError("dct_amd: weights / gradients / Adam moments were (re)allocated while the step was being "
                                "captured; they would live in the graph's private pool")
         self._graphs[sig] = cap

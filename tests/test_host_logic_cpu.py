@@ -378,6 +378,176 @@ def test_step_scheduling_switches_on_cpu_modules(tmp_path, monkeypatch):
     assert seen == [1]
 
 
+# ---- the step's route (trainer/step_route.py).  Expected values: the predicates of the step as they stood when every layout asked for itself
+# (_fused_ok, graphable / segmented, _use_segments, fuse, _wide_ok, _group_passes_ok, _adv_chain_ok, the early-backward condition, the three
+# unions of the overwrite set, and _capture's pass_streams = False / grad_sync = None / _defer_optimizer = True around a one-graph capture).
+def _route_kit():
+    from dct_amd.trainer.cotraining_totalloss import ExecutionPlan
+    from dct_amd.trainer.step_route import NetFacts, StepFacts
+    unet = NetFacts(plan_net=True, batch_independent=True, supports_grad_overwrite=True, supports_forward_reuse=True, grad_buckets=True, training=True, grads_attached=True)
+    enet = NetFacts(plan_net=True, supports_pass_streams=True, supports_deferred_running_stats=True, supports_pass_groups=True, prefers_segmented_graphs=True, training=True,
+                    grads_attached=True)
+
+    def facts(net, S=2, adv=None, **kw):
+        base = dict(S=S, nets=(net,) * S, train_jsd=True, train_adv=adv is not None, adv_choice=adv, unlabeled=True, labeled_shapes_equal=True,
+                    labeled_equals_unlabeled=False, labeled_pixels=2 * 64 * 64, gpu=True, fused_criteria=True, optimizers_graphable=True, group_max=4)
+        base.update(kw)
+        return StepFacts(**base)
+    return ExecutionPlan, unet, enet, facts
+
+
+def _no_probe():
+    raise AssertionError("the hardware-queue probe was asked")
+
+
+def test_step_route_table():
+    import dataclasses as dc
+    from dct_amd.trainer.step_route import plan_execution, plan_step
+    Plan, unet, enet, facts = _route_kit()
+    yes, no = (lambda: True), (lambda: False)
+    # 1. 2 x UNet, JSD only: one graph, sequential, joint pass, no pass streams
+    f = facts(unet)
+    assert plan_execution(Plan(), f) == "one_graph"
+    r = plan_step(Plan(), f, "one_graph", _no_probe)
+    assert (r.kind, r.joint_pass, r.model_streams, any(r.pass_streams), any(r.early_backward)) == ("sequential", True, True, False, False)
+    assert r.overwrite == ("first", "first") and r.exchange == ("none", "none") and not r.defer_optimizer and not r.adv_chain_eligible
+    assert plan_step(Plan(), f, "eager", _no_probe) == r                      # UNet has no layout that needs four queues without FGSM
+    # 2. 2 x UNet + FGSM, pair (0, 1): a program; the adversarial chain layout with four queues, else sequential
+    f = facts(unet, adv=(0, 1))
+    assert plan_execution(Plan(), f) == "program"
+    r = plan_step(Plan(), f, "program", yes)
+    assert (r.kind, r.adv_chain_eligible, r.joint_pass, r.share_fgsm_encoder, r.late_b) == ("adv_chain", True, True, True, 2)
+    assert r.overwrite == ("first", "first") and not any(r.pass_streams)
+    r = plan_step(Plan(), f, "program", no)
+    assert (r.kind, r.adv_chain_eligible, r.joint_pass, r.share_fgsm_encoder, r.late_b) == ("sequential", True, True, False, 0)
+    assert plan_step(Plan(), f, "eager", yes).kind == "adv_chain"
+    assert plan_step(Plan(), f, "one_graph", _no_probe).kind == "sequential"       # (segmented_graphs=False: joins into forked streams stay out of ONE graph)
+    assert plan_step(Plan(adv_chain_late_b=1), f, "program", yes).late_b == 1 and plan_step(Plan(adv_chain_late_b=0), f, "program", yes).late_b == 0
+    assert not plan_step(Plan(), dc.replace(f, nets=(unet, dc.replace(unet, supports_forward_reuse=False))), "program", yes).share_fgsm_encoder
+    # 3. ... not eligible: the same model twice, three models, data parallelism, external dropout masks (these also end the joint pass)
+    masks = dc.replace(unet, dropout_masks_set=True)
+    for g, joint in ((facts(unet, adv=(0, 0)), True), (facts(unet, S=3, adv=(0, 2)), True), (facts(unet, adv=(0, 1), ddp=True), True),
+                     (facts(masks, adv=(0, 1)), False)):
+        r = plan_step(Plan(), g, "program", _no_probe)
+        assert (r.kind, r.adv_chain_eligible, r.joint_pass) == ("sequential", False, joint), g
+        assert plan_execution(Plan(), g) == ("program" if g.ddp else "one_graph")
+    # 4. 2 x UNet under data parallelism: a program with the buckets handed out of the backward pass; two graphs when segments are refused
+    f = facts(unet, ddp=True)
+    assert plan_execution(Plan(), f) == "program"
+    r = plan_step(Plan(), f, "program", _no_probe)
+    assert (r.kind, r.exchange, r.defer_optimizer, r.overwrite) == ("sequential", ("buckets", "buckets"), False, ("first", "first"))
+    assert plan_execution(Plan(segmented_graphs=False), f) == "ddp_two_graphs"
+    assert plan_execution(Plan(ddp_segmented_graph=False), f) == "eager"      # no capture holds a collective: without segments the step is launched
+    assert plan_step(Plan(ddp_segmented_graph=False), f, "eager", _no_probe).exchange == ("buckets", "buckets")
+    for plan in (Plan(segmented_graphs=False), Plan(ddp_segmented_graph=False)):
+        r = plan_step(plan, f, "ddp_two_graphs", _no_probe)
+        assert (r.kind, r.exchange, r.defer_optimizer, any(r.pass_streams)) == ("sequential", ("two_graphs", "two_graphs"), True, False)
+    e = plan_step(Plan(segmented_graphs=False), facts(enet, adv=(0, 1), ddp=True), "ddp_two_graphs", _no_probe)
+    assert (e.kind, e.exchange, e.defer_optimizer, any(e.pass_streams), e.overwrite) == ("sequential", ("two_graphs",) * 2, True, False, ("none",) * 2)
+    assert plan_step(Plan(), facts(enet, adv=(0, 1), ddp=True), "program", yes).exchange == ("model", "model")
+    # 5. 2 x Enet, JSD, with and without FGSM: a program, the grouped four-queue layout
+    for adv in (None, (0, 1)):
+        f = facts(enet, adv=adv)
+        assert plan_execution(Plan(), f) == "program"
+        r = plan_step(Plan(), f, "program", yes)
+        assert (r.kind, r.joint_pass, r.group_one, r.leaf_offload) == ("wide_grouped", False, False, adv is not None)
+        assert r.overwrite == ("buffers", "buffers") and all(r.pass_streams) and not any(r.early_backward)
+        assert plan_step(Plan(), dc.replace(f, labeled_equals_unlabeled=True), "program", yes).group_one
+        assert not plan_step(Plan(), dc.replace(f, labeled_equals_unlabeled=True, group_max=3), "program", yes).group_one       # 2 S > group_max
+        assert plan_step(Plan(), dc.replace(f, group_max=1), "program", yes).kind == "wide"                                  # S > group_max
+        assert not plan_step(Plan(), dc.replace(f, lam_adv_zero=True), "program", yes).leaf_offload
+        for g, plan in ((f, Plan(group_passes=False)), (dc.replace(f, labeled_shapes_equal=False), Plan())):
+            r = plan_step(plan, g, "program", yes)
+            assert (r.kind, r.group_one, r.leaf_offload, r.overwrite) == ("wide", False, False, ("buffers", "buffers"))
+    # 6. 2 x Enet, segmented_graphs=False: ONE graph holds the sequential step without pass streams; its warm-up steps stay wide
+    f = facts(enet, adv=(0, 1))
+    assert plan_execution(Plan(segmented_graphs=False), f) == "one_graph"
+    r = plan_step(Plan(segmented_graphs=False), f, "one_graph", _no_probe)
+    assert (r.kind, any(r.pass_streams), any(r.early_backward), r.overwrite, r.model_streams) == ("sequential", False, False, ("none", "none"), True)
+    assert plan_step(Plan(segmented_graphs=False), f, "eager", yes).kind == "wide_grouped"
+    # 7. 2 x Enet without four queues: sequential, pass streams, the co-training backward passes beside the adversarial block
+    r = plan_step(Plan(), f, "program", no)
+    assert (r.kind, r.pass_streams, r.early_backward, r.overwrite) == ("sequential", (True, True), (True, True), ("buffers", "buffers"))
+    r = plan_step(Plan(), facts(enet), "program", no)                           # no FGSM: nothing to run beside; two passes per model, in parallel
+    assert (r.kind, r.pass_streams, r.early_backward, r.overwrite) == ("sequential", (True, True), (False, False), ("buffers", "buffers"))
+    r = plan_step(Plan(), facts(enet, lam_cot_zero=True), "program", no)        # one pass per model: nothing to run in parallel
+    assert (r.pass_streams, r.overwrite) == ((True, True), ("none", "none"))
+    cold = dc.replace(enet, grads_attached=False)                               # first step: no gradient buffer yet
+    r = plan_step(Plan(), facts(cold, adv=(0, 1)), "eager", _no_probe)
+    assert (r.kind, r.early_backward, r.overwrite) == ("sequential", (False, False), ("none", "none"))
+    # 8. UNet with BatchNorm: the samples of a pass interact -- no joint pass, no adversarial chain
+    bn = dc.replace(unet, batch_independent=False)
+    r = plan_step(Plan(), facts(bn, adv=(0, 1)), "one_graph", _no_probe)
+    assert (r.kind, r.joint_pass, r.adv_chain_eligible, r.overwrite) == ("sequential", False, False, ("first", "first"))
+    assert plan_execution(Plan(), facts(bn, adv=(0, 1))) == "one_graph"
+    # 9. a network in eval mode, an optimizer that cannot be replayed, use_hip_graph off: launched eagerly
+    for net in (unet, enet):
+        assert plan_execution(Plan(), facts(net, nets=(net, dc.replace(net, training=False)))) == "eager"
+        assert plan_execution(Plan(), facts(net, optimizers_graphable=False)) == "eager"
+        assert plan_execution(Plan(use_hip_graph=False), facts(net)) == "eager"
+    assert plan_step(Plan(), facts(enet, nets=(enet, dc.replace(enet, training=False))), "eager", _no_probe).kind == "sequential"
+    # 10. CPU device, other criteria, plain modules, nine models: the generic step; the probe is never asked
+    from dct_amd.trainer.step_route import NetFacts
+    for g in (facts(enet, gpu=False), facts(enet, fused_criteria=False), facts(NetFacts(), adv=(0, 1)), facts(unet, S=9)):
+        assert plan_execution(Plan(), g) == "generic"
+        r = plan_step(Plan(), g, "eager", _no_probe)
+        assert (r.kind, r.joint_pass, r.model_streams, any(r.pass_streams), r.overwrite, r.loss_scale) == ("sequential", False, False, False, ("none",) * g.S, 1.0)
+    assert plan_step(Plan(), facts(NetFacts(), ddp=True), "eager", _no_probe).exchange == ("model", "model")
+    # the fp16 loss scale: a power of two >= the labeled pixel count, within [2^10, 2^24]; forced by the plan
+    half = dc.replace(enet, fp16=True)
+    assert plan_step(Plan(), facts(half), "eager", no).loss_scale == 2.0 ** 13 and plan_step(Plan(), facts(enet), "eager", no).loss_scale == 1.0
+    assert plan_step(Plan(), facts(half, labeled_pixels=100), "eager", no).loss_scale == 2.0 ** 10
+    assert plan_step(Plan(), facts(half, labeled_pixels=1 << 30), "eager", no).loss_scale == 2.0 ** 24
+    assert plan_step(Plan(force_loss_scale=4.0), facts(enet), "eager", no).loss_scale == 4.0
+
+
+def test_step_route_each_switch_governs_its_own_fields():
+    """Every ExecutionPlan switch turned off alone: the route fields that differ from the default route's, per configuration."""
+    import dataclasses as dc
+    from dct_amd.trainer.step_route import plan_execution, plan_step
+    Plan, unet, enet, facts = _route_kit()
+
+    def changed(f, mode, queues=True, **switch):
+        base, r = plan_step(Plan(), f, mode, lambda: queues), plan_step(Plan(**switch), f, mode, lambda: queues)
+        return {k: getattr(r, k) for k in (fl.name for fl in dc.fields(r)) if getattr(r, k) != getattr(base, k)}
+    e_adv, u_adv, u = facts(enet, adv=(0, 1)), facts(unet, adv=(0, 1)), facts(unet)
+    # 2 x Enet + FGSM on four queues (wide_grouped, leaf offload on)
+    assert changed(e_adv, "program", leaf_offload=False) == dict(leaf_offload=False)
+    assert changed(e_adv, "program", group_passes=False) == dict(kind="wide", leaf_offload=False)
+    assert changed(dc.replace(e_adv, labeled_equals_unlabeled=True), "program", group_one=False) == dict(group_one=False)
+    assert changed(e_adv, "program", wide_forward=False) == dict(kind="sequential", early_backward=(True, True), leaf_offload=False)
+    assert changed(e_adv, "program", pass_streams=False) == dict(kind="sequential", pass_streams=(False, False), leaf_offload=False, overwrite=("none", "none"))
+    assert changed(e_adv, "program", model_streams=False) == dict(kind="sequential", model_streams=False, pass_streams=(False, False), leaf_offload=False,
+                                                                  overwrite=("none", "none"))
+    for name in ("early_backward", "grad_overwrite", "adv_chain_layout", "batch_lab_unlab", "spread_streams", "segmented_graphs", "use_hip_graph",
+                 "ddp_segmented_graph", "fgsm_shares_encoder", "adv_chain_late_b"):
+        assert changed(e_adv, "program", **{name: False}) == {}, name
+    # ... without four queues (sequential, pass streams, early backward)
+    assert changed(e_adv, "program", queues=False, early_backward=False) == dict(early_backward=(False, False))
+    assert changed(e_adv, "program", queues=False, pass_streams=False) == dict(pass_streams=(False, False), early_backward=(False, False), overwrite=("none", "none"))
+    for name in ("wide_forward", "group_passes", "group_one", "leaf_offload", "grad_overwrite"):
+        assert changed(e_adv, "program", queues=False, **{name: False}) == {}, name
+    # 2 x UNet + FGSM on four queues (adv_chain)
+    seq = dict(kind="sequential", share_fgsm_encoder=False, late_b=0)
+    assert changed(u_adv, "program", adv_chain_layout=False) == dict(seq, adv_chain_eligible=False)
+    assert changed(u_adv, "program", model_streams=False) == dict(seq, adv_chain_eligible=False, model_streams=False)
+    assert changed(u_adv, "program", batch_lab_unlab=False) == dict(seq, adv_chain_eligible=False, joint_pass=False)
+    assert changed(u_adv, "program", grad_overwrite=False) == dict(seq, overwrite=("none", "none"))
+    assert changed(u_adv, "program", fgsm_shares_encoder=False) == dict(share_fgsm_encoder=False)
+    assert changed(u_adv, "program", adv_chain_late_b=1) == dict(late_b=1)
+    for name in ("pass_streams", "early_backward", "wide_forward", "group_passes", "group_one", "leaf_offload", "spread_streams"):
+        assert changed(u_adv, "program", **{name: False}) == {}, name
+    # 2 x UNet, JSD only, inside one graph
+    assert changed(u, "one_graph", batch_lab_unlab=False) == dict(joint_pass=False)
+    assert changed(u, "one_graph", grad_overwrite=False) == dict(overwrite=("none", "none"))
+    assert changed(u, "one_graph", model_streams=False) == dict(model_streams=False)
+    assert changed(u, "one_graph", force_loss_scale=8.0) == dict(loss_scale=8.0)
+    # the switches that govern the replay, not the layout
+    assert plan_execution(Plan(use_hip_graph=False), u_adv) == "eager" and plan_execution(Plan(adv_chain_layout=False), u_adv) == "one_graph"
+    assert plan_execution(Plan(segmented_graphs=True), u) == "program" and plan_execution(Plan(segmented_graphs=False), e_adv) == "one_graph"
+    assert plan_execution(Plan(model_streams=False), u_adv) == "one_graph" and plan_execution(Plan(batch_lab_unlab=False), u_adv) == "one_graph"
+
+
 def test_refused_capture_filter_recognises_the_runtime_messages():
     """step_graph keeps a step shape on eager launches only for refused captures; the library's own launch errors propagate."""
     from dct_amd.trainer.step_graph import _is_refused_capture

@@ -15,7 +15,11 @@ from helpers import FakeLoader, batches  # noqa: E402
 DEV = "cuda:0"
 
 
-def _run(tmp_path, arch, adv, n=7, S=2, **attrs):
+WIDE = ("wide", "wide_grouped")
+
+
+def _run(tmp_path, arch, adv, n=7, S=2, flip=None, **attrs):
+    """``flip`` = (k, switches): set before step k, after the step has been captured."""
     from dct_amd.loss import get_loss_fn
     from dct_amd.models import Segmentator
     from dct_amd.trainer import CoTrainer
@@ -37,8 +41,13 @@ def _run(tmp_path, arch, adv, n=7, S=2, **attrs):
         setattr(tr, k, v)
     for s in segs:
         s.train()
-    sups = []
+    sups, kind_before_flip = [], None
     for k in range(n):
+        if flip is not None and k == flip[0]:
+            kind_before_flip = tr.last_route.kind
+            for name, v in flip[1].items():
+                assert hasattr(tr, name), name
+                setattr(tr, name, v)
         lb = [(lab[i][k][0][0], lab[i][k][0][1]) for i in range(S)]
         out = tr._run_step(lb, (unl[k][0][0], unl[k][0][1]), True, adv, (0, S - 1) if adv else None)
         sups.append([float(v) for v in out["sup"]] + [float(out["jsd"]), float(out["adv"]) if adv else 0.0])
@@ -48,7 +57,7 @@ def _run(tmp_path, arch, adv, n=7, S=2, **attrs):
         state.append(torch.cat([p.detach().flatten() for p in s.torchnet.parameters()]).cpu())
         state.append(s.optimizer._m.cpu())
         state += [b.detach().clone().cpu() for b in s.torchnet.buffers()]
-    return tr, sups, state
+    return tr, sups, state, kind_before_flip
 
 
 @pytest.fixture
@@ -94,6 +103,10 @@ def test_program_of_graphs_equals_one_graph_equals_eager(tmp_path, arch, adv, S)
         elif op[0] == 'wait_event':
             assert id(op[2]) in seen
     assert one[0]._step_graphs.replays == prog[0]._step_graphs.replays >= 4
+    # one graph holds the sequential layout; the program and the eager step the multi-queue one where the device shows four queues
+    multi = (WIDE if arch == "enet" else ("adv_chain",)) if prog[0]._queue_streams() is not None else ("sequential",)
+    assert one[0].last_route.kind == "sequential" and not any(one[0].last_route.pass_streams)
+    assert prog[0].last_route.kind in multi and eager[0].last_route.kind in multi
     _same(eager, one)
     _same(eager, prog)
 
@@ -125,6 +138,7 @@ def test_four_queue_layout_changes_nothing(tmp_path, four_queues, adv, S):
     seq = _run(tmp_path, "enet", adv, S=S, wide_forward=False)
     eager_wide = _run(tmp_path, "enet", adv, S=S, wide_forward=True, use_hip_graph=False)
     assert wide[0]._queue_streams() is not None, "fewer than four hardware queues found: the layout was not exercised"
+    assert wide[0].last_route.kind in WIDE and eager_wide[0].last_route.kind in WIDE and seq[0].last_route.kind == "sequential"
     _same(wide, seq)
     _same(wide, eager_wide)
 
@@ -138,8 +152,22 @@ def test_unet_adversarial_chain_layout_changes_nothing(tmp_path, four_queues):
     assert new[0]._queue_streams() is not None, "fewer than four hardware queues found: the layout was not exercised"
     assert all(c.program is not None for c in new[0]._step_graphs._graphs.values())      # adversarial steps replay as a program
     assert all(c.program is None for c in old[0]._step_graphs._graphs.values())
+    assert new[0].last_route.kind == "adv_chain" and new_eager[0].last_route.kind == "adv_chain" and old[0].last_route.kind == "sequential"
     _same(new, old)
     _same(new, new_eager)
+
+
+@pytest.mark.parametrize("switch", ["group_passes", "leaf_offload"])
+def test_switch_flipped_after_a_capture_is_captured_again(tmp_path, four_queues, switch):
+    """The captured step's signature holds the whole route: a layout switch flipped after the capture (these two were once missing
+    from a hand-written list, and the old layout went on being replayed) leads to a second capture, and the run ends where a run
+    with the switch off from the start ends."""
+    off = _run(tmp_path, "enet", True, **{switch: False})
+    flipped = _run(tmp_path, "enet", True, flip=(4, {switch: False}))          # steps 0-1 eager, 2 captured, 3 replayed | 4-5 eager, 6 captured
+    assert flipped[3] == "wide_grouped" and flipped[0].last_route == off[0].last_route
+    assert flipped[0].last_route.kind == ("wide" if switch == "group_passes" else "wide_grouped") and not flipped[0].last_route.leaf_offload
+    assert off[0]._step_graphs.captures == 1 and flipped[0]._step_graphs.captures == 2
+    _same(off, flipped)
 
 
 def test_queue_groups_partition_the_candidates(monkeypatch):
