@@ -612,26 +612,37 @@ __device__ __forceinline__ unsigned long long w3_stamp() {
 }
 #endif
 
-template <int RB> __device__ __forceinline__ int swz3(int k) {       // in 16-B chunks
-  return RB == 256 ? ((k & 3) << 2) : (((k >> 1) & 1) << 2);
-}
+__device__ __forceinline__ int swz3(int k) { return ((k >> 1) & 1) << 2; }       // in 16-B chunks (128-byte tile rows: two per bank row)
 
-// G: wave groups per block.  Each group of NW waves is a complete copy of the tile machinery (own stages, own half of the
-// block's K-steps); the groups' accumulators are added through LDS before the slab is written.  Two groups halve the
-// number of slabs (written once, read once by the fold: 38 MB per layer at 768 four-wave blocks) at the same waves per CU.
-// QSHIFT: the x fragments of a row's three taps come from ONE 12-pixel window per lane (three transposing reads) -- tap 2 is the
-// window moved by one dword, tap 1 four v_alignbit_b32 -- instead of three separate 8-pixel reads: 5 instead of 8 fragment reads per
-// sub-step (0.83 KiB of LDS per MFMA instead of 1.33; the kernel is LDS-bandwidth bound).  Same MFMA operands bit for bit.
-template <int BP, int BQ, int NW, bool NARROW, int G, bool QSHIFT, bool LEAN>
-__global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
+// The kernel as it ships: 64 x 64 tiles, two groups of four waves.  What the other values measured (tools/bench_conv.py --ab-wgrad):
+//  - tile: 64 x 64 (4 waves, 113 registers: four waves per SIMD) beat 128 x 64 and 128 x 128 (one 8-wave block per CU at 130 / 205
+//    VGPRs) on every eligible layer, by 20-35 %.
+//  - wave groups per block: each group of W3_NW waves is a complete copy of the tile machinery (own stages, own half of the block's
+//    K-steps); the groups' accumulators are added through LDS before the slab is written.  Two groups halve the number of slabs
+//    (written once, read once by the fold: 38 MB per layer at 768 four-wave blocks) at the same waves per CU: +4 % on the step.
+//    One group and four groups (one 16-wave block per CU: 0.7 % behind two) lost.
+//  - the x fragments of a row's three taps come from ONE 12-pixel window per lane (three transposing reads) -- tap 2 is the window
+//    moved by one dword, tap 1 four v_alignbit_b32 -- instead of three separate 8-pixel reads: 5 instead of 8 fragment reads per
+//    sub-step (0.83 KiB of LDS per MFMA instead of 1.33; the kernel is LDS-bandwidth bound), +5-6.5 % on the twelve layers that take
+//    this kernel.  Same MFMA operands bit for bit.
+constexpr int W3_TILE = 64;                                           // channels of dy and of x per block
+constexpr int W3_NW = 4;                                              // waves per group: 2 x 2 MFMA tiles of 32 x 32
+constexpr int W3_G = 2;                                               // wave groups per block
+constexpr int W3_QROWS = 72;                                          // x rows of a stage: 64 + 2 halo pixels, rounded up to whole pieces
+constexpr int W3_RB = W3_TILE * 2;                                    // bytes of a tile row (one pixel's channels)
+constexpr int W3_STAGE = (64 + W3_QROWS) * W3_RB;                     // dy tile + x strip
+constexpr size_t W3_LDS = (size_t)W3_G * 2 * W3_STAGE;                // two stages per group
+
+template <bool NARROW, bool LEAN>
+__global__ __launch_bounds__(W3_G * W3_NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
   const WgradParams& p = pr.w;
-  constexpr int RBP = BP * 2, RBQ = BQ * 2;
-  constexpr int CPRP = RBP / 16, CPRQ = RBQ / 16, RPIP = 64 / CPRP, RPIQ = 64 / CPRQ;
-  constexpr int QROWS = 72;                                         // 64 + 2 halo pixels, rounded up to whole pieces
-  constexpr int NPCP = 64 / RPIP, NPCQ = QROWS / RPIQ, NPC = NPCP + NPCQ;
+  constexpr int BP = W3_TILE, BQ = W3_TILE, NW = W3_NW, G = W3_G, RB = W3_RB, QROWS = W3_QROWS, STAGE = W3_STAGE;
+  constexpr int CPR = RB / 16, RPI = 64 / CPR;
+  constexpr int NPCP = 64 / RPI, NPCQ = QROWS / RPI, NPC = NPCP + NPCQ;
   constexpr int NPW = (NPC + NW - 1) / NW;                          // pieces per wave per stage
+  // TP = TQ = 1: the [TP][TQ] dimensions stay in the source -- without them (and with one lrow for lrowP / lrowQ below) hipcc
+  // allocates and orders this kernel differently, and it is kept instruction for instruction
   constexpr int WPR = BP / (NW / 2), TP = WPR / 32, TQ = BQ / 64;
-  constexpr int STAGE = 64 * RBP + QROWS * RBQ;
   static_assert(TP >= 1 && TQ >= 1, "tile/wave mismatch");
   static_assert(!LEAN || NPCP % NW == 0, "LEAN: piece i of every wave must be of one kind");
   extern __shared__ __attribute__((aligned(128))) char smem_all[];
@@ -681,15 +692,15 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
     const int piece = wave + i * NW;
     live[i] = piece < NPC;
     isP[i] = piece < NPCP;
-    const int k = isP[i] ? piece * RPIP + lane / CPRP : (piece - NPCP) * RPIQ + lane / CPRQ;
+    const int k = isP[i] ? piece * RPI + lane / CPR : (piece - NPCP) * RPI + lane / CPR;
     rho[i] = NARROW ? k / pr.pitch : 0;
     col[i] = NARROW ? k - rho[i] * pr.pitch : k;
     if (isP[i]) {
-      loff[i] = (rho[i] * (int)p.psH + col[i] * psW) * 2 + (((lane % CPRP) ^ swz3<RBP>(k)) * 16);
+      loff[i] = (rho[i] * (int)p.psH + col[i] * psW) * 2 + (((lane % CPR) ^ swz3(k)) * 16);
       ldst[i] = piece * 1024;
     } else {
-      loff[i] = (rho[i] * (int)p.qsH + col[i] * qsW) * 2 + (((lane % CPRQ) ^ swz3<RBQ>(k)) * 16);
-      ldst[i] = 64 * RBP + (piece - NPCP) * 1024;
+      loff[i] = (rho[i] * (int)p.qsH + col[i] * qsW) * 2 + (((lane % CPR) ^ swz3(k)) * 16);
+      ldst[i] = 64 * RB + (piece - NPCP) * 1024;
     }
     if constexpr (LEAN) {
       // static part of "this lane stages a pixel": dy gap columns / rows past the last packed row, x rows past the strip
@@ -714,7 +725,7 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
     rsP = __builtin_amdgcn_make_buffer_rsrc((void*)Pb, 0, (int)(pr.p_bytes - (long long)p0 * 2), 0x00020000);
     rsQ = __builtin_amdgcn_make_buffer_rsrc((void*)Qb, 0, (int)(pr.q_bytes - (long long)q0 * 2), 0x00020000);
   }
-  const int lrowP = lane / CPRP, lrowQ = lane / CPRQ;
+  const int lrowP = lane / CPR, lrowQ = lane / CPR;
   // LEAN: 16-row sub-steps of the step staged last whose dy rows hold pixels (1..4).  The rows behind them are staged as zeros,
   // so their MFMAs (and bias sums) add exact zeros: the loop skips them -- a row tail of 20 pixels (84-pixel rows: 64 + 20) or
   // a packed step of 48 rows (one 46-pixel row + gap) costs two / three sub-steps instead of four.  Bit-identical.
@@ -765,10 +776,10 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
           if (!live[i]) continue;
           const int piece = wave + i * NW;
           if (i < NPCP / NW) {
-            const int v = lrowP < lim - piece * RPIP ? loff[i] : (int)0x80000000u;
+            const int v = lrowP < lim - piece * RPI ? loff[i] : (int)0x80000000u;
             buf_lds16(rsP, buf + ldst[i], v, cP);
           } else {
-            const int v = lrowQ < limQ - (piece - NPCP) * RPIQ ? loff[i] : (int)0x80000000u;
+            const int v = lrowQ < limQ - (piece - NPCP) * RPI ? loff[i] : (int)0x80000000u;
             buf_lds16(rsQ, buf + ldst[i], v, cQ);
           }
         }
@@ -815,25 +826,25 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
   __syncthreads();
   int cur = 0;
   int nsub = sub_staged;             // sub-steps of the step about to be multiplied
-  int pbase[TP], qbase[3][TQ];
+  int pbase[TP], qbase[3][TQ];       // the lane's first dy fragment; [0]: the first of its 12-pixel x window ([1], [2] are not read: same remark)
   {
     const int g = lane >> 4, li = lane & 15, lq = li >> 2, lpp = li & 3, lh = g >> 1;
     const int kq0 = 8 * lh + lq;
 #pragma unroll
     for (int i = 0; i < TP; ++i) {
       const int colb = (wp * WPR + i * 32 + 16 * (g & 1) + 4 * lpp) * 2;
-      pbase[i] = kq0 * RBP + (colb ^ (swz3<RBP>(kq0) << 4));
+      pbase[i] = kq0 * RB + (colb ^ (swz3(kq0) << 4));
     }
 #pragma unroll
     for (int s = 0; s < 3; ++s)
 #pragma unroll
       for (int j = 0; j < TQ; ++j) {
         const int colb = (wq * (BQ / 2) + j * 32 + 16 * (g & 1) + 4 * lpp) * 2;
-        qbase[s][j] = 64 * RBP + (kq0 + s) * RBQ + (colb ^ (swz3<RBQ>(kq0 + s) << 4));
+        qbase[s][j] = 64 * RB + (kq0 + s) * RB + (colb ^ (swz3(kq0 + s) << 4));
       }
   }
-  constexpr int P_KK = 16 * RBP, P_HI = 4 * RBP, Q_KK = 16 * RBQ, Q_HI = 4 * RBQ;
-  constexpr int NRD = 2 * TP + (QSHIFT ? 3 : 6) * TQ;
+  constexpr int KK = 16 * RB, HI = 4 * RB;
+  constexpr int NRD = 2 * TP + 3 * TQ;      // transposing reads per sub-step: two of dy, three of x
   const unsigned smem_off = lds_off(smem);
   const bool do_bias = pr.with_bias && tr == 0 && qt == 0 && wq == 0;
   // bias gradient = column sums of dy: a lane's dy fragment is 8 pixels of ONE channel (row l31 of the MFMA A operand),
@@ -843,7 +854,6 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
 #pragma unroll
   for (int i = 0; i < TP; ++i) accb[i] = 0.f;
 
-  constexpr int QF = QSHIFT ? 1 : 3, QR = QSHIFT ? 3 : 2;     // fragment groups per column block and transposing reads per group
 #ifdef DCT_W3_STAMPS
   unsigned long long st_dma = 0, st_comp = 0, st_bar = 0, st_t0 = w3_stamp();
   const unsigned long long st_begin = st_t0;
@@ -856,18 +866,16 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
 #endif
     if (gi < gend) {                    // wave-uniform: a group with one step fewer only keeps the barrier     // all pieces up front: spreading them between the MFMA groups lands the stage later and was 8 % slower
     const unsigned Pl = smem_off + cur * STAGE;
-    bf16x4 fa[2][TP][2], fb[2][QF][TQ][QR];
+    bf16x4 fa[2][TP][2], fb[2][TQ][3];          // two fragment sets: dy rows +0..3, +4..7; x rows +0..3, +4..7, +8..11
     // the MFMAs (and the bias sums) of one 16-pixel sub-step on fragment set `set`
     auto compute = [&](auto setc) {
       constexpr int set = decltype(setc)::value;
 #pragma unroll
       for (int i = 0; i < TP; ++i) { touch(fa[set][i][0]); touch(fa[set][i][1]); }
 #pragma unroll
-      for (int s = 0; s < QF; ++s)
+      for (int j = 0; j < TQ; ++j)
 #pragma unroll
-        for (int j = 0; j < TQ; ++j)
-#pragma unroll
-          for (int r = 0; r < QR; ++r) touch(fb[set][s][j][r]);
+        for (int r = 0; r < 3; ++r) touch(fb[set][j][r]);
       __builtin_amdgcn_sched_barrier(0);
       bf16x8 a[TP];
 #pragma unroll
@@ -876,23 +884,18 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
       for (int s = 0; s < 3; ++s)
 #pragma unroll
         for (int j = 0; j < TQ; ++j) {
-          bf16x8 b;
-          if constexpr (QSHIFT) {
-            // the lane's 12 consecutive pixels of its x channel as six dwords (two pixels each, the earlier one in the low half)
-            union W { bf16x4 v; unsigned d[2]; };
-            W w0, w1, w2; w0.v = fb[set][0][j][0]; w1.v = fb[set][0][j][1]; w2.v = fb[set][0][j][2];
-            const unsigned D0 = w0.d[0], D1 = w0.d[1], D2 = w1.d[0], D3 = w1.d[1], D4 = w2.d[0];
-            union F { bf16x8 v; unsigned d[4]; } f;
-            if (s == 0) { f.d[0] = D0; f.d[1] = D1; f.d[2] = D2; f.d[3] = D3; }
-            else if (s == 2) { f.d[0] = D1; f.d[1] = D2; f.d[2] = D3; f.d[3] = D4; }
-            else {
-              f.d[0] = __builtin_amdgcn_alignbit(D1, D0, 16); f.d[1] = __builtin_amdgcn_alignbit(D2, D1, 16);
-              f.d[2] = __builtin_amdgcn_alignbit(D3, D2, 16); f.d[3] = __builtin_amdgcn_alignbit(D4, D3, 16);
-            }
-            b = f.v;
-          } else {
-            b = join(fb[set][s][j][0], fb[set][s][j][1]);
+          // the lane's 12 consecutive pixels of its x channel as six dwords (two pixels each, the earlier one in the low half)
+          union W { bf16x4 v; unsigned d[2]; };
+          W w0, w1, w2; w0.v = fb[set][j][0]; w1.v = fb[set][j][1]; w2.v = fb[set][j][2];
+          const unsigned D0 = w0.d[0], D1 = w0.d[1], D2 = w1.d[0], D3 = w1.d[1], D4 = w2.d[0];
+          union F { bf16x8 v; unsigned d[4]; } f;
+          if (s == 0) { f.d[0] = D0; f.d[1] = D1; f.d[2] = D2; f.d[3] = D3; }
+          else if (s == 2) { f.d[0] = D1; f.d[1] = D2; f.d[2] = D3; f.d[3] = D4; }
+          else {
+            f.d[0] = __builtin_amdgcn_alignbit(D1, D0, 16); f.d[1] = __builtin_amdgcn_alignbit(D2, D1, 16);
+            f.d[2] = __builtin_amdgcn_alignbit(D3, D2, 16); f.d[3] = __builtin_amdgcn_alignbit(D4, D3, 16);
           }
+          const bf16x8 b = f.v;
 #pragma unroll
           for (int i = 0; i < TP; ++i) acc[s][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b, acc[s][i][j], 0, 0, 0);
         }
@@ -921,25 +924,22 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
     constexpr std::integral_constant<int, 1> set1{};
     if constexpr (LEAN) {
       // one address register per fragment column block; sub-step (kk) and row-group offsets ride in the reads' immediates
-      unsigned pa[TP], qa[QF][TQ];
+      unsigned pa[TP], qa[TQ];
 #pragma unroll
       for (int i = 0; i < TP; ++i) pa[i] = Pl + pbase[i];
 #pragma unroll
-      for (int s = 0; s < QF; ++s)
-#pragma unroll
-        for (int j = 0; j < TQ; ++j) qa[s][j] = Pl + qbase[s][j];
-#define DCT_W3_ISSUE(set, KK)                                                                                       \
+      for (int j = 0; j < TQ; ++j) qa[j] = Pl + qbase[0][j];
+#define DCT_W3_ISSUE(set, kk)                                                                                       \
       {                                                                                                             \
         _Pragma("unroll") for (int i = 0; i < TP; ++i) {                                                            \
-          tr_issue_o<(KK) * P_KK>(pa[i], fa[set][i][0]);                                                            \
-          tr_issue_o<(KK) * P_KK + P_HI>(pa[i], fa[set][i][1]);                                                     \
+          tr_issue_o<(kk) * KK>(pa[i], fa[set][i][0]);                                                            \
+          tr_issue_o<(kk) * KK + HI>(pa[i], fa[set][i][1]);                                                     \
         }                                                                                                           \
-        _Pragma("unroll") for (int s = 0; s < QF; ++s)                                                              \
-          _Pragma("unroll") for (int j = 0; j < TQ; ++j) {                                                          \
-            tr_issue_o<(KK) * Q_KK>(qa[s][j], fb[set][s][j][0]);                                                    \
-            tr_issue_o<(KK) * Q_KK + Q_HI>(qa[s][j], fb[set][s][j][1]);                                             \
-            if constexpr (QR == 3) tr_issue_o<(KK) * Q_KK + 2 * Q_HI>(qa[s][j], fb[set][s][j][QR - 1]);             \
-          }                                                                                                         \
+        _Pragma("unroll") for (int j = 0; j < TQ; ++j) {                                                            \
+          tr_issue_o<(kk) * KK>(qa[j], fb[set][j][0]);                                                              \
+          tr_issue_o<(kk) * KK + HI>(qa[j], fb[set][j][1]);                                                         \
+          tr_issue_o<(kk) * KK + 2 * HI>(qa[j], fb[set][j][2]);                                                     \
+        }                                                                                                           \
       }
       // (nsub is wave-uniform: scalar branches)
       DCT_W3_ISSUE(0, 0)
@@ -959,15 +959,13 @@ __global__ __launch_bounds__(G * NW * 64) void wgrad3_kernel(Wgrad3Params pr) {
     auto issue = [&](int set, int kk) {
 #pragma unroll
       for (int i = 0; i < TP; ++i) {
-        tr_issue(Pl + pbase[i] + kk * P_KK, fa[set][i][0]);
-        tr_issue(Pl + pbase[i] + kk * P_KK + P_HI, fa[set][i][1]);
+        tr_issue(Pl + pbase[i] + kk * KK, fa[set][i][0]);
+        tr_issue(Pl + pbase[i] + kk * KK + HI, fa[set][i][1]);
       }
 #pragma unroll
-      for (int s = 0; s < QF; ++s)
+      for (int j = 0; j < TQ; ++j)
 #pragma unroll
-        for (int j = 0; j < TQ; ++j)
-#pragma unroll
-          for (int r = 0; r < QR; ++r) tr_issue(Pl + qbase[s][j] + kk * Q_KK + r * Q_HI, fb[set][s][j][r]);     // rows +0..3, +4..7 [, +8..11]
+        for (int r = 0; r < 3; ++r) tr_issue(Pl + qbase[0][j] + kk * KK + r * HI, fb[set][j][r]);
     };
     issue(0, 0);
     issue(1, 1); lgkm_wait<NRD>(); compute(set0);
@@ -1082,7 +1080,31 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* partial,
   *outp = (s0 + s1) + (s2 + s3);
 }
 
-struct WPlan { int bp, bq, chunks, ppc, ptiles, qtiles, v2, direct, slabs; int v3, segs_per_row, nseg, seg_per_chunk, pitch, nr, units, groups; };
+// The kernel of a dct_conv2d_wgrad call, in order of preference: plan_wgrad decides it once -- kernel, tile, pixel chunks,
+// grid, loop form, workspace -- and dct_conv2d_wgrad_bias only executes it.
+enum WgradRoute {
+  WGRAD_ROWS,      // wgrad3_kernel: a block owns a filter row of a 3x3 stride-1 layer (bf16, LDS-DMA)
+  WGRAD_TAP,       // wgrad2_kernel: a block owns one tap (bf16, LDS-DMA, 32-bit element offsets)
+  WGRAD_WIDE       // wgrad_kernel: fp32, and bf16 tensors beyond the 32-bit offsets of the other two
+};
+struct WgradPlan {
+  WgradRoute route;
+  int bp, bq, ptiles, qtiles;      // tile (channels of p x channels of q) and tile counts
+  int taps_per_block;              // a block's share of the R x S taps: the three of a filter row | one
+  int chunks;                      // pixel chunks (the split-K): slabs to fold, unless ...
+  int direct;                      // ... one chunk of an LDS-DMA kernel, which writes dw (and db) itself
+  unsigned grid;
+  int lean, skip_empty;            // loop form: buffer-descriptor staging; (filter-row) skipping the sub-steps that hold no dy pixel
+  long long p_bytes, q_bytes;      // bytes from the first to one past the last element of the bf16 views (the lean forms' descriptor ranges)
+  long long slab_stride;           // floats per slab: dw [+ db]
+  size_t workspace;                // bytes this call needs (0: direct)
+  size_t workspace_query;          // what dct_conv2d_wgrad_workspace_bytes reports: the bias rows always counted, 16 for a direct plan
+  int pix_per_chunk;               // WGRAD_TAP, WGRAD_WIDE: whole K-steps
+  struct Rows {                    // WGRAD_ROWS: K-steps ("segments") of 64 LDS rows
+    int segs_per_row, nseg, seg_per_chunk;
+    int pitch, nr, units;          // pitch > 0: narrow images -- nr image rows per step at a pitch of Wp + 2; units: steps per image
+  } rows;
+};
 
 int g_tune_wgrad_target = 256;     // block target of the per-tap kernel (slab bytes = blocks x 64 KiB; round 4, final sweep: 256 is 0.7 % ahead of 384 / 320 / 192 on the step).  In isolation ~1150 blocks is
                                    // fastest; on the whole step (tools/ab_step.py --knob 14) 256-768 are level and 1.5 % ahead of 1150
@@ -1091,100 +1113,119 @@ int g_tune_wgrad_rows_fill = 70;   // percent: minimum fill of the 64-row K-step
 int g_tune_wgrad_rows = 1;     // 3x3 stride-1 layers on wide images: three taps of a filter row per block (wgrad3_kernel)
 int g_tune_wgrad_chunks = -1;  // >= 1 forces the number of pixel chunks
 
-static bool make_wplan(const dct_view* p, const dct_view* q, const dct_conv_desc* d, int dtype, WPlan& pl) {
-  if (p->c % 64 || q->c % 64) return false;
+// with_bias: the call wants db (the query passes false: its answer counts the bias rows regardless).  The only place that reads the
+// wgrad knobs and g_tune_lean.
+static int plan_wgrad(const dct_view* p, const dct_view* q, const dct_conv_desc* d, int dtype, bool with_bias, WgradPlan& pl) {
+  if (p->c % 64 || q->c % 64) return DCT_ERR_UNSUPPORTED;
   const long long M = (long long)p->n * p->h * p->w;
-  pl.bp = (p->c % 128 == 0) ? 128 : 64;
-  pl.bq = (q->c % 128 == 0) ? 128 : 64;
-  pl.ptiles = p->c / pl.bp; pl.qtiles = q->c / pl.bq;
+  const int taps = d->R * d->S;
+  const long long E = (long long)p->c * q->c * taps;
   const bool fits32 = (long long)p->n * p->sn < (1ll << 30) && (long long)q->n * q->sn < (1ll << 30);   // 32-bit element offsets
-  pl.v2 = (dtype == DCT_BF16 && M < (1 << 24) && fits32) ? 1 : 0;
-  const int bkp = pl.v2 ? 64 : (dtype == DCT_BF16 ? 32 : 16);
-  const long long tiles = (long long)pl.ptiles * pl.qtiles * d->R * d->S;
-  long long chunks;
-  if (pl.v2) {
-    // measured (tools/bench_conv.py chunk sweep): ~1150 blocks in total, at most 64 slabs to fold
-    chunks = (g_tune_wgrad_target + tiles / 2) / tiles;
-    if (chunks > 64) chunks = 64;
-    const long long max_by_pix = (M + 4 * bkp - 1) / (4 * bkp);      // >= 4 K-steps per chunk
-    if (chunks > max_by_pix) chunks = max_by_pix;
-  } else {
-    chunks = (1536 + tiles - 1) / tiles;                      // aim for ~1.5k blocks
-    const long long max_by_pix = (M + 8 * bkp - 1) / (8 * bkp);      // >= 8 K-steps per chunk
-    if (chunks > max_by_pix) chunks = max_by_pix;
-  }
-  // bound the partial-sum workspace to 192 MiB
-  const long long per_chunk = (long long)p->c * q->c * d->R * d->S * 4;
-  while (chunks > 1 && chunks * per_chunk > (192ll << 20)) --chunks;
-  if (g_tune_wgrad_chunks >= 1) chunks = g_tune_wgrad_chunks;
-  if (chunks < 1) chunks = 1;
-  long long ppc = (M + chunks - 1) / chunks;
-  ppc = (ppc + bkp - 1) / bkp * bkp;
-  pl.ppc = (int)ppc;
-  pl.chunks = (int)((M + ppc - 1) / ppc);
-  pl.slabs = pl.chunks;
-  pl.direct = (pl.v2 && pl.chunks == 1) ? 1 : 0;
-  pl.v3 = 0;
-  if (pl.v2 && g_tune_wgrad_rows && d->R == 3 && d->S == 3 && d->stride == 1 && d->dil == 1) {
-    // K-steps of 64 LDS rows: wide images -- runs of <= 64 pixels of one dy row; narrow ones -- nr whole rows at a pitch
-    // of Wp + 2.  Worth it when the steps are mostly full (threshold measured with tools/bench_conv.py --ab-wgrad).
+  const bool dma = dtype == DCT_BF16 && M < (1 << 24) && fits32;      // the two LDS-DMA kernels
+  pl.p_bytes = view_span(p) * 2; pl.q_bytes = view_span(q) * 2;
+  const bool desc_ok = pl.p_bytes < (1ll << 31) && pl.q_bytes < (1ll << 31);      // a buffer descriptor's range
+  // `want` chunks within the 192 MiB bound on the partial-sum workspace, unless the knob forces a count
+  const auto bounded = [&](long long want) {
+    while (want > 1 && want * E * 4 > (192ll << 20)) --want;
+    if (g_tune_wgrad_chunks >= 1) want = g_tune_wgrad_chunks;
+    return want < 1 ? 1 : want;
+  };
+  // `want` chunks of whole K-steps of bkp pixels
+  const auto split_pixels = [&](long long want, int bkp) {
+    long long ppc = (M + want - 1) / want;
+    ppc = (ppc + bkp - 1) / bkp * bkp;
+    pl.pix_per_chunk = (int)ppc;
+    pl.chunks = (int)((M + ppc - 1) / ppc);
+  };
+
+  // Filter-row kernel: K-steps of 64 LDS rows.  Wide images -- runs of <= 64 pixels of one dy row; narrow ones -- nr whole rows at a
+  // pitch of Wp + 2.  Worth it when the steps are mostly full (threshold measured with tools/bench_conv.py --ab-wgrad).
+  WgradPlan::Rows g = {};
+  bool rows = false;
+  if (dma && g_tune_wgrad_rows && d->R == 3 && d->S == 3 && d->stride == 1 && d->dil == 1) {
     const int Wp = p->w;
-    int segs = 1, pitch = 0, nr = 1;
     double fill;
-    long long units;
-    // the lean loop multiplies only the 16-row sub-steps of a step that hold dy pixels: the fill is counted in those
+    // The lean loop multiplies only the 16-row sub-steps of a step that hold dy pixels: the fill is counted in those.  `skips` is the
+    // knobs and the padding only; it does NOT look at the byte ranges that `lean` below also asks for.  For dense views that pass fits32
+    // (n * sn < 2^30 elements) the byte condition holds anyway; it can fail only for a single image with an unusual sn, and then the
+    // fill is counted for a loop that does not run.  Kept as measured.
     const bool skips = (g_tune_lean & 17) == 17 && d->pad_h == 0 && d->pad_w == 0;
     if (Wp > 64) {
-      segs = (Wp + 63) / 64; units = (long long)p->h * segs;
-      const int tail = Wp - 64 * (segs - 1);
-      fill = skips ? (double)Wp / (16.0 * (4 * (segs - 1) + (tail + 15) / 16)) : (double)Wp / (segs * 64.0);
+      g.segs_per_row = (Wp + 63) / 64; g.pitch = 0; g.nr = 1; g.units = p->h * g.segs_per_row;
+      const int full = g.segs_per_row - 1, tail = Wp - 64 * full;
+      fill = skips ? (double)Wp / (16.0 * (4 * full + (tail + 15) / 16)) : (double)Wp / (g.segs_per_row * 64.0);
     } else {
-      pitch = Wp + 2; nr = 66 / pitch; if (nr < 1) nr = 1;
-      const int steps = (p->h + nr - 1) / nr;
+      g.segs_per_row = 1; g.pitch = Wp + 2; g.nr = 66 / g.pitch; if (g.nr < 1) g.nr = 1;
+      g.units = (p->h + g.nr - 1) / g.nr;
       // (narrow images keep the whole-step count: what the skipping saves there is an image's LAST step, and on the layers that
       //  would newly qualify -- cen_a, cen_b, enc4a: one pixel chunk, direct -- the per-tap kernel measured 6-11 % faster:
       //  profiles/r05_wgrad3_substep_skip_ab.txt)
-      fill = (double)p->h * Wp / (steps * 64.0);
-      units = steps;
+      fill = (double)p->h * Wp / (g.units * 64.0);
     }
-    if (fill >= g_tune_wgrad_rows_fill * 0.01 && (long long)p->h * p->sh < (1ll << 29) && (long long)q->h * q->sh < (1ll << 29)) {
-      const long long nseg = (long long)p->n * units;
-      // measured (tools/bench_conv.py --ab-wgrad): 64 x 64 tiles (4 waves, 113 registers: four waves per SIMD) beat
-      // 128 x 64 and 128 x 128 (one 8-wave block per CU at 130 / 205 VGPRs) on every eligible layer, by 20-35 %
-      pl.bp = 64; pl.ptiles = p->c / 64; pl.bq = 64; pl.qtiles = q->c / 64;
-      const int tiles3 = pl.ptiles * pl.qtiles * 3;
-      const int target = g_tune_wgrad3_target;     // 4-wave units; swept 384 / 512 / 640 / 768 / 1024 on the UNet layers: 768 is 10-25 % ahead of the rest
-      pl.groups = 2;     // four groups (one 16-wave block per CU) measured 0.7 % behind two     // two wave groups per block: half the slabs at the same waves per CU
-      long long ch = (target / pl.groups + tiles3 / 2) / tiles3;
-      if (ch > 256) ch = 256;
-      if (ch > nseg / (4 * pl.groups)) ch = nseg / (4 * pl.groups);
-      while (ch > 1 && ch * per_chunk > (192ll << 20)) --ch;
-      if (g_tune_wgrad_chunks >= 1) ch = g_tune_wgrad_chunks;
-      if (ch < 1) ch = 1;
-      const long long spc = (nseg + ch - 1) / ch;
-      pl.v3 = 1;
-      pl.segs_per_row = segs; pl.nseg = (int)nseg; pl.seg_per_chunk = (int)spc;
-      pl.pitch = pitch; pl.nr = nr; pl.units = (int)units;
-      pl.chunks = (int)((nseg + spc - 1) / spc);
-      pl.slabs = pl.chunks;
-      pl.direct = pl.chunks == 1 ? 1 : 0;
-    }
+    rows = fill >= g_tune_wgrad_rows_fill * 0.01 && (long long)p->h * p->sh < (1ll << 29) && (long long)q->h * q->sh < (1ll << 29);
   }
-  return true;
-}
 
-static unsigned wgrid(const WPlan& pl, int taps) {
-  const int tiles = pl.ptiles * pl.qtiles * taps;
-  return (unsigned)((pl.chunks >= 8 ? ((pl.chunks + 7) / 8) * 8 : pl.chunks) * tiles);
+  if (rows) {
+    pl.route = WGRAD_ROWS;
+    pl.bp = pl.bq = W3_TILE; pl.taps_per_block = 3;
+    const long long nseg = (long long)p->n * g.units;
+    const int tiles3 = (p->c / W3_TILE) * (q->c / W3_TILE) * 3;
+    // target in 4-wave units; swept 384 / 512 / 640 / 768 / 1024 on the UNet layers: 768 is 10-25 % ahead of the rest
+    long long ch = (g_tune_wgrad3_target / W3_G + tiles3 / 2) / tiles3;
+    if (ch > 256) ch = 256;
+    if (ch > nseg / (4 * W3_G)) ch = nseg / (4 * W3_G);      // >= 4 K-steps per wave group
+    ch = bounded(ch);
+    g.nseg = (int)nseg; g.seg_per_chunk = (int)((nseg + ch - 1) / ch);
+    pl.rows = g;
+    pl.chunks = (g.nseg + g.seg_per_chunk - 1) / g.seg_per_chunk;
+    pl.pix_per_chunk = 0;
+    pl.direct = pl.chunks == 1;
+    // lean: no padding, views under 2 GiB
+    pl.lean = (g_tune_lean & 1) && d->pad_h == 0 && d->pad_w == 0 && desc_ok;
+    pl.skip_empty = pl.lean && (g_tune_lean & 16);
+  } else {
+    pl.route = dma ? WGRAD_TAP : WGRAD_WIDE;
+    pl.bp = (p->c % 128 == 0) ? 128 : 64;
+    pl.bq = (q->c % 128 == 0) ? 128 : 64;
+    pl.taps_per_block = 1;
+    pl.rows = {};
+    const long long tiles = (long long)(p->c / pl.bp) * (q->c / pl.bq) * taps;
+    if (dma) {
+      // measured (tools/bench_conv.py chunk sweep): ~1150 blocks in total, at most 64 slabs to fold, >= 4 K-steps of 64 pixels per chunk
+      long long ch = (g_tune_wgrad_target + tiles / 2) / tiles;
+      if (ch > 64) ch = 64;
+      if (ch > (M + 255) / 256) ch = (M + 255) / 256;
+      split_pixels(bounded(ch), 64);
+      pl.direct = pl.chunks == 1;
+      pl.lean = (g_tune_lean & 4) && desc_ok;      // views under 2 GiB
+    } else {
+      // ~1.5k blocks, >= 8 K-steps (bf16: 32 pixels, fp32: 16) per chunk
+      const int bkp = dtype == DCT_BF16 ? 32 : 16;
+      long long ch = (1536 + tiles - 1) / tiles;
+      if (ch > (M + 8 * bkp - 1) / (8 * bkp)) ch = (M + 8 * bkp - 1) / (8 * bkp);
+      split_pixels(bounded(ch), bkp);
+      pl.direct = 0;
+      pl.lean = 0;
+    }
+    pl.skip_empty = 0;
+  }
+  pl.ptiles = p->c / pl.bp; pl.qtiles = q->c / pl.bq;
+  // with >= 8 chunks the kernels deal the blocks chunk by chunk over the XCDs (decode_block): whole rounds of 8 chunks
+  const int rounded = pl.chunks >= 8 ? (pl.chunks + 7) / 8 * 8 : pl.chunks;
+  pl.grid = (unsigned)(rounded * pl.ptiles * pl.qtiles * (taps / pl.taps_per_block));
+  pl.slab_stride = E + (with_bias ? p->c : 0);
+  pl.workspace = pl.direct ? 0 : (size_t)pl.chunks * pl.slab_stride * sizeof(float);
+  pl.workspace_query = pl.direct ? 16 : (size_t)pl.chunks * (E + p->c) * sizeof(float);
+  // the fused bias gradient lives in the two LDS-DMA kernels
+  return with_bias && pl.route == WGRAD_WIDE ? DCT_ERR_UNSUPPORTED : DCT_OK;
 }
 
 template <typename T>
-static void launch_w(const WgradParams& wp, const WPlan& pl, hipStream_t st) {
-  const unsigned grid = wgrid(pl, wp.R * wp.S);
-  if (pl.bp == 128 && pl.bq == 128) DCT_LAUNCH(DCT_PROF_WGRAD, (wgrad_kernel<T, 128, 128>), dim3(grid), dim3(256), 0, st, wp);
-  else if (pl.bp == 128) DCT_LAUNCH(DCT_PROF_WGRAD, (wgrad_kernel<T, 128, 64>), dim3(grid), dim3(256), 0, st, wp);
-  else if (pl.bq == 128) DCT_LAUNCH(DCT_PROF_WGRAD, (wgrad_kernel<T, 64, 128>), dim3(grid), dim3(256), 0, st, wp);
-  else DCT_LAUNCH(DCT_PROF_WGRAD, (wgrad_kernel<T, 64, 64>), dim3(grid), dim3(256), 0, st, wp);
+static void launch_w(const WgradParams& wp, const WgradPlan& pl, hipStream_t st) {
+  if (pl.bp == 128 && pl.bq == 128) DCT_LAUNCH(DCT_PROF_WGRAD, (wgrad_kernel<T, 128, 128>), dim3(pl.grid), dim3(256), 0, st, wp);
+  else if (pl.bp == 128) DCT_LAUNCH(DCT_PROF_WGRAD, (wgrad_kernel<T, 128, 64>), dim3(pl.grid), dim3(256), 0, st, wp);
+  else if (pl.bq == 128) DCT_LAUNCH(DCT_PROF_WGRAD, (wgrad_kernel<T, 64, 128>), dim3(pl.grid), dim3(256), 0, st, wp);
+  else DCT_LAUNCH(DCT_PROF_WGRAD, (wgrad_kernel<T, 64, 64>), dim3(pl.grid), dim3(256), 0, st, wp);
 }
 
 template <int BP, int BQ, int NW, bool LEAN>
@@ -1199,45 +1240,39 @@ static void launch_w2_k(const Wgrad2Params& pr, unsigned grid, hipStream_t st) {
   DCT_LAUNCH_FAM(DCT_FAM_WGRAD2, DCT_PROF_WGRAD, (wgrad2_kernel<BP, BQ, NW, LEAN>), dim3(grid), dim3(NW * 64), lds, st, pr);
 }
 template <int BP, int BQ, int NW>
-static void launch_w2_t(const Wgrad2Params& pr, unsigned grid, hipStream_t st) {
-  if ((g_tune_lean & 4) && pr.p_bytes < (1ll << 31) && pr.q_bytes < (1ll << 31)) launch_w2_k<BP, BQ, NW, true>(pr, grid, st);
-  else launch_w2_k<BP, BQ, NW, false>(pr, grid, st);
+static void launch_w2_t(const Wgrad2Params& pr, const WgradPlan& pl, hipStream_t st) {
+  if (pl.lean) launch_w2_k<BP, BQ, NW, true>(pr, pl.grid, st); else launch_w2_k<BP, BQ, NW, false>(pr, pl.grid, st);
 }
-template <int BP, int BQ, int NW, bool NARROW, int G, bool QSHIFT, bool LEAN>
-static void launch_w3_q(const Wgrad3Params& pr, unsigned grid, hipStream_t st) {
-  constexpr size_t lds = G * 2 * (64 * (size_t)BP * 2 + 72 * (size_t)BQ * 2);
+static void launch_w2(const Wgrad2Params& pr, const WgradPlan& pl, hipStream_t st) {
+  if (pl.bp == 128 && pl.bq == 128) launch_w2_t<128, 128, 8>(pr, pl, st);      // eight waves: half the LDS-DMA pieces and decode work per wave
+  else if (pl.bp == 128) launch_w2_t<128, 64, 4>(pr, pl, st);
+  else if (pl.bq == 128) launch_w2_t<64, 128, 4>(pr, pl, st);
+  else launch_w2_t<64, 64, 4>(pr, pl, st);
+}
+template <bool NARROW, bool LEAN>
+static void launch_w3_k(const Wgrad3Params& pr, unsigned grid, hipStream_t st) {
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<BP, BQ, NW, NARROW, G, QSHIFT, LEAN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<NARROW, LEAN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)W3_LDS);
     attr_set = true;
   }
-  DCT_LAUNCH_FAM(DCT_FAM_WGRAD3, DCT_PROF_WGRAD, (wgrad3_kernel<BP, BQ, NW, NARROW, G, QSHIFT, LEAN>), dim3(grid), dim3(G * NW * 64), lds, st, pr);
+  DCT_LAUNCH_FAM(DCT_FAM_WGRAD3, DCT_PROF_WGRAD, (wgrad3_kernel<NARROW, LEAN>), dim3(grid), dim3(W3_G * W3_NW * 64), W3_LDS, st, pr);
 }
-// lean form of the filter-row kernel: no padding, views under 2 GiB (buffer descriptors)
-static bool w3_lean(const Wgrad3Params& pr) {
-  return (g_tune_lean & 1) && pr.w.pad_h == 0 && pr.w.pad_w == 0 && pr.p_bytes < (1ll << 31) && pr.q_bytes < (1ll << 31);
-}
-static void launch_w3(const Wgrad3Params& pr, const WPlan& pl, hipStream_t st) {
-  const unsigned grid = wgrid(pl, 3);
-  // the planner only picks 64 x 64 tiles for this kernel; always two wave groups per block (half the fp32 slabs at the same waves
-  // per CU: +4 % on the step; one group and four groups measured behind) and the three taps' x fragments from ONE 12-pixel window
-  // per lane (QSHIFT: 5 transposing reads per sub-step instead of 8, +5-6.5 % on the twelve layers that take this kernel)
-  // LEAN (the staging as buffer loads with constant lane offsets; bit-identical): layers without padding whose views stay under 2 GiB
-  const bool lean = w3_lean(pr);
-  if (pr.pitch > 0) {
-    if (lean) launch_w3_q<64, 64, 4, true, 2, true, true>(pr, grid, st); else launch_w3_q<64, 64, 4, true, 2, true, false>(pr, grid, st);
+static void launch_w3(const Wgrad3Params& pr, const WgradPlan& pl, hipStream_t st) {
+  if (pl.rows.pitch > 0) {
+    if (pl.lean) launch_w3_k<true, true>(pr, pl.grid, st); else launch_w3_k<true, false>(pr, pl.grid, st);
   } else {
-    if (lean) launch_w3_q<64, 64, 4, false, 2, true, true>(pr, grid, st); else launch_w3_q<64, 64, 4, false, 2, true, false>(pr, grid, st);
+    if (pl.lean) launch_w3_k<false, true>(pr, pl.grid, st); else launch_w3_k<false, false>(pr, pl.grid, st);
   }
 }
-static void launch_w2(const Wgrad2Params& pr, const WPlan& pl, hipStream_t st) {
-  const unsigned grid = wgrid(pl, pr.w.R * pr.w.S);
-  if (pl.bp == 128 && pl.bq == 128) {
-    launch_w2_t<128, 128, 8>(pr, grid, st);      // eight waves: half the LDS-DMA pieces and decode work per wave
-  } else if (pl.bp == 128) launch_w2_t<128, 64, 4>(pr, grid, st);
-  else if (pl.bq == 128) launch_w2_t<64, 128, 4>(pr, grid, st);
-  else launch_w2_t<64, 64, 4>(pr, grid, st);
+
+// what Wgrad2Params and Wgrad3Params share
+template <typename Params>
+static void fill_lds_dma(Params& pr, const WgradParams& wp, const WgradPlan& pl, const dct_conv_desc* d, float* db) {
+  pr.w = wp;
+  pr.direct = pl.direct; pr.accumulate = d->accumulate;
+  pr.bias = db; pr.with_bias = db ? 1 : 0; pr.slab_stride = pl.slab_stride;
+  pr.p_bytes = pl.p_bytes; pr.q_bytes = pl.q_bytes;
 }
 
 }  // namespace
@@ -1246,10 +1281,8 @@ unsigned long long* g_w3_stamps = nullptr;    // diagnostic builds only
 extern "C" int dct_debug_w3_stamps(void* buf) { g_w3_stamps = (unsigned long long*)buf; return 0; }
 
 extern "C" size_t dct_conv2d_wgrad_workspace_bytes(const dct_view* p, const dct_view* q, const dct_conv_desc* d, int dtype) {
-  if (!p || !q || !d) return 0;
-  WPlan pl;
-  if (!make_wplan(p, q, d, dtype, pl)) return 0;
-  return pl.direct ? 16 : (size_t)pl.slabs * ((size_t)p->c * q->c * d->R * d->S + p->c) * sizeof(float);
+  WgradPlan pl;
+  return p && q && d && plan_wgrad(p, q, d, dtype, false, pl) == DCT_OK ? pl.workspace_query : 0;
 }
 
 extern "C" int dct_conv2d_wgrad(const dct_view* p, const dct_view* q, float* dw, const dct_conv_desc* d, int dtype,
@@ -1259,60 +1292,64 @@ extern "C" int dct_conv2d_wgrad(const dct_view* p, const dct_view* q, float* dw,
 
 extern "C" int dct_conv2d_wgrad_bias(const dct_view* p, const dct_view* q, float* dw, float* db, const dct_conv_desc* d, int dtype,
                                      void* workspace, size_t workspace_bytes, dct_stream stream) {
+  // ---- the arguments
   if (!view_ok(p) || !view_ok(q) || !dw || !d) return DCT_ERR_BAD_ARG;
   if (dtype != DCT_F32 && dtype != DCT_BF16) return DCT_ERR_BAD_ARG;
   if (p->n != q->n) return DCT_ERR_BAD_ARG;
   if (!conv_extent_ok(q->h, q->w, d, p->h, p->w)) return DCT_ERR_BAD_ARG;
   const int esz = dtype == DCT_BF16 ? 2 : 4, epv = 16 / esz;
   if (((uintptr_t)p->ptr & 15) || ((uintptr_t)q->ptr & 15) || (p->sw % epv) || (p->sh % epv) || (p->sn % epv) ||
-      (q->sw % epv) || (q->sh % epv) || (q->sn % epv) || ((uintptr_t)dw & 15))
+      (q->sw % epv) || (q->sh % epv) || (q->sn % epv) || ((uintptr_t)dw & 15) || ((uintptr_t)db & 15))
     return DCT_ERR_UNSUPPORTED;
-  WPlan pl;
-  if (!make_wplan(p, q, d, dtype, pl)) return DCT_ERR_UNSUPPORTED;
-  if (db && (!pl.v2 || ((uintptr_t)db & 15))) return DCT_ERR_UNSUPPORTED;   // the fused bias gradient lives in the bf16 LDS-DMA kernel
-  const long long E = (long long)p->c * q->c * d->R * d->S;
-  const long long slab_stride = E + (db ? p->c : 0);
-  const size_t need = pl.direct ? 0 : (size_t)pl.slabs * slab_stride * sizeof(float);
-  if (need && (!workspace || workspace_bytes < need)) return DCT_ERR_WORKSPACE;
+  // ---- the plan
+  WgradPlan pl;
+  const int rc = plan_wgrad(p, q, d, dtype, db != nullptr, pl);
+  if (rc != DCT_OK) return rc;
+  if (pl.workspace && (!workspace || workspace_bytes < pl.workspace)) return DCT_ERR_WORKSPACE;
+  // ---- the parameters
   WgradParams wp;
   wp.P = (const char*)p->ptr; wp.Q = (const char*)q->ptr; wp.out = pl.direct ? dw : (float*)workspace;
   wp.M = p->n * p->h * p->w; wp.Cp = p->c; wp.Cq = q->c; wp.R = d->R; wp.S = d->S;
   wp.Hp = p->h; wp.Wp = p->w; wp.Hq = q->h; wp.Wq = q->w;
   wp.stride = d->stride; wp.dil = d->dil; wp.pad_h = d->pad_h; wp.pad_w = d->pad_w;
   wp.psN = p->sn; wp.psH = p->sh; wp.psW = p->sw; wp.qsN = q->sn; wp.qsH = q->sh; wp.qsW = q->sw;
-  wp.chunks = pl.chunks; wp.pix_per_chunk = pl.ppc; wp.ptiles = pl.ptiles; wp.qtiles = pl.qtiles;
+  wp.chunks = pl.chunks; wp.pix_per_chunk = pl.pix_per_chunk; wp.ptiles = pl.ptiles; wp.qtiles = pl.qtiles;
   hipStream_t st = (hipStream_t)stream;
-  if (pl.v3) {
-    Wgrad3Params pr;
-    pr.w = wp;
-    pr.segs_per_row = pl.segs_per_row; pr.nseg = pl.nseg; pr.seg_per_chunk = pl.seg_per_chunk;
-    pr.pitch = pl.pitch; pr.nr = pl.nr; pr.units_per_image = pl.units;
-    pr.direct = pl.direct; pr.accumulate = d->accumulate;
-    pr.bias = db; pr.with_bias = db ? 1 : 0; pr.slab_stride = slab_stride;
-    pr.skip_empty = (g_tune_lean & 16) ? 1 : 0;
-    pr.p_bytes = view_span(p) * 2;
-    pr.q_bytes = view_span(q) * 2;
-    pr.stamps = g_w3_stamps;
-    launch_w3(pr, pl, st);
-  } else if (pl.v2) {
-    Wgrad2Params pr;
-    pr.w = wp;
-    pr.dhw.d = p->h * p->w; pr.dhw.rcp = 1.0f / (float)pr.dhw.d;
-    pr.dw_.d = p->w; pr.dw_.rcp = 1.0f / (float)pr.dw_.d;
-    pr.direct = pl.direct; pr.accumulate = d->accumulate;
-    pr.bias = db; pr.with_bias = db ? 1 : 0; pr.slab_stride = slab_stride;
-    pr.p_bytes = view_span(p) * 2;
-    pr.q_bytes = view_span(q) * 2;
-    launch_w2(pr, pl, st);
-  } else if (dtype == DCT_BF16) launch_w<bf16_t>(wp, pl, st);
-  else launch_w<float>(wp, pl, st);
-  DCT_PLAN_NOTE("%s %d x %d tile: %d x %d x %d taps, %d pixel chunks%s%s", pl.v3 ? "wgrad3 filter-row" : pl.v2 ? "wgrad2 per-tap" : "wgrad",
-                pl.bp, pl.bq, pl.ptiles, pl.qtiles, d->R * d->S, pl.chunks, pl.v3 ? (pl.pitch ? " (narrow rows)" : " (wide rows)") : "",
-                pl.direct ? ", direct" : "");
+  const char* kernel = "";
+  switch (pl.route) {
+    case WGRAD_ROWS: {
+      Wgrad3Params pr;
+      fill_lds_dma(pr, wp, pl, d, db);
+      pr.segs_per_row = pl.rows.segs_per_row; pr.nseg = pl.rows.nseg; pr.seg_per_chunk = pl.rows.seg_per_chunk;
+      pr.pitch = pl.rows.pitch; pr.nr = pl.rows.nr; pr.units_per_image = pl.rows.units;
+      pr.skip_empty = pl.skip_empty;
+      pr.stamps = g_w3_stamps;
+      launch_w3(pr, pl, st);
+      kernel = "wgrad3 filter-row";
+      break;
+    }
+    case WGRAD_TAP: {
+      Wgrad2Params pr;
+      fill_lds_dma(pr, wp, pl, d, db);
+      pr.dhw.d = p->h * p->w; pr.dhw.rcp = 1.0f / (float)pr.dhw.d;
+      pr.dw_.d = p->w; pr.dw_.rcp = 1.0f / (float)pr.dw_.d;
+      launch_w2(pr, pl, st);
+      kernel = "wgrad2 per-tap";
+      break;
+    }
+    case WGRAD_WIDE:
+      if (dtype == DCT_BF16) launch_w<bf16_t>(wp, pl, st); else launch_w<float>(wp, pl, st);
+      kernel = "wgrad";
+      break;
+  }
+  DCT_PLAN_NOTE("%s %d x %d tile: %d x %d x %d taps, %d pixel chunks%s%s%s", kernel, pl.bp, pl.bq, pl.ptiles, pl.qtiles, d->R * d->S, pl.chunks,
+                pl.route != WGRAD_ROWS ? "" : pl.rows.pitch ? " (narrow rows)" : " (wide rows)", pl.direct ? ", direct" : "",
+                pl.skip_empty ? ", lean + skip" : pl.lean ? ", lean" : "");
+  // ---- the fold of the slabs
   if (!pl.direct) {
-    const long long n4b = db ? p->c / 4 : 0;
+    const long long E = (long long)p->c * q->c * d->R * d->S, n4b = db ? p->c / 4 : 0;
     DCT_LAUNCH_FAM(DCT_FAM_FOLDS, DCT_PROF_WGRAD, wgrad_reduce_kernel, dim3(div_up(E / 4 + n4b, 256)), dim3(256), 0, st,
-               (const float*)workspace, dw, db, E / 4, n4b, slab_stride, pl.slabs, d->accumulate);
+               (const float*)workspace, dw, db, E / 4, n4b, pl.slab_stride, pl.chunks, d->accumulate);
   }
   return dct_check_launch();
 }

@@ -918,10 +918,11 @@ def wgrad_case(K, p_shape, q_shape, R=3, S=3, stride=1, pad=0, dtype=torch.bfloa
 
 
 def wgrad_note(note):
-    m = re.match(r"(wgrad3 filter-row|wgrad2 per-tap|wgrad) \d+ x \d+ tile: \d+ x \d+ x \d+ taps, (\d+) pixel chunks( \((narrow|wide) rows\))?(, direct)?",
-                 note)
+    """(kernel, pixel chunks, direct, loop form: "plain" | "lean" | "lean + skip") of a weight-gradient plan note."""
+    m = re.match(r"(wgrad3 filter-row|wgrad2 per-tap|wgrad) \d+ x \d+ tile: \d+ x \d+ x \d+ taps, (\d+) pixel chunks( \((narrow|wide) rows\))?(, direct)?"
+                 r"(, (lean|lean \+ skip))?$", note)
     assert m, note
-    return m.group(1).split()[0], int(m.group(2)), bool(m.group(5))
+    return m.group(1).split()[0], int(m.group(2)), bool(m.group(5)), m.group(7) or "plain"
 
 
 @gpu
@@ -943,7 +944,7 @@ def test_wgrad2_plan_edges(K, p_shape, R, stride, chunks, target, acc, db):
     assert pl["kind"] == "wgrad2"
     with knobs(WGRAD_CHUNKS=chunks, WGRAD_ROWS=0, WGRAD_TARGET=target):
         note = wgrad_case(K, p_shape, q_shape, R, R, stride, with_db=db, acc=acc, seed=Cp + Hp, what="wgrad2")
-    assert wgrad_note(note) == ("wgrad2", pl["chunks"], pl["direct"]), (note, pl)
+    assert wgrad_note(note) == ("wgrad2", pl["chunks"], pl["direct"], "lean"), (note, pl)
     if p_shape == (8, 64, 64, 64):
         assert pl["chunks"] == 64 and cdiv(8 * 64 * 64, 4 * 64) == 128, pl
     if p_shape == (8, 22, 22, 1024):
@@ -967,7 +968,8 @@ def test_wgrad3_plan_edges(K, p_shape, Cq, pad, chunks, target3):
     assert pl["kind"] == "wgrad3", pl
     with knobs(WGRAD_CHUNKS=chunks, WGRAD3_TARGET=target3):
         note = wgrad_case(K, p_shape, q_shape, pad=pad, with_db=True, seed=Hp + Wp, what="wgrad3")
-    assert wgrad_note(note) == ("wgrad3", pl["chunks"], pl["direct"]), (note, pl)
+    # the lean loop (buffer descriptors, empty sub-steps skipped) takes the layers without padding; the padded one runs the plain loop
+    assert wgrad_note(note) == ("wgrad3", pl["chunks"], pl["direct"], "plain" if pad else "lean + skip"), (note, pl)
     if target3 == 4096:
         assert pl["chunks"] == 256, pl
     if chunks == 11:
@@ -985,7 +987,24 @@ def test_wgrad_v1_plan_edges(K, p_shape, Cq, R, stride, dtype):
     q_shape = (n, (Hp - 1) * stride + R, (Wp - 1) * stride + R, Cq)
     pl = wgrad_plan(dtype, p_shape, q_shape, R, R, stride)
     note = wgrad_case(K, p_shape, q_shape, R, R, stride, dtype=dtype, seed=Hp + Cq, what="wgrad v1")
-    assert wgrad_note(note) == ("wgrad", pl["chunks"], False), (note, pl)
+    assert wgrad_note(note) == ("wgrad", pl["chunks"], False, "plain"), (note, pl)
+
+
+@gpu
+@pytest.mark.parametrize("p_shape,rows,chunks,lean,form", [
+    ((5, 21, 20, 64), 1, -1, 0, "plain"),      # filter-row, narrow rows: the plain loop ...
+    ((5, 21, 20, 64), 1, -1, 1, "lean"),       # ... and the lean one without the skipping
+    ((2, 21, 23, 256), 0, 3, 0, "plain"),      # per-tap, forced 3 chunks
+])
+def test_wgrad_loop_forms(K, p_shape, rows, chunks, lean, form):
+    """DCT_TUNE_LEAN picks the loop form of the two LDS-DMA kernels, the plan note names it, and every form gives the same bits (those of
+    the float64 reference on exact-integer data) on cases that test_wgrad3_plan_edges / test_wgrad2_plan_edges run in the shipped form."""
+    n, Hp, Wp, Cp = p_shape
+    q_shape = (n, Hp + 2, Wp + 2, Cp)
+    pl = wgrad_plan(torch.bfloat16, p_shape, q_shape, 3, 3, chunks_knob=chunks, rows=rows, lean=lean)
+    with knobs(WGRAD_CHUNKS=chunks, WGRAD_ROWS=rows, LEAN=lean):
+        note = wgrad_case(K, p_shape, q_shape, with_db=True, seed=Hp + Wp, what=f"LEAN={lean}")
+    assert wgrad_note(note) == ("wgrad3" if rows else "wgrad2", pl["chunks"], pl["direct"], form), (note, pl)
 
 
 # ================================================================================================ 3. the 32-bit addressing guards

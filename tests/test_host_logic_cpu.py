@@ -700,3 +700,93 @@ def test_conv2d_workspace_bytes_table():
     got = [(shape, kw, ws(*shape, **kw)) for shape, kw, _ in _CONV_WS_TABLE]
     assert got == _CONV_WS_TABLE, [(g, w[2]) for g, w in zip(got, _CONV_WS_TABLE) if g != w]
     assert sum(1 for _, _, n in _CONV_WS_TABLE if n) >= 30 and sum(1 for _, _, n in _CONV_WS_TABLE if not n) >= 15
+
+
+# dct_conv2d_wgrad_workspace_bytes for (n, H, W, C of dy, C of x), descriptor fields / planner knobs -> bytes.  The numbers were read from the
+# library built from the commit before dct_conv2d_wgrad got its one planner (plan_wgrad, csrc/wgrad.hip), never from the planner itself: the
+# query returns 16 for a direct plan and counts the bias rows of every slab whether or not the call will ask for db.
+_WGRAD_WS_KNOBS = {"WGRAD_CHUNKS": (3, -1), "WGRAD_ROWS": (8, 1), "WGRAD_ROWS_FILL": (9, 70), "WGRAD_TARGET": (14, 256), "WGRAD3_TARGET": (15, 768),
+                   "LEAN": (38, 31)}      # name -> (knob, shipped value)
+_WGRAD_WS_TABLE = [
+    # per-tap (filter rows off, or not 3x3 stride 1): direct, natural and forced chunk counts, the 64-chunk and the 192 MiB caps, 2x2 stride 2
+    ((2, 30, 30, 512, 512), dict(WGRAD_ROWS=0, WGRAD_CHUNKS=1), 16),
+    ((8, 9, 9, 1024, 1024), dict(), 16),
+    ((8, 9, 9, 1024, 1024), dict(WGRAD_ROWS_FILL=30), 16),
+    ((3, 33, 29, 256, 256), dict(WGRAD_ROWS=0), 16522240),
+    ((4, 60, 60, 128, 128), dict(WGRAD_ROWS=0), 14758400),
+    ((2, 21, 23, 256, 256), dict(WGRAD_ROWS=0, WGRAD_CHUNKS=3), 7080960),
+    ((2, 37, 41, 128, 128), dict(WGRAD_ROWS=0, WGRAD_CHUNKS=13), 7084032),
+    ((8, 64, 64, 64, 64), dict(R=1), 1064960),
+    ((8, 22, 22, 1024, 1024), dict(WGRAD_ROWS=0, WGRAD_TARGET=8192), 188764160),
+    ((8, 22, 22, 1024, 1024), dict(WGRAD_ROWS=0), 16),
+    ((4, 33, 35, 64, 128), dict(R=2, stride=2), 2495232),
+    ((8, 18, 18, 1024, 512), dict(R=2, stride=2), 16785408),
+    # filter-row, wide rows (the padded case runs the plain loop: its fill counts whole steps)
+    ((2, 40, 130, 64, 64), dict(), 4431360),
+    ((2, 40, 130, 64, 64), dict(WGRAD_ROWS=0), 4135936),
+    ((3, 31, 200, 128, 64), dict(), 12407808),
+    ((2, 33, 200, 64, 128), dict(pad=2), 9740544),
+    ((3, 50, 130, 64, 64), dict(WGRAD_CHUNKS=11), 1624832),
+    ((8, 256, 254, 64, 64), dict(), 18907136),
+    ((8, 256, 254, 64, 64), dict(WGRAD3_TARGET=4096), 37814272),
+    ((8, 126, 126, 128, 128), dict(), 18890752),
+    # filter-row, narrow rows; the fill threshold from both sides
+    ((5, 21, 20, 64, 64), dict(), 590848),
+    ((4, 45, 48, 64, 64), dict(), 2954240),
+    ((4, 45, 48, 64, 64), dict(WGRAD_CHUNKS=7), 1033984),
+    ((8, 61, 61, 256, 256), dict(), 18882560),
+    ((8, 40, 40, 64, 64), dict(), 3692800),
+    ((8, 40, 40, 64, 64), dict(WGRAD_ROWS_FILL=30), 5908480),
+    ((8, 40, 40, 64, 64), dict(WGRAD_ROWS_FILL=70), 3692800),
+    # the loop form in the fill: 84-pixel rows are 88 % full counted in sub-steps (LEAN 31), 66 % in whole steps (14: no filter-row lean loop)
+    ((4, 40, 84, 64, 64), dict(LEAN=31), 5908480),
+    ((4, 40, 84, 64, 64), dict(LEAN=14), 3988224),
+    ((4, 40, 84, 64, 64), dict(LEAN=15), 3988224),
+    ((4, 40, 84, 64, 64), dict(pad=1), 3988224),
+    ((2, 40, 130, 64, 64), dict(LEAN=14), 4135936),
+    # the guards of the LDS-DMA kernels: rows of 2^29 elements per image, M < 2^24 pixels, 2^30 elements per tensor
+    ((1, 2890, 2894, 64, 64), dict(), 18907136),
+    ((1, 2898, 2898, 64, 64), dict(), 4135936),
+    ((63, 510, 510, 64, 64), dict(), 18907136),
+    ((65, 510, 510, 64, 64), dict(), 25258752),
+    ((2, 1024, 1024, 512, 64), dict(), 50812928),
+    # fp32
+    ((2, 30, 30, 64, 64), dict(dtype=0), 2215680),
+    ((2, 62, 62, 128, 128), dict(dtype=0), 36010496),
+    ((4, 33, 35, 64, 128), dict(R=2, stride=2, dtype=0), 4859136),
+    ((1, 7, 9, 64, 64), dict(dtype=0), 147712),
+    # channel counts no tile takes
+    ((2, 12, 12, 32, 64), dict(), 0),
+    ((2, 12, 12, 64, 96), dict(), 0),
+    ((2, 12, 12, 16, 64), dict(dtype=0), 0),
+]
+
+
+def test_conv2d_wgrad_workspace_bytes_table():
+    """The weight-gradient planner's workspace size on every route and on both sides of its edges (chunk caps, forced chunks, the fill
+    threshold and the loop form that enters it, the 32-bit guards).  The query reads shapes only: the views carry made-up pointers, and
+    dct_conv2d_wgrad itself is never called with them."""
+    import ctypes as C
+    from dct_amd import _lib
+    lib = _lib.load()
+
+    def ws(n, Hp, Wp, Cp, Cq, R=3, stride=1, pad=0, dtype=_lib.BF16, **knobs):
+        Hq, Wq = (Hp - 1) * stride + R - 2 * pad, (Wp - 1) * stride + R - 2 * pad
+        p = _lib.View(4096, n, Hp, Wp, Cp, Hp * Wp * Cp, Wp * Cp, Cp)
+        q = _lib.View(4096, n, Hq, Wq, Cq, Hq * Wq * Cq, Wq * Cq, Cq)
+        d = _lib.ConvDesc(R, R, stride, 1, pad, pad, 0, 0, 0, 0, 1.0, None, None, None, None, 0, None, None, None, 0)
+        try:
+            for k, v in knobs.items():
+                assert lib.dct_tune_set(_WGRAD_WS_KNOBS[k][0], v) == 0, (k, v)
+            return lib.dct_conv2d_wgrad_workspace_bytes(C.byref(p), C.byref(q), C.byref(d), dtype)
+        finally:
+            for k in knobs:
+                lib.dct_tune_set(*_WGRAD_WS_KNOBS[k])
+
+    got = [(shape, kw, ws(*shape, **kw)) for shape, kw, _ in _WGRAD_WS_TABLE]
+    assert got == _WGRAD_WS_TABLE, [(g, w[2]) for g, w in zip(got, _WGRAD_WS_TABLE) if g != w]
+    assert len(_WGRAD_WS_TABLE) >= 25 and sum(1 for _, _, n in _WGRAD_WS_TABLE if n in (0, 16)) >= 5
+    # the loop form moves the choice on 84-pixel rows, the fill threshold on 40-pixel ones
+    by = {(s, tuple(sorted(kw.items()))): n for s, kw, n in _WGRAD_WS_TABLE}
+    assert by[((4, 40, 84, 64, 64), (("LEAN", 31),))] != by[((4, 40, 84, 64, 64), (("LEAN", 14),))]
+    assert by[((8, 40, 40, 64, 64), (("WGRAD_ROWS_FILL", 30),))] != by[((8, 40, 40, 64, 64), (("WGRAD_ROWS_FILL", 70),))]
