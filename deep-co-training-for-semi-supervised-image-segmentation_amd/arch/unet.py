@@ -20,6 +20,7 @@ No CPU path: inputs must be on the HIP device.
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 from typing import Dict, List, Optional
 
 import torch
@@ -27,6 +28,7 @@ import torch.nn as nn
 
 from .. import hip_ops as K
 from .flat import FlatParams
+from .unet_route import BackwardFacts, ForwardFacts, ForwardRoute, plan_backward_pass, plan_forward_pass
 
 _WIDTHS = (64, 128, 256, 512)
 
@@ -211,6 +213,7 @@ class UNet(nn.Module):
         self.batch_skip_resize = True        # the four skip connections' bilinear resizes in one launch, in front of the centre
         self.fuse_drop_pool = True           # the fourth level's dropout + max-pool in one launch (the dropped tensor is never written)
         self._wgrad_stream = None
+        self.last_route = {"forward": None, "backward": None}   # the routes of the last passes issued (arch/unet_route.py)
 
     # ------------------------------------------------------------------------------ weights
     def mark_weights_updated(self, shadow_fresh: bool = False):
@@ -313,8 +316,9 @@ class UNet(nn.Module):
         run again; the pass starts at the fourth level's dropout with masks of its own.  (The FGSM generator's clean forward pass follows the
         joint forward pass of the same network over the same batch: AEGenerator.py:27 behind cotraining_totalloss.py:208-227.)"""
         self._check_input(x)
-        self._ensure_packs(late=bool(self.late_packs))
-        return self._run_forward(x, save, keep_predrop=keep_predrop, reuse=reuse)
+        facts = self._forward_facts(save, keep_predrop)
+        self._ensure_packs(late=facts.late_packs)
+        return self._run_forward(x, facts, reuse=reuse)
 
     supports_grad_overwrite = True
     supports_forward_reuse = True        # plan_forward(keep_predrop=..., reuse=...)
@@ -325,7 +329,7 @@ class UNet(nn.Module):
         contents of) the flat gradient buffer (attached as p.grad); returns d/dx as [B,1,H,W] when need_dx."""
         if need_dw:
             self.flat_params.ensure_grads()
-        dx = self._run_backward(tape, dlogits, need_dx, need_dw, overwrite=overwrite and need_dw)
+        dx = self._run_backward(tape, dlogits, need_dx, need_dw, overwrite=overwrite)
         return dx.reshape(dx.shape[0], 1, dx.shape[1], dx.shape[2]) if dx is not None else None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -347,18 +351,45 @@ class UNet(nn.Module):
                 (0, fp.offsets[first_center])]
 
     def _side_stream(self, dev):
-        if not self.wgrad_side_stream:
-            return None
         if self._wgrad_stream is None or self._wgrad_stream.device != dev:
             self._wgrad_stream = torch.cuda.Stream(device=dev)
         return self._wgrad_stream
 
     # The plan itself ------------------------------------------------------------------------
-    def _run_forward(self, x: torch.Tensor, save: bool, keep_predrop: bool = False, reuse=None):
+    # The two readers of the layout switches and of the network's state (arch/unet_route.py): nothing else in this file asks for them.
+    def _forward_facts(self, save: bool, keep_predrop: bool = False) -> ForwardFacts:
+        return ForwardFacts(relu_bits=bool(self.relu_bits), pool_codes=bool(self.pool_codes), fuse_pool=bool(self.fuse_pool),
+                            pool_only=bool(self.pool_only), fuse_drop_pool=bool(self.fuse_drop_pool),
+                            batch_skip_resize=bool(self.batch_skip_resize), late_packs=bool(self.late_packs),
+                            save=bool(save), keep_predrop=bool(keep_predrop),
+                            net_training=bool(self.training), dropout_on=self.dropout_p > 0, batchnorm=self.batchnorm,
+                            masks_external=self.external_dropout_masks is not None, masks_recorded=bool(self.record_dropout_masks),
+                            debug=self._debug is not None)
+
+    def _backward_facts(self, forward: ForwardRoute, need_dx: bool, need_dw: bool, overwrite: bool) -> BackwardFacts:
+        return BackwardFacts(forward=forward, fuse_skip_grad=bool(self.fuse_skip_grad), fuse_stem_wgrad=bool(self.fuse_stem_wgrad),
+                             batch_bias_grads=bool(self.batch_bias_grads), wgrad_side_stream=bool(self.wgrad_side_stream),
+                             need_dx=bool(need_dx), need_dw=bool(need_dw), overwrite=bool(overwrite),
+                             bf16=self.compute_dtype == torch.bfloat16, batchnorm=self.batchnorm, debug=self._debug is not None,
+                             grad_hook_set=self._grad_hook is not None)
+
+    def _run_forward(self, x: torch.Tensor, facts: ForwardFacts, reuse=None):
+        """``facts``: `_forward_facts` of this pass (its caller has gathered them: plan_forward needs them for the packs)."""
         dt, dev = self.compute_dtype, x.device
         B, _, H, W = x.shape
         P = self._packs
         A: Dict[str, torch.Tensor] = {}
+        xs = x.detach().to(torch.float32).reshape(B, H, W, 1)
+        if not xs.is_contiguous():
+            xs = xs.contiguous()
+        A["x"] = xs
+        # a tape to take the encoder from: of the same input tensor, under the same weights (the packs' key), with the pre-dropout tensor and
+        # the codes kept; whether this pass may use it is the planner's part
+        if (reuse is not None and reuse.get("d4pre") is not None and reuse.get("pack_key") == self._pack_key
+                and reuse["x"].data_ptr() == xs.data_ptr() and reuse["x"].shape == xs.shape and all(reuse.get(f"pc{k}") is not None for k in (1, 2, 3))):
+            facts = dataclasses.replace(facts, reuse_offered=True)
+        route = A["route"] = self.last_route["forward"] = plan_forward_pass(facts)
+        p_drop = self.dropout_p
 
         def new(h, w, c, dtype=dt):
             return torch.empty(B, h, w, c, dtype=dtype, device=dev)
@@ -370,44 +401,46 @@ class UNet(nn.Module):
             vec = torch.empty(4, bn.num_features, dtype=torch.float32, device=dev)
             y = torch.empty_like(raw)
             K.bn_fwd(raw, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean, bn.running_var,
-                     self.training, vec[0], vec[1], vec[2], vec[3], y=y, relu=True)
+                     facts.net_training, vec[0], vec[1], vec[2], vec[3], y=y, relu=True)
             bn_recs[name] = (raw, vec, bn)
             return y
 
         bits: Dict[int, torch.Tensor] = {}     # ReLU-gate bits of the activations whose consumer's data gradient masks by them
 
         def want_bits(t, bn):
-            if not (save and self.relu_bits and bn is None):
+            if not (route.keep_bits and bn is None):
                 return None
             b = K.relu_bits_like(t)
             if b is not None:
                 bits[id(t)] = b
             return b
 
-        def conv3(src, conv, dst, bn=None, name=None, gate=False, pool_out=None, pool_codes=None, pool_only=False):
-            """``gate``: dst feeds a convolution whose data gradient is masked by (dst > 0) -- keep the one-bit image of it."""
+        def taped(name):
+            """An activation of the tape this pass shares its encoder with, and its gate bits."""
+            t = reuse[name]
+            if id(t) in reuse["bits"]:
+                bits[id(t)] = reuse["bits"][id(t)]
+            return t
+
+        def conv3(src, conv, dst, bn=None, name=None, gate=False, pool=(None, None, False)):
+            """``gate``: dst feeds a convolution whose data gradient is masked by (dst > 0) -- keep the one-bit image of it.
+            ``pool`` = (pooled, codes, only): dst's max pooling (and its routing codes) from the same call; ``only``: dst itself is not stored."""
             K.conv2d(src, P[id(conv)]["fwd"], conv.bias, dst, relu=bn is None, relu_bits_out=want_bits(dst, bn) if gate else None,
-                     pool_out=pool_out, pool_codes=pool_codes, pool_only=pool_only)
+                     pool_out=pool[0], pool_codes=pool[1], pool_only=pool[2])
             return dst if bn is None else bn_relu(dst, bn, name)
 
-        xs = x.detach().to(torch.float32).reshape(B, H, W, 1)
-        if not xs.is_contiguous():
-            xs = xs.contiguous()
-        A["x"] = xs
-        training = self.training and self.dropout_p > 0
-        masks_out = [] if self.record_dropout_masks else None
+        masks_out = [] if facts.masks_recorded else None
 
         def dropout(src, which):
-            if self.external_dropout_masks is not None:
-                dst = torch.empty_like(src)
-                K.dropout_apply(src, dst, self.external_dropout_masks[which], self.dropout_p)
-                return dst
-            if not training:
+            if route.drop == "none":
                 return src
             dst = torch.empty_like(src)
+            if route.drop == "external":
+                K.dropout_apply(src, dst, self.external_dropout_masks[which], p_drop)
+                return dst
             m = torch.empty(src.shape, dtype=torch.uint8, device=dev) if masks_out is not None else None
             state, parity = drop_turn()
-            K.dropout_fwd(src, dst, self.dropout_p, self.dropout_seed, 0, mask_out=m, calls_dev=state, parity=parity)
+            K.dropout_fwd(src, dst, p_drop, self.dropout_seed, 0, mask_out=m, calls_dev=state, parity=parity)
             if masks_out is not None:
                 masks_out.append(m)
             return dst
@@ -425,125 +458,105 @@ class UNet(nn.Module):
         # encoder ("dec" in the reference's naming)
         h, w = H, W
         src = xs
-        if reuse is not None:
-            # same input tensor, same weights (the packs' key), a training pass with the pre-dropout tensor kept: else run everything
-            ok = (training and not self.batchnorm and self.external_dropout_masks is None and masks_out is None and self._debug is None
-                  and reuse.get("d4pre") is not None and reuse.get("pack_key") == self._pack_key
-                  and reuse["x"].data_ptr() == xs.data_ptr() and reuse["x"].shape == xs.shape and all(reuse.get(f"pc{k}") is not None for k in (1, 2, 3)))
-            if not ok:
-                reuse = None
         for lvl, width in enumerate(_WIDTHS, start=1):
-            if reuse is not None and lvl < 4:
-                a, dd, p, codes = (reuse[f"{k}{lvl}"] for k in ("a", "d", "p", "pc"))
-                if id(a) in reuse["bits"]:
-                    bits[id(a)] = reuse["bits"][id(a)]
-                h, w = p.shape[1], p.shape[2]
-                A[f"a{lvl}"], A[f"d{lvl}"], A[f"p{lvl}"], A[f"pc{lvl}"] = a, dd, p, codes
-                src = p
-                continue
+            kind = route.pool[lvl - 1]
             ca, bna, cb, _ = self._roles[f"dec{lvl}"]
-            if reuse is not None:                # level 4: the two convolutions from the tape, dropout + pool with this pass's mask
-                a, d = reuse["a4"], reuse["d4pre"]
-                if id(a) in reuse["bits"]:
-                    bits[id(a)] = reuse["bits"][id(a)]
-                hp, wp = (h - 4 + 1) // 2, (w - 4 + 1) // 2
-                codes = torch.empty(B, hp, wp, width, dtype=torch.uint8, device=dev)
-                p = new(hp, wp, width)
-                state, parity = drop_turn()
-                K.dropout_maxpool_fwd(d, p, codes, self.dropout_p, self.dropout_seed, state, parity)
-                h, w = hp, wp
-                A[f"a{lvl}"], A[f"d{lvl}"], A[f"p{lvl}"], A[f"pc{lvl}"] = a, _ShapeOf(d), p, codes
-                src = p
-                continue
-            a = new(h - 2, w - 2, width)
-            if lvl == 1:
+            hp, wp = (h - 4 + 1) // 2, (w - 4 + 1) // 2
+            if route.reuse:                      # everything in front of the first dropout comes from the tape
+                a = taped(f"a{lvl}")
+            elif lvl == 1:
+                a = new(h - 2, w - 2, width)
                 K.conv_cin1_fwd(xs, self._w(ca), ca.bias, a, relu=bna is None, relu_bits_out=want_bits(a, bna))
                 if bna is not None:
                     a = bn_relu(a, bna, "a1")
             else:
-                a = conv3(src, ca, a, bna, f"a{lvl}", gate=True)
-            hp, wp = (h - 4 + 1) // 2, (w - 4 + 1) // 2
-            codes = torch.empty(B, hp, wp, width, dtype=torch.uint8, device=dev) if (save and self.pool_codes) else None
-            # the pool reads the convolution's output as it is (no dropout in between: every level but a training pass's fourth)
-            fuse = self.fuse_pool and not (lvl == 4 and (training or self.external_dropout_masks is not None))
-            p = new(hp, wp, width)
-            # ... and alone: the backward pass routes by the codes and never reads the block's full-resolution output
-            only = fuse and self.pool_only and (codes is not None or not save) and self._debug is None
-            d = conv3(a, cb, new(h - 4, w - 4, width), pool_out=p if fuse else None, pool_codes=codes if fuse else None, pool_only=only)
-            # the fourth level of a training pass: dropout and the pool behind it in one launch; the dropped tensor is never written
-            drop_pool = (lvl == 4 and not fuse and training and self.fuse_drop_pool and self.external_dropout_masks is None and masks_out is None
-                         and codes is not None and self._debug is None)
-            if drop_pool:
-                state, parity = drop_turn()
-                K.dropout_maxpool_fwd(d, p, codes, self.dropout_p, self.dropout_seed, state, parity)
-                if keep_predrop and save:
-                    A["d4pre"], A["pack_key"] = d, self._pack_key        # for a later pass over the same input (plan_forward(reuse=...))
-                d = dd = _ShapeOf(d)
+                a = conv3(src, ca, new(h - 2, w - 2, width), bna, f"a{lvl}", gate=True)
+            if kind == "reused":
+                d, p, codes = (reuse[f"{k}{lvl}"] for k in ("d", "p", "pc"))
             else:
-                dd = dropout(d, 0) if lvl == 4 else d
-            if only:
-                # nobody reads the block's full-resolution output again (the backward pass routes by the codes and needs its SHAPE):
-                # the buffer goes back to the allocator now instead of riding in the tape until the backward pass (130 MB at level 1)
-                d = dd = _ShapeOf(d)
-            h, w = hp, wp
-            if not fuse and not drop_pool:
-                K.maxpool_fwd(dd, p, codes=codes)
-            A[f"a{lvl}"], A[f"d{lvl}"], A[f"p{lvl}"], A[f"pc{lvl}"] = a, dd, p, codes
-            src = p
+                # (the dropout + pool launch writes codes whether or not the backward pass will ask for them)
+                codes = new(hp, wp, width, torch.uint8) if (route.keep_codes or kind == "dropout_pool") else None
+                p = new(hp, wp, width)
+                if kind in ("conv", "conv_only"):
+                    d = conv3(a, cb, new(h - 4, w - 4, width), pool=(p, codes, kind == "conv_only"))
+                    if kind == "conv_only":
+                        # nobody reads the block's full-resolution output again (the backward pass routes by the codes and needs its SHAPE):
+                        # the buffer goes back to the allocator now instead of riding in the tape until the backward pass (130 MB at level 1)
+                        d = _ShapeOf(d)
+                elif kind == "dropout_pool":
+                    # the fourth level of a training pass: dropout and the pool behind it in one launch; the dropped tensor is never written
+                    d = reuse["d4pre"] if route.reuse else conv3(a, cb, new(h - 4, w - 4, width))
+                    state, parity = drop_turn()
+                    K.dropout_maxpool_fwd(d, p, codes, p_drop, self.dropout_seed, state, parity)
+                    if route.keep_d4pre:
+                        A["d4pre"], A["pack_key"] = d, self._pack_key        # for a later pass over the same input (plan_forward(reuse=...))
+                    d = _ShapeOf(d)
+                else:
+                    d = conv3(a, cb, new(h - 4, w - 4, width))
+                    if lvl == 4:
+                        d = dropout(d, 0)
+                    K.maxpool_fwd(d, p, codes=codes)
+            A[f"a{lvl}"], A[f"d{lvl}"], A[f"p{lvl}"], A[f"pc{lvl}"] = a, d, p, codes
+            h, w, src = hp, wp, p
         # center
         self._flush_packs()                  # first reader of a transposed pack: the centre's up-convolution below
         # The four skip connections' resizes (pooled tensor -> second half of the decoder level's concatenation) in ONE launch here, where all
-        # four pooled tensors exist, instead of one launch per decoder level (UNet.batch_skip_resize; dct_bilinear_fwd_batched)
+        # four pooled tensors exist, instead of one launch per decoder level (dct_bilinear_fwd_batched)
         cats = {}
-        if self.batch_skip_resize:
+        if route.batch_skip_resize:
             ch, cw = h, w
             for lvl, co in ((4, 512), (3, 256), (2, 128), (1, 64)):
                 ch, cw = 2 * (ch - 4), 2 * (cw - 4)
                 cats[lvl] = new(ch, cw, 2 * co)
             K.bilinear_fwd_batched([A[f"p{lvl}"] for lvl in (4, 3, 2, 1)], [cats[lvl][..., cats[lvl].shape[3] // 2:] for lvl in (4, 3, 2, 1)])
+
+        def up_cat(src, ct, lvl, co):
+            """-> decoder level ``lvl``'s concatenation: the up-convolution of src (+ ReLU) in its first ``co`` channels, the resized skip
+            connection in the others."""
+            cat = cats[lvl] if cats else new(2 * src.shape[1], 2 * src.shape[2], 2 * co)
+            K.conv2d(src, P[id(ct)]["fwd"], ct.bias, cat[..., :co], R=1, S=1, relu=True, scatter2x2=True)
+            if not cats:
+                K.bilinear_fwd(A[f"p{lvl}"], cat[..., co:])
+            return cat
+
         ca, bna, cb, bnb, ct = self._roles["center"]
         c1 = conv3(src, ca, new(h - 2, w - 2, 1024), bna, "c1", gate=True)
         c2 = conv3(c1, cb, new(h - 4, w - 4, 1024), bnb, "c2")
         c2d = dropout(c2, 1)
-        h, w = 2 * (h - 4), 2 * (w - 4)
-        cat = cats[4] if cats else new(h, w, 1024)
-        K.conv2d(c2d, P[id(ct)]["fwd"], ct.bias, cat[..., :512], R=1, S=1, relu=True, scatter2x2=True)
-        if not cats:
-            K.bilinear_fwd(A["p4"], cat[..., 512:])
+        cat = up_cat(c2d, ct, 4, 512)
         A["c1"], A["c2"], A["cat4"] = c1, c2d, cat
         # decoder ("enc")
         for lvl, feat, co in ((4, 512, 256), (3, 256, 128), (2, 128, 64)):
             ca, bna, cb, bnb, ct = self._roles[f"enc{lvl}"]
+            h, w = cat.shape[1], cat.shape[2]
             ea = conv3(cat, ca, new(h - 2, w - 2, feat), bna, f"e{lvl}a", gate=True)
             eb = conv3(ea, cb, new(h - 4, w - 4, feat), bnb, f"e{lvl}b", gate=True)
-            h, w = 2 * (h - 4), 2 * (w - 4)
-            cat = cats[lvl - 1] if cats else new(h, w, 2 * co)
-            K.conv2d(eb, P[id(ct)]["fwd"], ct.bias, cat[..., :co], R=1, S=1, relu=True, scatter2x2=True)
-            if not cats:
-                K.bilinear_fwd(A[f"p{lvl - 1}"], cat[..., co:])
+            cat = up_cat(eb, ct, lvl - 1, co)
             A[f"e{lvl}a"], A[f"e{lvl}b"], A[f"cat{lvl - 1}"] = ea, eb, cat
         ca, bna, cb, _ = self._roles["enc1"]
+        h, w = cat.shape[1], cat.shape[2]
         e1a = conv3(cat, ca, new(h - 2, w - 2, 64), bna, "e1a", gate=True)
         e1b = conv3(e1a, cb, new(h - 4, w - 4, 64))
         f = K.head_fwd(e1b, self._w(self.final), self.final.bias, new(h - 4, w - 4, self.num_classes, torch.float32))
         logits = K.bilinear_fwd(f, new(H, W, self.num_classes, torch.float32))
-        A["bn"], A["bn_training"], A["bits"] = bn_recs, bool(self.training), bits
-        if bn_recs and self.training:      # nn.BatchNorm2d bookkeeping: one multi-tensor launch for all thirteen layers
+        A["bn"], A["bn_training"], A["bits"] = bn_recs, facts.net_training, bits
+        if bn_recs and facts.net_training:      # nn.BatchNorm2d bookkeeping: one multi-tensor launch for all thirteen layers
             torch._foreach_add_([rec[2].num_batches_tracked for rec in bn_recs.values()], 1)
         A["e1a"], A["e1b"] = e1a, e1b
         A["fshape"] = (h - 4, w - 4)
         if masks_out is not None:
             self.last_dropout_masks = masks_out
             self.dropout_mask_log.append(masks_out)
-        drop_scale = 1.0 / (1.0 - self.dropout_p) if (training or self.external_dropout_masks is not None) else 1.0
-        A["drop_scale"] = drop_scale
-        return logits, (A if save else None)
+        A["drop_scale"] = 1.0 / (1.0 - p_drop) if route.scale_by_keep else 1.0
+        return logits, (A if facts.save else None)
 
     def _run_backward(self, A, dlogits: torch.Tensor, need_dx: bool, need_dw: bool, overwrite: bool = False):
         """dlogits: fp32 NHWC [B,H,W,C].  Accumulates parameter grads in place (``overwrite``: writes them -- every
         parameter of the network receives a gradient in every backward pass, so the first pass of a step can replace
         the zero fill of the 124 MB gradient buffer and the read-modify-write of the folds); returns dx or None."""
-        gacc = not overwrite
+        route = self.last_route["backward"] = plan_backward_pass(
+            self._backward_facts(A["route"], need_dx, need_dw, overwrite))
+        gacc = route.accumulate
         dt, dev = self.compute_dtype, dlogits.device
         B = dlogits.shape[0]
         P = self._packs
@@ -559,7 +572,7 @@ class UNet(nn.Module):
         # buffer to a later data-gradient while a weight-gradient kernel still reads it.
         gate_bits = A.get("bits") or {}
         cur = torch.cuda.current_stream(dev)
-        side = self._side_stream(dev) if need_dw else None
+        side = self._side_stream(dev) if route.side_stream else None
         keep: List[torch.Tensor] = []
 
         def on_side(*operands):
@@ -576,7 +589,7 @@ class UNet(nn.Module):
             the stem's weight gradient from this data gradient's output tile (dx_out is then not written; stem_fused[0] tells)."""
             if need_dw:
                 with on_side(dy, x_in):
-                    if dt == torch.bfloat16:     # bias gradient rides along in the weight-gradient launch
+                    if route.bias_in_wgrad:      # bias gradient rides along in the weight-gradient launch
                         K.conv2d_wgrad(dy, x_in, self._gw(conv), accumulate=gacc, db=self._gb(conv))
                     else:
                         K.conv2d_wgrad(dy, x_in, self._gw(conv), accumulate=gacc)
@@ -611,7 +624,7 @@ class UNet(nn.Module):
                 with on_side(dy, x_in):
                     K.conv2d_wgrad(x_in, dy, self._gw(conv), R=2, S=2, stride=2, accumulate=gacc)
                 pending_bias.append((dy, self._gb(conv)))
-                if not self.batch_bias_grads:
+                if not route.batch_bias_grads:
                     flush_bias()
             K.conv2d(dy, P[id(conv)]["dgrad"], None, dx_out, R=2, S=2, stride=2, mask=mask, mask_scale=mask_scale,
                      mask_bits=gate_bits.get(id(mask)))
@@ -630,6 +643,24 @@ class UNet(nn.Module):
                      c1c2, g, training=A["bn_training"], relu=True, accumulate=gacc)
             return g
 
+        dp: Dict[int, torch.Tensor] = {}            # per encoder level: the gradient at its pooled output
+        skip_g: Dict[int, torch.Tensor] = {}
+
+        def skip_bwd(lvl, g):
+            """g: the gradient at the resized copy of level ``lvl``'s pooled output (the second half of a concatenation): left for that level's
+            un-pooling to gather (K.maxpool_bwd(..., skip=)), or brought back to the pooled size now, where the data gradient will add to it."""
+            if route.skip_fused:
+                skip_g[lvl] = g
+            else:
+                dp[lvl] = K.bilinear_bwd(g, new_like(A[f"p{lvl}"]))
+
+        def pooled_bwd(lvl, conv, dy):
+            """The data gradient of the convolution that reads level ``lvl``'s pooled output, into dp[lvl] (onto the skip connection's share
+            where that was summed in memory)."""
+            if route.skip_fused:
+                dp[lvl] = new_like(A[f"p{lvl}"])
+            conv_bwd(conv, A[f"p{lvl}"], dy, dp[lvl], accumulate=not route.skip_fused)
+
         fh, fw = A["fshape"]
         df = K.bilinear_bwd(dlogits, torch.empty(B, fh, fw, C, dtype=torch.float32, device=dev))
         e1b, e1a = A["e1b"], A["e1a"]
@@ -643,70 +674,52 @@ class UNet(nn.Module):
         de1a = bn_back("e1a", conv_bwd(cb, e1a, de1b, new_like(e1a), mask=e1a))
         cat = A["cat1"]
         dcat = conv_bwd(ca, cat, de1a, new_like(cat), mask=cat, mask_channels=64)
-        dp: Dict[int, torch.Tensor] = {}
-        skip_g: Dict[int, torch.Tensor] = {}
-        skip_fused = bool(self.fuse_skip_grad and all(A.get(f"pc{k}") is not None for k in (1, 2, 3, 4)))
         for lvl, co in ((2, 64), (3, 128), (4, 256)):
             ca, _, cb, _, ct = self._roles[f"enc{lvl}"]
             ea, eb = A[f"e{lvl}a"], A[f"e{lvl}b"]
-            p = A[f"p{lvl - 1}"]
-            if skip_fused:
-                skip_g[lvl - 1] = dcat[..., co:]          # gathered by level (lvl - 1)'s un-pooling (K.maxpool_bwd(..., skip=))
-            else:
-                dp[lvl - 1] = K.bilinear_bwd(dcat[..., co:], new_like(p))
+            skip_bwd(lvl - 1, dcat[..., co:])
             deb = bn_back(f"e{lvl}b", convT_bwd(ct, eb, dcat[..., :co], new_like(eb), mask=eb))
             dea = bn_back(f"e{lvl}a", conv_bwd(cb, ea, deb, new_like(ea), mask=ea))
             if self._debug is not None:
                 self._debug[f"de{lvl}b"], self._debug[f"de{lvl}a"], self._debug[f"dcat{lvl - 1}"] = deb, dea, dcat
             cat = A[f"cat{lvl}"]
             dcat = conv_bwd(ca, cat, dea, new_like(cat), mask=cat, mask_channels=2 * co)
-        hook = self._grad_hook if need_dw else None
-        if hook is not None and side is None:
+        if route.bucket_hooks:
             flush_bias()
-            hook(0)                           # decoder-side gradients are complete
+            self._grad_hook(0)                # decoder-side gradients are complete
         # center (cat4: 512 convT channels + 512 skip channels)
         ca, _, cb, _, ct = self._roles["center"]
-        p4 = A["p4"]
-        if skip_fused:
-            skip_g[4] = dcat[..., 512:]
-            dp[4] = new_like(p4)
-        else:
-            dp[4] = K.bilinear_bwd(dcat[..., 512:], new_like(p4))
+        skip_bwd(4, dcat[..., 512:])
         c2d, c1 = A["c2"], A["c1"]
         dc2 = bn_back("c2", convT_bwd(ct, c2d, dcat[..., :512], new_like(c2d), mask=c2d, mask_scale=ds))
         dc1 = bn_back("c1", conv_bwd(cb, c1, dc2, new_like(c1), mask=c1))
-        conv_bwd(ca, p4, dc1, dp[4], accumulate=not skip_fused)
+        pooled_bwd(4, ca, dc1)
         flush_bias()                          # (the centre's up-convolution was the last one)
-        if hook is not None and side is None:
-            hook(1)                           # centre gradients are complete
+        if route.bucket_hooks:
+            self._grad_hook(1)                # centre gradients are complete
         # encoder
         dx = None
         for lvl in (4, 3, 2, 1):
             ca, _, cb, _ = self._roles[f"dec{lvl}"]
             a, d = A[f"a{lvl}"], A[f"d{lvl}"]
-            dd = K.maxpool_bwd(d, dp[lvl], new_like(d), relu_mask=True, scale=ds if lvl == 4 else 1.0, codes=A.get(f"pc{lvl}"),
+            dd = K.maxpool_bwd(d, dp[lvl], new_like(d), relu_mask=True, scale=ds if lvl == 4 else 1.0, codes=A[f"pc{lvl}"],
                                skip=skip_g.get(lvl))
             stem = None
-            if (lvl == 1 and need_dw and not need_dx and self.fuse_stem_wgrad and dt == torch.bfloat16 and side is None and
-                    A["bn"].get("a1") is None and self._debug is None):
+            if lvl == 1 and route.try_stem_fusion:
                 stem = (A["x"], self._gw(ca), self._gb(ca), gacc)       # the stem's dy has no other reader: see dct_conv_desc.stem_x
             da = bn_back(f"a{lvl}", conv_bwd(cb, a, dd, new_like(a), mask=a, stem=stem))
             if lvl > 1:
-                summed = not skip_fused          # dp[lvl - 1] already holds the skip connection's share
-                if not summed:
-                    dp[lvl - 1] = new_like(A[f"p{lvl - 1}"])
-                conv_bwd(ca, A[f"p{lvl - 1}"], da, dp[lvl - 1], accumulate=summed)
+                pooled_bwd(lvl - 1, ca, da)
             else:
-                c0 = ca
                 if need_dw and not stem_fused[0]:
                     with on_side(da):
-                        K.conv_cin1_wgrad(A["x"], da, self._gw(c0), self._gb(c0), accumulate=gacc)
+                        K.conv_cin1_wgrad(A["x"], da, self._gw(ca), self._gb(ca), accumulate=gacc)
                 if need_dx:
-                    dx = K.conv_cin1_dgrad(da, self._w(c0), torch.empty_like(A["x"]), pad_h=0, pad_w=0)
+                    dx = K.conv_cin1_dgrad(da, self._w(ca), torch.empty_like(A["x"]), pad_h=0, pad_w=0)
         if side is not None:
             cur.wait_stream(side)
-        elif hook is not None:
-            hook(2)                           # encoder-side gradients: the whole buffer is final
+        if route.bucket_hooks:
+            self._grad_hook(2)                # encoder-side gradients: the whole buffer is final
         return dx
 
 
@@ -727,7 +740,7 @@ class _UNetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net: UNet, save: bool, x: torch.Tensor, *params):
         need_dw = any(p.requires_grad for p in params)
-        logits, acts = net._run_forward(x, save)
+        logits, acts = net._run_forward(x, net._forward_facts(save))
         ctx.net, ctx.acts, ctx.need_dw = net, acts, need_dw
         ctx.set_materialize_grads(False)
         # logical NCHW view of the physical NHWC logits (channels_last strides)

@@ -548,6 +548,153 @@ def test_step_route_each_switch_governs_its_own_fields():
     assert plan_execution(Plan(model_streams=False), u_adv) == "one_graph" and plan_execution(Plan(batch_lab_unlab=False), u_adv) == "one_graph"
 
 
+# ---- the UNet pass's route (arch/unet_route.py).  Expected values: the predicates of UNet._run_forward / _run_backward as they stood when the
+# two read the switches as they went, restated here with every "x is (not) None" test as a boolean.
+_UNET_FWD = ("relu_bits", "pool_codes", "fuse_pool", "pool_only", "fuse_drop_pool", "batch_skip_resize", "late_packs", "save", "keep_predrop",
+             "reuse_offered", "net_training", "dropout_on", "batchnorm", "masks_external", "masks_recorded", "debug")
+_UNET_BWD = ("fuse_skip_grad", "fuse_stem_wgrad", "batch_bias_grads", "wgrad_side_stream", "need_dx", "need_dw", "overwrite", "bf16", "batchnorm",
+             "debug", "grad_hook_set")
+
+
+def _unet_forward_as_it_stood(relu_bits, pool_codes, fuse_pool, pool_only, fuse_drop_pool, batch_skip_resize, late_packs, save, keep_predrop,
+                              reuse_offered, net_training, dropout_on, batchnorm, masks_external, masks_recorded, debug):
+    """-> (the route's fields, "pc1..4 are all in the tape")."""
+    external_is_none, masks_out_is_none, debug_is_none = not masks_external, not masks_recorded, not debug
+    training = net_training and dropout_on
+    reuse = bool(reuse_offered and (training and not batchnorm and external_is_none and masks_out_is_none and debug_is_none))
+    pool, codes_kept, d4pre = [], [], False
+    for lvl in (1, 2, 3, 4):
+        if reuse:                                   # levels 1-3 from the tape (whose pc1..3 the offer checked); level 4: dropout + pool, codes always
+            pool.append("reused" if lvl < 4 else "dropout_pool")
+            codes_kept.append(True)
+            continue
+        codes = bool(save and pool_codes)           # "codes is not None"
+        fuse = fuse_pool and not (lvl == 4 and (training or not external_is_none))
+        only = fuse and pool_only and (codes or not save) and debug_is_none
+        drop_pool = (lvl == 4 and not fuse and training and fuse_drop_pool and external_is_none and masks_out_is_none
+                     and codes and debug_is_none)
+        if drop_pool and keep_predrop and save:
+            d4pre = True
+        pool.append("conv_only" if only else "conv" if fuse else "dropout_pool" if drop_pool else "separate")
+        codes_kept.append(codes)
+    drop = "external" if not external_is_none else ("device" if training else "none")     # dropout(): the masks first, then "if not training"
+    fields = dict(training=training, drop=drop, scale_by_keep=bool(training or not external_is_none), keep_bits=bool(save and relu_bits),
+                  keep_codes=bool(save and pool_codes), reuse=reuse, pool=tuple(pool), keep_d4pre=d4pre, batch_skip_resize=batch_skip_resize,
+                  late_packs=late_packs)
+    return fields, all(codes_kept)
+
+
+def _unet_backward_as_it_stood(codes_on_every_level, fuse_skip_grad, fuse_stem_wgrad, batch_bias_grads, wgrad_side_stream, need_dx, need_dw,
+                               overwrite, bf16, batchnorm, debug, grad_hook_set):
+    side_is_none = not (need_dw and wgrad_side_stream)              # side = self._side_stream(dev) if need_dw else None
+    hook_is_none = not (need_dw and grad_hook_set)                  # hook = self._grad_hook if need_dw else None
+    return dict(side_stream=not side_is_none, accumulate=not (overwrite and need_dw), bias_in_wgrad=bf16,
+                skip_fused=bool(fuse_skip_grad and codes_on_every_level),
+                try_stem_fusion=bool(need_dw and not need_dx and fuse_stem_wgrad and bf16 and side_is_none and not batchnorm and not debug),
+                bucket_hooks=not hook_is_none and side_is_none, batch_bias_grads=batch_bias_grads)
+
+
+def test_unet_route_table():
+    import dataclasses as dc
+    import itertools
+    from dct_amd.arch.unet_route import BackwardFacts, ForwardFacts, plan_backward_pass, plan_forward_pass
+    assert tuple(f.name for f in dc.fields(ForwardFacts)) == _UNET_FWD and tuple(f.name for f in dc.fields(BackwardFacts))[1:] == _UNET_BWD
+    # every forward row: 2^16
+    routes = {}
+    for row in itertools.product((False, True), repeat=len(_UNET_FWD)):
+        r = plan_forward_pass(ForwardFacts(*row))
+        want, codes = _unet_forward_as_it_stood(*row)
+        assert dc.asdict(r) == want, dict(zip(_UNET_FWD, row))
+        assert routes.setdefault(r, codes) == codes, r        # (what the backward pass needs to know of the codes is in the route)
+    # every backward row, 2^11, over forward routes of both kinds (codes on every level or not), with and without a shared encoder;
+    # then every distinct forward route under the default backward facts and each single flip of them
+    some = sorted(routes, key=repr)[::max(1, len(routes) // 48)]
+    assert {routes[r] for r in some} == {False, True} and {r.reuse for r in some} == {False, True}
+    for fwd in some:
+        for row in itertools.product((False, True), repeat=len(_UNET_BWD)):
+            assert dc.asdict(plan_backward_pass(BackwardFacts(fwd, *row))) == _unet_backward_as_it_stood(routes[fwd], *row), (fwd, row)
+    base = BackwardFacts(None)
+    flips = [{}] + [{k: not getattr(base, k)} for k in _UNET_BWD]
+    for fwd, codes in routes.items():
+        for flip in flips:
+            f = dc.replace(base, forward=fwd, **flip)
+            assert dc.asdict(plan_backward_pass(f)) == _unet_backward_as_it_stood(codes, *dc.astuple(f)[1:]), (fwd, flip)
+    # named rows.  The benchmarked training pass (cfg2 / cfg3: bf16, train mode, p = 0.5, every switch at its default)
+    for keep in (False, True):
+        r = plan_forward_pass(ForwardFacts(keep_predrop=keep))
+        assert r.pool == ("conv_only", "conv_only", "conv_only", "dropout_pool") and r.keep_d4pre == keep
+        assert (r.training, r.drop, r.scale_by_keep, r.keep_bits, r.keep_codes, r.reuse) == (True, "device", True, True, True, False)
+    b = plan_backward_pass(BackwardFacts(r, overwrite=True))
+    assert (b.skip_fused, b.try_stem_fusion, b.bias_in_wgrad, b.accumulate, b.side_stream, b.bucket_hooks) == (True, True, True, False, False, False)
+    # ... its second pass over the same input, handed the first one's tape
+    r = plan_forward_pass(ForwardFacts(reuse_offered=True, keep_predrop=True))
+    assert r.reuse and r.pool == ("reused", "reused", "reused", "dropout_pool") and not r.keep_d4pre
+    for refusal in ("batchnorm", "masks_external", "masks_recorded", "debug"):
+        assert not plan_forward_pass(ForwardFacts(reuse_offered=True, **{refusal: True})).reuse
+    assert not plan_forward_pass(ForwardFacts(reuse_offered=True, net_training=False)).reuse
+    # an eval pass that saves nothing
+    r = plan_forward_pass(ForwardFacts(net_training=False, save=False))
+    assert r.pool == ("conv_only",) * 4 and (r.drop, r.scale_by_keep, r.keep_bits, r.keep_codes) == ("none", False, False, False)
+    # recorded masks, external masks: the fourth level's dropout is a launch of its own
+    r = plan_forward_pass(ForwardFacts(masks_recorded=True))
+    assert r.pool == ("conv_only", "conv_only", "conv_only", "separate") and r.drop == "device"
+    r = plan_forward_pass(ForwardFacts(masks_external=True))
+    assert r.pool[3] == "separate" and r.drop == "external" and r.scale_by_keep
+    assert plan_forward_pass(ForwardFacts(masks_external=True, net_training=False)).drop == "external"
+    # fp32 backward; the side stream
+    fwd = plan_forward_pass(ForwardFacts())
+    b = plan_backward_pass(BackwardFacts(fwd, bf16=False))
+    assert not b.try_stem_fusion and not b.bias_in_wgrad
+    b = plan_backward_pass(BackwardFacts(fwd, wgrad_side_stream=True, grad_hook_set=True))
+    assert b.side_stream and not b.try_stem_fusion and not b.bucket_hooks
+    assert plan_backward_pass(BackwardFacts(fwd, grad_hook_set=True)).bucket_hooks
+    assert not plan_backward_pass(BackwardFacts(fwd, wgrad_side_stream=True, need_dw=False)).side_stream
+
+
+def test_unet_route_each_switch_governs_its_own_fields():
+    """Every UNet switch flipped alone: the route fields that differ from the default route's."""
+    import dataclasses as dc
+    from dct_amd.arch.unet_route import BackwardFacts, ForwardFacts, plan_backward_pass, plan_forward_pass
+
+    def diff(r, base):
+        return {f.name: getattr(r, f.name) for f in dc.fields(r) if getattr(r, f.name) != getattr(base, f.name)}
+
+    def changed(base_facts=ForwardFacts(), back=None, **switch):
+        """-> (forward fields, backward fields) that a switch of either pass changes."""
+        fwd_sw = {k: v for k, v in switch.items() if k in _UNET_FWD}
+        bwd_sw = {k: v for k, v in switch.items() if k not in fwd_sw}
+        f0, f1 = plan_forward_pass(base_facts), plan_forward_pass(dc.replace(base_facts, **fwd_sw))
+        b0, b1 = plan_backward_pass(BackwardFacts(f0, **(back or {}))), plan_backward_pass(BackwardFacts(f1, **dict(back or {}, **bwd_sw)))
+        return diff(f1, f0), diff(b1, b0)
+    # a training pass that saves (default pools: conv_only x 3, dropout_pool)
+    assert changed(relu_bits=False) == (dict(keep_bits=False), {})
+    assert changed(pool_codes=False) == (dict(keep_codes=False, pool=("conv", "conv", "conv", "separate")), dict(skip_fused=False))
+    assert changed(fuse_pool=False) == (dict(pool=("separate", "separate", "separate", "dropout_pool")), {})
+    assert changed(pool_only=False) == (dict(pool=("conv", "conv", "conv", "dropout_pool")), {})
+    assert changed(fuse_drop_pool=False) == (dict(pool=("conv_only", "conv_only", "conv_only", "separate")), {})
+    assert changed(batch_skip_resize=False) == (dict(batch_skip_resize=False), {})
+    assert changed(late_packs=False) == (dict(late_packs=False), {})
+    assert changed(fuse_skip_grad=False) == ({}, dict(skip_fused=False))
+    assert changed(fuse_stem_wgrad=False) == ({}, dict(try_stem_fusion=False))
+    assert changed(batch_bias_grads=False) == ({}, dict(batch_bias_grads=False))
+    assert changed(wgrad_side_stream=True) == ({}, dict(side_stream=True, try_stem_fusion=False))
+    assert changed(back=dict(grad_hook_set=True), wgrad_side_stream=True) == ({}, dict(side_stream=True, try_stem_fusion=False, bucket_hooks=False))
+    assert changed(back=dict(need_dw=False), wgrad_side_stream=True) == ({}, {})
+    # an eval pass (all four pools ride in their convolutions): the dropout + pool switch governs nothing
+    ev = ForwardFacts(net_training=False)
+    assert changed(ev, fuse_drop_pool=False) == ({}, {})
+    assert changed(ev, fuse_pool=False) == (dict(pool=("separate",) * 4), {})
+    assert changed(ev, pool_only=False) == (dict(pool=("conv",) * 4), {})
+    assert changed(ev, pool_codes=False) == (dict(keep_codes=False, pool=("conv",) * 4), dict(skip_fused=False))
+    # ... that saves nothing: no codes to keep, nothing for the backward pass to need
+    assert changed(dc.replace(ev, save=False), pool_codes=False) == ({}, {}) and changed(dc.replace(ev, save=False), relu_bits=False) == ({}, {})
+    # a pass over a shared encoder: only what lies behind the first dropout can still be switched
+    sh = ForwardFacts(reuse_offered=True)
+    for name in ("fuse_pool", "pool_only", "fuse_drop_pool"):
+        assert changed(sh, **{name: False}) == ({}, {}), name
+    assert changed(sh, pool_codes=False) == (dict(keep_codes=False), {})          # (the tape's codes and the dropout + pool launch's are there)
+
+
 def test_refused_capture_filter_recognises_the_runtime_messages():
     """step_graph keeps a step shape on eager launches only for refused captures; the library's own launch errors propagate."""
     from dct_amd.trainer.step_graph import _is_refused_capture

@@ -301,6 +301,34 @@ def test_unet_second_pass_over_the_same_input_reuses_the_encoder_bit_for_bit():
     assert not torch.equal(outs[0][0], outs[0][1])                             # (the two passes drew different masks)
 
 
+def test_unet_tape_carries_its_route():
+    """The tape holds the route its forward pass was recorded under (arch/unet_route.py), and the backward pass follows THAT: switches of the
+    forward layout flipped between the two passes change no gradient."""
+    from dct_amd.arch.unet_route import plan_forward_pass
+    C = 3
+    onet = _oracle_net(C, 37, p=0.5).train()
+    x = torch.rand(1, 1, 176, 176, generator=torch.Generator().manual_seed(76)).to(DEV)
+    gl = torch.randn(1, 176, 176, C, generator=torch.Generator().manual_seed(77)).to(DEV)
+    outs = []
+    for flip in (False, True):
+        net = _hip_net(onet, C, torch.bfloat16, p=0.5).train()
+        net.dropout_seed = 80
+        lp, tape = net.plan_forward(x, True)
+        route = tape["route"]
+        assert route == plan_forward_pass(net._forward_facts(True)) and net.last_route["forward"] is route
+        assert route.pool == ("conv_only", "conv_only", "conv_only", "dropout_pool") and route.keep_codes and route.keep_bits
+        if flip:
+            net.pool_codes = net.fuse_pool = False
+            assert plan_forward_pass(net._forward_facts(True)) != route
+        dx = net.plan_backward(tape, gl, need_dx=True, need_dw=True, overwrite=True)
+        torch.cuda.synchronize()
+        assert net.last_route["backward"].skip_fused and not net.last_route["backward"].accumulate
+        outs.append([lp.clone(), dx.clone(), net.flat_params.gflat.clone()])
+    for k, a, b in zip(("logits", "grad_x", "flat gradient buffer"), *outs):
+        assert torch.isfinite(a).all() and a.abs().max().item() > 0, k
+        assert torch.equal(a, b), k
+
+
 def test_unet_rejects_small_and_cpu_inputs():
     from dct_amd.arch import get_arch
     net = get_arch("unet", {"num_classes": 4}).to(DEV)

@@ -24,7 +24,7 @@ def main(B, H, W, C, dtype):
     yo.backward(gl)
     net._ensure_packs()
     xd = x.to("cuda:0")
-    logits, A = net._run_forward(xd, True)
+    logits, A = net._run_forward(xd, net._forward_facts(True))
     m = {"dec1": "p1", "dec2": "p2", "dec3": "p3", "dec4": "p4", "enc1": "e1b"}
     print(f"== B{B} {H}x{W} C{C} {dtype}")
     for k, ak in m.items():
