@@ -638,6 +638,37 @@ def hausdorff(logits_bhwc, gt_bhw, method3d=False, spacing=(1., 1., 1.)):
     return hd2
 
 
+def confusion_counts(logits: List[torch.Tensor], gt: Optional[torch.Tensor] = None):
+    """logits: S fp32 tensors [B, pix, C] (or [B, H, W, C]), the predictions of S raters on one batch; gt [B, pix] (or [B, H, W])
+    int64 or None -> int32 [B, P, C, C]: the confusion matrix of every pair of raters per image, gt being the last rater, pairs
+    (i, j), i < j, in lexicographic order (``dct_confusion_counts``, include/dct.h)."""
+    if not isinstance(logits, (list, tuple)) or len(logits) < 1:
+        raise ValueError("confusion_counts needs a list of at least one logits tensor")
+    shape = logits[0].shape
+    if len(shape) not in (3, 4) or any(t.shape != shape for t in logits):
+        raise ValueError(f"confusion_counts needs tensors of one shape [B, pix, C] or [B, H, W, C], got {[tuple(t.shape) for t in logits]}")
+    B, C_ = shape[0], shape[-1]
+    ppi = 1
+    for d in shape[1:-1]:
+        ppi *= d
+    if gt is not None and gt.numel() != B * ppi:
+        raise ValueError(f"confusion_counts: gt {tuple(gt.shape)} does not match logits {tuple(shape)}")
+
+    def dense(t, dtype):
+        ptr(t)                              # (refuses a CPU tensor before anything is copied)
+        if t.dtype != dtype or not t.is_contiguous():
+            t = t.to(dtype).contiguous()
+        # the kernel reads a pixel at a time, 16 bytes at C = 4: a dense view that starts inside its storage gets a copy of its own
+        return t.clone() if t.data_ptr() % 16 else t
+
+    ls = [dense(t.detach(), torch.float32) for t in logits]
+    g = dense(gt, torch.int64) if gt is not None else None
+    R = len(ls) + (g is not None)
+    cnt = torch.zeros(B, R * (R - 1) // 2, C_, C_, dtype=torch.int32, device=ls[0].device)
+    call("dct_confusion_counts", _ptr_array(ls), len(ls), ptr(g), B, ppi, C_, ptr(cnt), stream())
+    return cnt
+
+
 # ------------------------------------------------------------------------------ Enet family
 class Tf(object):
     """Producer transform act(scale*x + shift) applied by consumers on load (include/dct.h dct_enet_tf)."""

@@ -1,16 +1,19 @@
 """Meters used inside the step (reference: generalframework/metrics/dice_meter.py:12-83,
 averagemeter.py:3-48), kept on the device: ``add`` launches one counting kernel and never
 synchronises; ``value`` is where the (tiny) results are read.  ``HausdorffMeter`` is the second column of the reference's
-result tables (Summary.py:70-252), which takes it from an external package: here ``dct_hausdorff`` (include/dct.h)."""
+result tables (Summary.py:70-252), which takes it from an external package: here ``dct_hausdorff`` (include/dct.h).
+``AgreementMeter`` is the third: Cohen's kappa between every pair of raters (the models, an ensemble, gt), and the IoU of the
+reference's ``IoU`` / ``ConfusionMatrix`` meters, from the pairwise confusion matrices of ``dct_confusion_counts``."""
 from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from .. import hip_ops as K
 
-__all__ = ["DiceMeter", "HausdorffMeter", "AverageValueMeter"]
+__all__ = ["DiceMeter", "HausdorffMeter", "AgreementMeter", "AverageValueMeter", "pair_index", "kappa_of", "iou_of"]
 
 
 class DiceMeter(object):
@@ -176,6 +179,154 @@ class HausdorffMeter(object):
     def summary(self) -> dict:
         (means, var), (_, _) = self.value()
         return {'mHD': means.item(), 'mVars': var.item()}
+
+
+def pair_index(i: int, j: int, R: int) -> int:
+    """Index of the pair (i, j), i < j, of R raters in lexicographic order (include/dct.h, ``dct_confusion_counts``)."""
+    assert 0 <= i < j < R, (i, j, R)
+    return i * (2 * R - i - 1) // 2 + (j - i - 1)
+
+
+def kappa_of(M, cols=None):
+    """Cohen's kappa (unweighted) of confusion matrices M [..., C, C] in float64: (po - pe) / (1 - pe), po = tr M / n,
+    pe = sum_k row_k col_k / n^2; NaN where n = 0 or pe = 1.  ``cols``: keep only these columns (the pixels whose second
+    rater lies in this class set -- the reference's ``considered_classes`` on the target)."""
+    M = np.asarray(M, dtype=np.float64)
+    if cols is not None:
+        keep = np.zeros(M.shape[-1])
+        keep[list(cols)] = 1.0
+        M = M * keep
+    n = M.sum((-2, -1))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        po = np.trace(M, axis1=-2, axis2=-1) / n
+        pe = (M.sum(-1) * M.sum(-2)).sum(-1) / (n * n)
+        k = (po - pe) / (1.0 - pe)
+    return np.where((n == 0) | (pe == 1.0), np.nan, k)
+
+
+def iou_of(M):
+    """IoU per class of confusion matrices M [..., C, C] in float64: M[c][c] / (row_c + col_c - M[c][c]), NaN where that is 0."""
+    M = np.asarray(M, dtype=np.float64)
+    d = np.diagonal(M, axis1=-2, axis2=-1)
+    den = M.sum(-1) + M.sum(-2) - d
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(den == 0, np.nan, d / den)
+
+
+def _nan_moments(v):
+    """mean, sample std and count over the defined (non-NaN) entries along axis 0 of v [n, ...]; NaN where there are too few."""
+    ok = ~np.isnan(v)
+    n = ok.sum(0)
+    z = np.where(ok, v, 0.0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mean = np.where(n > 0, z.sum(0) / np.maximum(n, 1), np.nan)
+        dev = np.where(ok, v - mean, 0.0)
+        std = np.where(n > 1, np.sqrt((dev * dev).sum(0) / np.maximum(n - 1, 1)), np.nan)
+    return mean, std, n
+
+
+class AgreementMeter(object):
+    """Agreement between ``n_models`` predictions (and gt, the last rater, ``with_gt``) from the confusion matrix of every pair
+    of raters (``dct_confusion_counts``, one launch per ``add``): '2d' = one row per slice, '3d' = one row for the batch.
+    ``kappa`` is Cohen's kappa per pair, restricted to the pixels whose second rater lies in ``considered_classes`` when that is
+    set; ``iou`` the IoU per model and class against gt.  A kappa or IoU that is undefined on a row (include/dct.h) is NaN, is
+    left out of every statistic and is not counted in ``defined``.  ``rater_names`` renames the predictions (default ``S{i}``)."""
+
+    def __init__(self, method='2d', C=4, n_models=2, with_gt=True, considered_classes=None, rater_names=None) -> None:
+        assert method in ('2d', '3d')
+        assert 1 <= n_models <= 8 and n_models + bool(with_gt) >= 2, (n_models, with_gt)
+        assert 1 <= C <= 8, C
+        assert considered_classes is None or all(0 <= int(c) < C for c in considered_classes), considered_classes
+        self.method = method
+        self.C = C
+        self.n_models = n_models
+        self.with_gt = bool(with_gt)
+        self.considered_classes = None if considered_classes is None else [int(c) for c in considered_classes]
+        names = list(rater_names) if rater_names is not None else [f"S{i}" for i in range(n_models)]
+        assert len(names) == n_models, names
+        self.raters = names + (["gt"] if self.with_gt else [])
+        R = len(self.raters)
+        self.pairs = [f"{self.raters[i]}_{self.raters[j]}" for i in range(R) for j in range(i + 1, R)]
+        self._gt_pairs = [pair_index(i, R - 1, R) for i in range(n_models)] if self.with_gt else []
+        self.reset()
+
+    def reset(self):
+        self.countLog = []
+        self._cache = None
+
+    def add(self, preds, gt=None):
+        """preds: ``n_models`` tensors [B,C,H,W] (logits or probabilities: only the argmax matters), gt [B,1,H,W] integer (None
+        without ``with_gt``)."""
+        if not isinstance(preds, (list, tuple)) or len(preds) != self.n_models:
+            raise RuntimeError(f"dct_amd AgreementMeter was built for a list of {self.n_models} predictions")
+        if self.with_gt != (gt is not None):
+            raise RuntimeError("dct_amd AgreementMeter: gt is " + ("required" if self.with_gt else "not expected (with_gt=False)"))
+        if any(not p.is_cuda for p in preds) or (gt is not None and not gt.is_cuda):
+            raise RuntimeError("dct_amd AgreementMeter counts on the HIP device only (no CPU fallback)")
+        B = preds[0].shape[0]
+        ls = [p.detach().permute(0, 2, 3, 1) for p in preds]
+        g = gt.reshape(B, -1) if gt is not None else None
+        cnt = K.confusion_counts(ls, g).to(torch.int64)      # (confusion_counts makes the dense fp32 / int64 copies it needs)
+        if self.method == '3d':
+            cnt = cnt.sum(0, keepdim=True)
+        self.countLog.append(cnt)                               # nothing here waits for the device
+        self._cache = None
+
+    def _rows(self):
+        # ONE device->host copy of the log per reading (cached until the next add); everything derived is float64 host
+        # arithmetic on rows x P x C x C integers
+        if self._cache is None:
+            if self.countLog:
+                rows = torch.cat(self.countLog).cpu().numpy()
+            else:
+                rows = np.zeros((0, len(self.pairs), self.C, self.C), dtype=np.int64)
+            self._cache = {'rows': rows}
+        return self._cache['rows']
+
+    def confusion(self):
+        """int64 [P, C, C]: the confusion matrix of every pair over everything added."""
+        return torch.from_numpy(self._rows().sum(0))
+
+    def _kappa_stats(self):
+        rows = self._rows()
+        if 'kappa' not in self._cache:
+            k = kappa_of(rows, self.considered_classes)              # [rows, P]
+            mean, std, n = _nan_moments(k)
+            report = self._gt_pairs or list(range(len(self.pairs)))
+            with np.errstate(invalid='ignore'):
+                rep = _nan_moments(k[:, report].T)[0]                # a row's report value: the mean over its defined report pairs
+            rmean, rstd, _ = _nan_moments(rep[:, None])
+            self._cache['kappa'] = (mean, std, n, float(rmean[0]), float(rstd[0]))
+        return self._cache['kappa']
+
+    def kappa(self):
+        """(mean [P], std [P], defined [P]) of the per-row kappa of every pair, in the order of ``pairs``."""
+        mean, std, n, _, _ = self._kappa_stats()
+        return torch.from_numpy(mean), torch.from_numpy(std), torch.from_numpy(n)
+
+    def iou(self):
+        """(mean [n_models, C], std [n_models, C]) of the per-row IoU of every model against gt."""
+        if not self.with_gt:
+            raise RuntimeError("dct_amd AgreementMeter.iou needs with_gt=True")
+        rows = self._rows()
+        if 'iou' not in self._cache:
+            mean, std, _ = _nan_moments(iou_of(rows[:, self._gt_pairs]))
+            self._cache['iou'] = (mean, std)
+        mean, std = self._cache['iou']
+        return torch.from_numpy(mean), torch.from_numpy(std)
+
+    def value(self, **kwargs):
+        mean, std, _, rmean, rstd = self._kappa_stats()
+        return (rmean, rstd), (torch.from_numpy(mean), torch.from_numpy(std))
+
+    def detailed_summary(self) -> dict:
+        mean = self._kappa_stats()[0]
+        return {name: float(mean[p]) for p, name in enumerate(self.pairs)}
+
+    def summary(self) -> dict:
+        """Mean (and std) over the rows of a row's mean kappa over the pairs that contain gt (all pairs without gt)."""
+        (mean, std), _ = self.value()
+        return {'mKappa': mean, 'mVars': std}
 
 
 class AverageValueMeter(object):

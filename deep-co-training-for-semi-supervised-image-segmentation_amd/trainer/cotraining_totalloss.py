@@ -33,7 +33,7 @@ from torch import Tensor, nn
 
 from .. import ModelMode
 from .. import scheduler
-from ..metrics import AverageValueMeter, DiceMeter, HausdorffMeter
+from ..metrics import AgreementMeter, AverageValueMeter, DiceMeter, HausdorffMeter
 from ..models import Segmentator
 from ..utils import iterator_, map_, dict_merge, tqdm_
 from ..utils.AEGenerator import FSGMGenerator
@@ -161,8 +161,12 @@ class CoTrainer(Trainer):
                  steps_per_epoch: int = 300,
                  grad_sync=None,
                  val_hausdorff: bool = False,
-                 val_spacing=(1., 1., 1.)) -> None:
+                 val_spacing=(1., 1., 1.),
+                 val_kappa: bool = False) -> None:
         self.max_epoch = max_epoch
+        # opt-in: _eval_loop also measures Cohen's kappa between every pair of views and of each view with gt (3-D, restricted to the
+        # pixels whose second rater lies in `axises`) and uploads it as 'val_kappa': the agreement that the JSD term drives
+        self.val_kappa = bool(val_kappa)
         # opt-in: _eval_loop also measures the 3-D Hausdorff distance per model (voxel spacing (sz, sy, sx)) and uploads it as 'val_hd'
         self.val_hausdorff = bool(val_hausdorff)
         self.val_spacing = tuple(val_spacing)
@@ -1120,11 +1124,15 @@ class CoTrainer(Trainer):
         vallossMeters = [AverageValueMeter() for _ in range(S)]
         hdMeters = [HausdorffMeter(report_axises=self.axises, method='3d', C=self.C, spacing=self.val_spacing)
                     for _ in range(S)] if self.val_hausdorff else []
+        kappaMeter = AgreementMeter(method='3d', C=self.C, n_models=S, with_gt=True,
+                                    considered_classes=list(self.axises)) if self.val_kappa else None
         val_iter = tqdm_(val_dataloader) if self.use_tqdm else val_dataloader
         for batch_num, [(img, gt), _, path] in enumerate(val_iter):
             img, gt = img.to(self.device), gt.to(self.device)
             preds = map_(lambda x: x.predict(img, logit=True), self.segmentators)
             loss = map_(lambda pred: self.criterions.get('sup')(pred, gt.squeeze(1)), preds)
+            if kappaMeter is not None:
+                kappaMeter.add(list(preds), gt)
             for i in range(S):
                 coefdiceMeters[i].add(preds[i], gt)
                 batchdiceMeters[i].add(preds[i], gt)
@@ -1138,6 +1146,8 @@ class CoTrainer(Trainer):
         if hdMeters:
             vals = [m.value() for m in hdMeters]
             self.upload_dicts('val_hd', {f"S{i}": {f"HD{n}": float(vals[i][1][0][n]) for n in self.axises} for i in range(S)}, epoch)
+        if kappaMeter is not None:
+            self.upload_dicts('val_kappa', {pair: {'kappa': k} for pair, k in kappaMeter.detailed_summary().items()}, epoch)
         nice_dict = self._report_dict(batchdiceMeters)
         if self._is_main():
             print(f"{desc} " + ', '.join([f'{k}_{k_}: {v[k_]:.2f}' for k, v in nice_dict.items() for k_ in v.keys()]))

@@ -483,6 +483,28 @@ int dct_hausdorff(const float* logits /*[B][H][W][C]*/, const int64_t* gt /*[B][
                   int B, int H, int W, int C, int method3d, float sz, float sy, float sx,
                   float* hd2 /*[rows][C]*/, void* workspace, size_t workspace_bytes, dct_stream stream);
 
+/* ---- Agreement between raters on device: pairwise confusion matrices (the kappa table of Summary.py:70-252, which takes
+ * cohen_kappa_score from scikit-learn; the same counts give the reference's ConfusionMatrix and IoU meters) -------------------
+ * Raters: the S predictions are raters 0..S-1; the class of a pixel is the argmax of its logits, first maximum, exactly as
+ *   dct_argmax / dct_dice_counts.  When gt != NULL, gt is rater S.  R = S + (gt ? 1 : 0).
+ * Pairs: (i, j) with i < j in lexicographic order: p = i (2R - i - 1) / 2 + (j - i - 1); P = R (R - 1) / 2.
+ * Counts: counts[b][p][a][c] (int32) += the number of pixels of image b where rater i says class a and rater j says class c.  A
+ *   pixel whose gt value is outside [0, C) (255, negative, >= C) is counted in no pair that contains gt, and still in every
+ *   prediction-against-prediction pair.
+ * Derived quantities are host arithmetic in float64 on a matrix M with n = sum M, both unweighted:
+ *   kappa = (po - pe) / (1 - pe), po = tr M / n, pe = sum_k row_k col_k / n^2; NaN when n = 0 or pe = 1 (scikit-learn's
+ *   cohen_kappa_score gives NaN in the same cases).
+ *   IoU_c = M[c][c] / (row_c + col_c - M[c][c]), NaN where that denominator is 0.
+ *   kappa restricted to the pixels whose SECOND rater lies in a class set = kappa of M with the other columns zeroed (the
+ *   reference's considered_classes on the target): the kernel needs no mask argument.
+ * One launch reads every pixel of every rater once ((4 C S + 8) bytes per pixel); integer sums: bit-identical from run to run.
+ * logits: S host-side entries, each a device [B][pixels][C] fp32 tensor aligned to its pixel (16 bytes at C = 4, 8 at C = 2, else
+ * 4); counts is zeroed by the caller (or holds earlier counts: the call adds).  No workspace.
+ * DCT_ERR_BAD_ARG: a null logits / entry / counts, a misaligned pointer, S < 1, B < 1, pixels < 1, R < 2 (S = 1 without gt);
+ * DCT_ERR_UNSUPPORTED: S > 8, C < 1 or C > 8, pixels_per_image >= 2^31 (a per-image count must fit int32), B > 65535. */
+int dct_confusion_counts(const float* const* logits, int S, const int64_t* gt /*[B][pixels], nullable*/,
+                         int B, int64_t pixels_per_image, int C, int32_t* counts /*[B][P][C][C]*/, dct_stream stream);
+
 /* ---- per-kernel-class timing (bench.py roofline leg) --------------------------------------
  * When enabled every launch made through this library is bracketed by hipEvents on its stream;
  * dct_prof_read synchronises and returns accumulated milliseconds and launch counts per class. */
