@@ -146,6 +146,118 @@ __global__ __launch_bounds__(256) void ce_bwd_fin_kernel(const float* logits, co
   }
 }
 
+// ---- class-weighted cross entropy, sum reduction, per-pixel map (the rule: include/dct.h) ---------------------------------------------
+// The C class weights are read once per wave (a uniform address: they sit in scalar registers) and w_t is picked by the select that picks
+// x_t -- never weight[t].  A target outside [0, C) is ignored like ignore_index: w = 0, no logit read for the value, gradient exactly 0.
+template <int C> __device__ __forceinline__ void load_weights(const float* weight, float wr[C]) {
+#pragma unroll
+  for (int c = 0; c < C; ++c) wr[c] = weight ? weight[c] : 1.f;
+}
+template <int C> __device__ __forceinline__ bool counted(long long t, int ignore) { return t != ignore && t >= 0 && t < C; }
+template <int C> __device__ __forceinline__ float weight_of(long long t, const float wr[C]) {
+  float w = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) w = (t == c) ? wr[c] : w;
+  return w;
+}
+// w_t and l = logsumexp(x) - x_t of one counted pixel
+template <int C> __device__ __forceinline__ float ce_px(const float* logits, long long pix, long long t, const float wr[C], float& w) {
+  float x[C], p[C];
+  load_px<C>(logits, pix, x);
+  const float lse = softmax_px<C>(x, p);
+  float xt = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) xt = (t == c) ? x[c] : xt;
+  w = weight_of<C>(t, wr);
+  return lse - xt;
+}
+// dl (=|+=) (g * w_t) * (p - onehot) over the grid's pixels; g_px (nullable): a per-pixel factor times g (the map's dmap)
+template <int C>
+__device__ __forceinline__ void ce_w_grad_pixels(const float* logits, const long long* tgt, long long P, int ignore, const float wr[C], float g,
+                                                 const float* g_px, float* dl, int acc) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[pix];
+    const bool on = counted<C>(t, ignore);
+    float x[C], p[C], d[C];
+    load_px<C>(logits, pix, x);
+    softmax_px<C>(x, p);
+    const float gw = (g_px ? g * g_px[pix] : g) * weight_of<C>(t, wr);
+#pragma unroll
+    for (int c = 0; c < C; ++c) d[c] = on ? gw * (p[c] - (t == c ? 1.f : 0.f)) : 0.f;
+    store_px<C>(dl, pix, d, acc);
+  }
+}
+// partial[2b] = the block's sum of w l, partial[2b + 1] = its sum of w (ce_fwd_kernel's walk; with all weights 1 its partials)
+template <int C>
+__global__ __launch_bounds__(256) void ce_w_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                        float* partial) {
+  float wr[C];
+  load_weights<C>(weight, wr);
+  float sum = 0.f, den = 0.f;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[pix];
+    if (!counted<C>(t, ignore)) continue;
+    float w;
+    const float l = ce_px<C>(logits, pix, t, wr, w);
+    sum += w * l; den += w;
+  }
+  block_partial2(sum, den, partial);
+}
+template <int C>
+__global__ __launch_bounds__(256) void ce_w_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                        const float* denom, const float* gscale, float gmul, float* dl, int acc) {
+  float wr[C];
+  load_weights<C>(weight, wr);
+  float g = (gscale ? gscale[0] : 1.f) * gmul;
+  if (denom) g = g / denom[0];          // (the sum reduction passes none: its denominator is 1)
+  ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, g, nullptr, dl, acc);
+}
+// ce_bwd_fin_kernel's fold (finalize_kernel's order, in every block) in front of the weighted gradient
+template <int C>
+__global__ __launch_bounds__(256) void ce_w_bwd_fin_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                            int mean, const float* partial, int blocks, float* out2, const float* gscale,
+                                                            float gmul, float* dl, int acc) {
+  __shared__ float sa[256], sb[256];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
+  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  const float den = sb[0];
+  if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = mean ? sa[0] / den : sa[0]; out2[1] = den; }
+  float wr[C];
+  load_weights<C>(weight, wr);
+  float g = (gscale ? gscale[0] : 1.f) * gmul;
+  if (mean) g = g / den;
+  ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, g, nullptr, dl, acc);
+}
+template <int C>
+__global__ __launch_bounds__(256) void ce_map_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                          float* map) {
+  float wr[C];
+  load_weights<C>(weight, wr);
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[pix];
+    float v = 0.f;
+    if (counted<C>(t, ignore)) {
+      float w;
+      const float l = ce_px<C>(logits, pix, t, wr, w);
+      v = w * l;
+    }
+    map[pix] = v;
+  }
+}
+template <int C>
+__global__ __launch_bounds__(256) void ce_map_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                          const float* dmap, float gmul, float* dl, int acc) {
+  float wr[C];
+  load_weights<C>(weight, wr);
+  ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, gmul, dmap, dl, acc);
+}
+
 // ---- softmax / entropy (module API) -------------------------------------------------------------
 template <int C>
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* logits, float* probs, long long P) {
@@ -592,6 +704,54 @@ extern "C" int dct_ce_step(const float* logits, const int64_t* targets, int64_t 
   DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, (float*)workspace));
   DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_bwd_fin_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index,
                             (const float*)workspace, (int)grid, out2, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+extern "C" int dct_ce_weighted_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                                   int reduction, float* out2, void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !out2 || pixels < 1 || (reduction != 0 && reduction != 1)) return DCT_ERR_BAD_ARG;
+  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_w_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, (float*)workspace));
+  DCT_LAUNCH(DCT_PROF_LOSS, finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, reduction == 0 ? 1 : 0, 1.f, 1);
+  return dct_check_launch();
+}
+extern "C" int dct_ce_weighted_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                                   int reduction, const float* denom, const float* gscale, float gmul, float* dlogits, int accumulate,
+                                   dct_stream stream) {
+  if (!logits || !targets || !dlogits || pixels < 1 || (reduction != 0 && reduction != 1) || (reduction == 0 && !denom)) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_w_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
+                            reduction == 0 ? denom : (const float*)nullptr, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+extern "C" int dct_ce_weighted_step(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                                    int reduction, float* out2, const float* gscale, float gmul, float* dlogits, int accumulate,
+                                    void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !out2 || !dlogits || pixels < 1 || (reduction != 0 && reduction != 1)) return DCT_ERR_BAD_ARG;
+  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);       // dct_ce_weighted_fwd's grid: the same block partials
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_w_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, (float*)workspace));
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_w_bwd_fin_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
+                            reduction == 0 ? 1 : 0, (const float*)workspace, (int)grid, out2, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+extern "C" int dct_ce_map_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                              float* map, dct_stream stream) {
+  if (!logits || !targets || !map || pixels < 1) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_map_fwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, map));
+  return dct_check_launch();
+}
+extern "C" int dct_ce_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                              const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream) {
+  if (!logits || !targets || !dmap || !dlogits || pixels < 1) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_map_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, dmap, gmul,
+                            dlogits, accumulate));
   return dct_check_launch();
 }
 extern "C" int dct_softmax_fwd(const float* logits, float* probs, int64_t pixels, int C_, dct_stream stream) {

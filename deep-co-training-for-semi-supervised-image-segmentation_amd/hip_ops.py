@@ -483,6 +483,50 @@ def ce_step(logits_pc, targets, C_, dlogits, gscale=None, gmul=1.0, ignore_index
     return out
 
 
+CE_MEAN, CE_SUM = 0, 1      # the ``reduction`` argument of dct_ce_weighted_*
+
+
+def ce_weighted_fwd(logits_pc, targets, C_, weight=None, reduction=CE_MEAN, ignore_index=255):
+    """``weight``: fp32 [C] on the device, or None (all ones).  Returns the device tensor [2] = (sum w l / sum w | sum w l, sum w)."""
+    out = torch.empty(2, dtype=torch.float32, device=logits_pc.device)
+    ws = _loss_ws(logits_pc.device)
+    call("dct_ce_weighted_fwd", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), int(reduction),
+         ptr(out), ptr(ws), ws.numel(), stream())
+    return out
+
+
+def ce_weighted_bwd(logits_pc, targets, C_, denom, dlogits, weight=None, reduction=CE_MEAN, gscale=None, gmul=1.0, ignore_index=255,
+                    accumulate=False):
+    """``denom``: ``out[1:2]`` of ce_weighted_fwd (not read under CE_SUM, where it may be None)."""
+    call("dct_ce_weighted_bwd", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), int(reduction),
+         ptr(denom), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), stream())
+    return dlogits
+
+
+def ce_weighted_step(logits_pc, targets, C_, dlogits, weight=None, reduction=CE_MEAN, gscale=None, gmul=1.0, ignore_index=255,
+                     accumulate=False):
+    """ce_weighted_fwd + ce_weighted_bwd of the same logits in two launches (dct_ce_weighted_step; bit for bit the two calls).  Returns the
+    device tensor [2]; ``dlogits`` is written (added to)."""
+    out = torch.empty(2, dtype=torch.float32, device=logits_pc.device)
+    ws = _loss_ws(logits_pc.device)
+    call("dct_ce_weighted_step", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), int(reduction),
+         ptr(out), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), ptr(ws), ws.numel(), stream())
+    return out
+
+
+def ce_map_fwd(logits_pc, targets, C_, weight=None, ignore_index=255):
+    """-> fp32 [P]: w_t * (logsumexp(x) - x_t) per pixel, 0 where the target is ignored."""
+    m = torch.empty(logits_pc.numel() // C_, dtype=torch.float32, device=logits_pc.device)
+    call("dct_ce_map_fwd", ptr(logits_pc), ptr(targets), m.numel(), C_, int(ignore_index), ptr(weight), ptr(m), stream())
+    return m
+
+
+def ce_map_bwd(logits_pc, targets, C_, dmap, dlogits, weight=None, gmul=1.0, ignore_index=255, accumulate=False):
+    call("dct_ce_map_bwd", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), ptr(dmap), float(gmul),
+         ptr(dlogits), int(accumulate), stream())
+    return dlogits
+
+
 def softmax_fwd(logits_pc, C_):
     probs = torch.empty_like(logits_pc)
     call("dct_softmax_fwd", ptr(logits_pc), ptr(probs), logits_pc.numel() // C_, C_, stream())

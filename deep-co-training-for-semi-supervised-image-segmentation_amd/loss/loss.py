@@ -63,20 +63,103 @@ class _CEFn(torch.autograd.Function):
         return _nchw(dl), None, None
 
 
+def _targets(targets):
+    t = targets.reshape(-1)
+    if t.dtype != torch.int64 or not t.is_contiguous():
+        t = t.to(torch.int64).contiguous()
+    return t
+
+
+class _CEWeightedFn(torch.autograd.Function):
+    """Class-weighted mean (``reduction`` 0) or sum (1) on dct_ce_weighted_*; ``weight``: the fp32 device buffer or None (all ones)."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, reduction, ignore_index):
+        lp = _pc(logits)
+        t = _targets(targets)
+        out = K.ce_weighted_fwd(lp, t, lp.shape[3], weight, reduction, ignore_index)
+        ctx.save_for_backward(lp, t, out)
+        ctx.weight, ctx.reduction, ctx.ignore_index = weight, reduction, ignore_index
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lp, t, out = ctx.saved_tensors
+        dl = torch.empty_like(lp)
+        g = g.to(torch.float32).contiguous()
+        K.ce_weighted_bwd(lp, t, lp.shape[3], out[1:2], dl, weight=ctx.weight, reduction=ctx.reduction, gscale=g,
+                          ignore_index=ctx.ignore_index)
+        return _nchw(dl), None, None, None, None
+
+
+class _CEMapFn(torch.autograd.Function):
+    """The [B, H, W] map w_t * (logsumexp(x) - x_t) of ``reduce=False`` on dct_ce_map_*."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, ignore_index):
+        lp = _pc(logits)
+        t = _targets(targets)
+        ctx.save_for_backward(lp, t)
+        ctx.weight, ctx.ignore_index = weight, ignore_index
+        return K.ce_map_fwd(lp, t, lp.shape[3], weight, ignore_index).view(lp.shape[:3])
+
+    @staticmethod
+    def backward(ctx, g):
+        lp, t = ctx.saved_tensors
+        dl = torch.empty_like(lp)
+        K.ce_map_bwd(lp, t, lp.shape[3], g.to(torch.float32).contiguous().view(-1), dl, weight=ctx.weight, ignore_index=ctx.ignore_index)
+        return _nchw(dl), None, None, None
+
+
 class CrossEntropyLoss2d(nn.Module):
+    """``nn.NLLLoss(weight, reduce=, size_average=, ignore_index=)`` of the log-softmax, as the reference builds it: the class-weighted
+    mean ``sum w_t l / sum w_t`` (default), the sum (``reduce=True, size_average=False``) or the [B, H, W] map ``w_t l``
+    (``reduce=False``, whatever ``size_average`` is) -- torch's ``F.cross_entropy(weight=, ignore_index=, reduction=)``.
+
+    ``weight`` (None, or C values) stays on the module as passed.  The kernels read an fp32 copy on the device, made once per device
+    on first use (``device_weight``) and never refreshed from ``weight``: nothing is copied from the host per call, and an in-place
+    update of that buffer (``crit.device_weight(dev).copy_(...)``) is what the next call -- and every replay of a captured step --
+    sees.  None or all-ones weights with the mean reduction run the unweighted kernels."""
+
     def __init__(self, weight=None, reduce=True, size_average=True, ignore_index=255):
         super().__init__()
-        if weight is not None and any(float(w) != 1.0 for w in weight):
-            raise NotImplementedError("dct_amd CrossEntropyLoss2d: class weights are not on the co-training path "
-                                      "(train_ACDC_cotraining.py:48 uses weight=None)")
-        if not (reduce and size_average):
-            raise NotImplementedError("dct_amd CrossEntropyLoss2d: only the mean reduction of the reference path")
         self.weight = weight
+        self.reduce, self.size_average = reduce, size_average
+        self.reduction = 'none' if not reduce else ('mean' if size_average else 'sum')
         self.ignore_index = ignore_index
+        self._host_weight = None if weight is None else [float(w) for w in weight]
+        self._unit = self._host_weight is None or all(w == 1.0 for w in self._host_weight)
+        self._device_weights = {}
+
+    def device_weight(self, device, C=None):
+        """The fp32 [C] buffer of the class weights on ``device`` that the kernels read (None when the weights are None or all ones:
+        the kernels then take every weight as 1)."""
+        if self._unit:
+            if C is not None and self._host_weight is not None and len(self._host_weight) != C:
+                raise ValueError(f"dct_amd CrossEntropyLoss2d: {len(self._host_weight)} class weights for logits of {C} classes")
+            return None
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if C is not None and len(self._host_weight) != C:
+            raise ValueError(f"dct_amd CrossEntropyLoss2d: {len(self._host_weight)} class weights for logits of {C} classes")
+        buf = self._device_weights.get(device)
+        if buf is None:
+            buf = self._device_weights[device] = torch.tensor(self._host_weight, dtype=torch.float32, device=device)
+        return buf
 
     def forward(self, outputs, targets):
         assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
-        return _CEFn.apply(outputs, targets, self.ignore_index)
+        if not outputs.is_cuda:
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        w = self.device_weight(outputs.device, outputs.shape[1])
+        if self.reduction == 'none':
+            return _CEMapFn.apply(outputs, targets, w, self.ignore_index)
+        if self.reduction == 'mean' and w is None:
+            return _CEFn.apply(outputs, targets, self.ignore_index)
+        return _CEWeightedFn.apply(outputs, targets, w, K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM, self.ignore_index)
 
 
 class _SoftmaxFn(torch.autograd.Function):

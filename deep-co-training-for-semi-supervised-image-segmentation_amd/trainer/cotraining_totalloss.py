@@ -115,9 +115,9 @@ class ExecutionPlan:
 class _StepContext(object):
     """What one issue of the step carries from its forward passes to its optimizers; dropped when the step returns (the join closure
     holds this step's streams, the pass buffers' owners its tapes)."""
-    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore")
+    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight")
 
-    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None):
+    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None):
         self.sched, self.route = sched, route
         # the gradient exchange as far as it is issued from inside the step (between two graphs it is the replay's business)
         self.sync = grad_sync if any(e in ("model", "buckets") for e in route.exchange) else None
@@ -130,6 +130,7 @@ class _StepContext(object):
         self.g_cot = dict(gscale=lam_dev[0:1], gmul=gs) if lam_dev is not None else dict(gmul=lam[0] * gs)
         self.g_adv = dict(gscale=lam_dev[1:2], gmul=gs) if lam_dev is not None else dict(gmul=lam[1] * gs)
         self.ignore = ignore
+        self.ce_weight = ce_weight          # the supervised criterion's fp32 class weights on the device, or None (all ones)
 
     def on(self, streams, i):
         """Model i's stream of ``streams`` as the current one (no-op without streams, or for the joint backward of the generic step)."""
@@ -288,7 +289,9 @@ class CoTrainer(Trainer):
         fused_criteria = False
         if gpu:
             from ..loss.loss import CrossEntropyLoss2d, JSD_2D
-            fused_criteria = type(self.criterions['sup']) is CrossEntropyLoss2d and type(self.criterions['jsd']) is JSD_2D
+            sup = self.criterions['sup']
+            # (class weights ride the fused kernels; the sum and the per-pixel map go through the module: the generic step)
+            fused_criteria = type(sup) is CrossEntropyLoss2d and sup.reduction == 'mean' and type(self.criterions['jsd']) is JSD_2D
         if self._group_max is None and gpu and all(n.plan_net and n.supports_pass_groups for n in nets):
             from .. import hip_ops as K
             self._group_max = K.group_max()
@@ -430,8 +433,15 @@ class CoTrainer(Trainer):
         """Cross entropy of the labeled logits: loss value + count and the logit gradient into ``dl`` (two launches).  -> (value, NCHW logits)."""
         from .. import hip_ops as K
         from ..loss.loss import _nchw
-        out = K.ce_step(lp, gt.reshape(-1), self.C, dl, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
+        out = self._ce_step(ctx, lp, gt.reshape(-1), dl)
         return out[0], _nchw(lp)
+
+    def _ce_step(self, ctx, lp, t, dl):
+        """The supervised criterion's value + logit gradient: class-weighted when it carries weights (dct_ce_weighted_step), else dct_ce_step."""
+        from .. import hip_ops as K
+        if ctx.ce_weight is not None:
+            return K.ce_weighted_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
+        return K.ce_step(lp, t, self.C, dl, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
 
     def _forward_ce(self, ctx, net, x, gt, B_l=None, **fwd):
         """Forward pass over ``x`` and the cross entropy of its labeled rows (the first ``B_l``; all of them when None).
@@ -473,7 +483,7 @@ class CoTrainer(Trainer):
             t = torch.cat((t, pseudo[t.numel():]))
         # only the sign of the input gradient is used: the (power-of-two) scale keeps it out of half's subnormals
         dl = torch.empty_like(lp)
-        K.ce_step(lp, t, C, dl, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
+        self._ce_step(ctx, lp, t, dl)         # criterions['sup'] (cotraining_totalloss.py:1165, AEGenerator.py:44): the pseudo-labelled tail is weighted too
         gx = net.plan_backward(tape, dl, need_dx=True, need_dw=False)
         x_adv, noise = K.fgsm_step(x.detach().contiguous(), gx.contiguous(), eps)
         return x_adv, noise, lp, tape
@@ -593,7 +603,7 @@ class CoTrainer(Trainer):
         device, as a captured graph needs."""
         nets = [s.torchnet for s in self.segmentators]
         ctx = _StepContext(self._sched, route, self.grad_sync, (float(self.cot_scheduler.value), float(self.adv_scheduler.value)),
-                           lam_dev, self.criterions['sup'].ignore_index)
+                           lam_dev, self.criterions['sup'].ignore_index, self.criterions['sup'].device_weight(self.device, self.C))
         streams = self._streams() if route.model_streams else None
         if route.kind in ("wide", "wide_grouped"):
             return self._run_step_wide(ctx, lab, unl, train_adv, adv_choice, nets)

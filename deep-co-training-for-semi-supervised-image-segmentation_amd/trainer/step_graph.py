@@ -87,6 +87,11 @@ class StepGraphCache(object):
                         opt._m.data_ptr() if getattr(opt, "_m", None) is not None else 0,
                         getattr(net, "external_dropout_masks", None) is None,
                         bool(getattr(net, "record_dropout_masks", False))))
+        # the supervised criterion's launch arguments: another criterion (ignore_index, weight buffer) is another capture; the weights
+        # themselves are read on the device, so changing them in place is not
+        sup = tr.criterions['sup']
+        w = sup.device_weight(tr.device, tr.C)
+        sig.append((sup.ignore_index, w.data_ptr() if w is not None else 0))
         return tuple(sig)
 
     def _lam(self) -> torch.Tensor:

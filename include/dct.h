@@ -263,6 +263,35 @@ int dct_ce_bwd(const float* logits, const int64_t* targets, int64_t pixels, int 
 int dct_ce_step(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index, float* out2,
                 const float* gscale, float gmul, float* dlogits, int accumulate, void* workspace, size_t workspace_bytes,
                 dct_stream stream);
+/* Class-weighted cross entropy with the reductions of torch's F.cross_entropy(weight=, ignore_index=, reduction=) (the weight / reduce /
+ * size_average arguments of loss/loss.py:12-25).  weight: C fp32 values in device memory, nullable = all ones; the kernels pick w_t by an
+ * unrolled select, never by weight[t].  Per pixel i:
+ *   l_i = logsumexp(x_i) - x_i[t_i];   w_i = weight[t_i] (1 when weight is NULL);
+ *   t_i == ignore_index: w_i = 0 and l_i = 0;  a target outside [0, C) that is not ignore_index is treated as ignored too (torch raises
+ *   there; nothing is indexed with it).
+ * reduction 0 (mean): out2[0] = sum w_i l_i / sum w_i, out2[1] = sum w_i (the denominator); NaN when sum w_i == 0, as in torch (the gradients
+ *   are then unspecified).      reduction 1 (sum): out2[0] = sum w_i l_i, out2[1] = sum w_i; the gradient's denominator is 1.
+ * Gradient: dlogits[i][c] (=|+=) (g * w_i) * (p_c - [t_i == c]) with g = gscale[0] * gmul / denom formed in this order (gscale nullable = 1;
+ *   denom = out2 + 1 of the forward call under mean, not read under sum): all-ones weights under mean give dct_ce_bwd's result bit for bit.
+ *   Ignored pixels get exactly 0 (exactly the old value under accumulate).
+ * dct_ce_weighted_step: fwd + bwd in two launches like dct_ce_step (the backward kernel folds the forward kernel's block partials itself);
+ *   out2 and dlogits are bit for bit those of dct_ce_weighted_fwd followed by dct_ce_weighted_bwd.
+ * map (reduce=False): map[i] = w_i l_i;  backward: dlogits[i][c] (=|+=) (gmul * dmap[i] * w_i) * (p_c - [t_i == c]).
+ * DCT_ERR_BAD_ARG: a null logits / targets / out pointer, pixels < 1, a reduction other than 0 or 1; DCT_ERR_UNSUPPORTED: C outside 2..8;
+ * DCT_ERR_WORKSPACE: less than dct_loss_workspace_bytes of workspace. */
+int dct_ce_weighted_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                        const float* weight /*nullable*/, int reduction, float* out2, void* workspace, size_t workspace_bytes,
+                        dct_stream stream);
+int dct_ce_weighted_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                        const float* weight, int reduction, const float* denom /*out2 + 1*/, const float* gscale, float gmul,
+                        float* dlogits, int accumulate, dct_stream stream);
+int dct_ce_weighted_step(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                         const float* weight, int reduction, float* out2, const float* gscale, float gmul, float* dlogits,
+                         int accumulate, void* workspace, size_t workspace_bytes, dct_stream stream);
+int dct_ce_map_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                   const float* weight /*nullable*/, float* map, dct_stream stream);
+int dct_ce_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                   const float* weight, const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream);
 int dct_softmax_fwd(const float* logits, float* probs, int64_t pixels, int C, dct_stream stream);
 /* dlogits (=|+=) p * (dprobs - sum_c dprobs*p) */
 int dct_softmax_bwd(const float* probs, const float* dprobs, float* dlogits, int64_t pixels, int C,
