@@ -258,6 +258,232 @@ __global__ __launch_bounds__(256) void ce_map_bwd_kernel(const float* logits, co
   ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, gmul, dmap, dl, acc);
 }
 
+// ---- soft Dice and CE + Dice (the rule: include/dct.h) ---------------------------------------------------------------------------------
+// Grid: x walks one image's pixels, y is the image (dice_kernel's choice), so a block's partial row is one image's and a group's sums
+// depend on that group's pixels alone.  A row is NS = 3 C + 2 floats: {sum w l, sum w, then I, S, Y per class}.  A sum is folded in one
+// fixed order wherever it is formed: over all rows by a block (fold_rows: thread tid takes rows tid, tid + 256, ... in order, then the wave
+// shuffle, then the four wave sums), over one image's rows by a wave (wave_fold_rows).
+constexpr int kDiceFwdBlocks = 512;      // rows every backward block folds: kept small (the fold is L2 traffic per backward block)
+constexpr int kDiceBwdBlocks = 1024;
+struct DiceRule { int mask, per_image; float smooth, ce_coef, dice_coef, inv_gk; };
+
+template <int N> __device__ __forceinline__ void block_partial_n(const float a[N], float* row) {
+  __shared__ float sm[4 * N];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < N; ++s) {
+    const float v = wave_sum(a[s]);
+    if (lane == 0) sm[w * N + s] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) row[threadIdx.x] = sm[threadIdx.x] + sm[N + threadIdx.x] + sm[2 * N + threadIdx.x] + sm[3 * N + threadIdx.x];
+}
+// out[s] = the sum over rows [first, first + count) of column OFF + s, in every thread of the block (sm: 4 N floats of LDS)
+template <int NS, int OFF, int N>
+__device__ __forceinline__ void fold_rows(const float* partial, int first, int count, float* sm, float out[N]) {
+  float a[N];
+#pragma unroll
+  for (int s = 0; s < N; ++s) a[s] = 0.f;
+  for (int i = threadIdx.x; i < count; i += 256) {
+    const float* row = partial + (long long)(first + i) * NS + OFF;
+#pragma unroll
+    for (int s = 0; s < N; ++s) a[s] += row[s];
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();                       // (the previous fold's readers are done with sm)
+#pragma unroll
+  for (int s = 0; s < N; ++s) {
+    const float v = wave_sum(a[s]);
+    if (lane == 0) sm[w * N + s] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < N; ++s) out[s] = sm[s] + sm[N + s] + sm[2 * N + s] + sm[3 * N + s];
+}
+// The same sums by ONE wave, in every lane: lane l takes rows l, l + 64, ... in order, then the wave shuffle.  This is the order of a group's
+// sums under per_image (a group is one image's rows, at most kDiceFwdBlocks / B of them): no LDS and no barrier, so the four waves of
+// ce_dice_finish fold four groups at a time and a backward block's waves each fold their image's rows for themselves.
+template <int NS, int OFF, int N>
+__device__ __forceinline__ void wave_fold_rows(const float* partial, int first, int count, float out[N]) {
+  float a[N];
+#pragma unroll
+  for (int s = 0; s < N; ++s) a[s] = 0.f;
+  for (int i = threadIdx.x & 63; i < count; i += 64) {
+    const float* row = partial + (long long)(first + i) * NS + OFF;
+#pragma unroll
+    for (int s = 0; s < N; ++s) a[s] += row[s];
+  }
+#pragma unroll
+  for (int s = 0; s < N; ++s) out[s] = wave_sum(a[s]);
+}
+// {sum w l, sum w} over every row and group g's {I, S, Y} per class: the one group of the whole batch folds all columns of all rows at once
+template <int C>
+__device__ __forceinline__ void ce_dice_fold(const float* partial, int B, int fbx, int per_image, int g, float* sm, float ce2[2], float d[3 * C]) {
+  constexpr int NS = 3 * C + 2;
+  if (!per_image) {
+    float a[NS];
+    fold_rows<NS, 0, NS>(partial, 0, B * fbx, sm, a);
+    ce2[0] = a[0]; ce2[1] = a[1];
+#pragma unroll
+    for (int s = 0; s < 3 * C; ++s) d[s] = a[2 + s];
+  } else {
+    fold_rows<NS, 0, 2>(partial, 0, B * fbx, sm, ce2);
+    wave_fold_rows<NS, 2, 3 * C>(partial, g * fbx, fbx, d);
+  }
+}
+// D = (2 I + smooth) / (S + Y + smooth), alpha = 2 / (S + Y + smooth), beta = D / (S + Y + smooth); an empty denominator: D = 1, no gradient
+__device__ __forceinline__ void dice_terms(float I, float S, float Y, float smooth, float& D, float& alpha, float& beta) {
+#pragma clang fp contract(off)    // one rounding per operation wherever this is inlined: _step's numbers are _fwd's and _bwd's
+  const float den = (S + Y) + smooth;
+  const float num = 2.f * I + smooth;
+  const bool empty = den == 0.f;
+  D = empty ? 1.f : num / den;
+  alpha = empty ? 0.f : 2.f / den;
+  beta = empty ? 0.f : D / den;
+}
+// q_c = qb[c] - [t == c] qa[c] with qa = m_c alpha_c / (G K), qb = m_c beta_c / (G K), from a group's folded sums d = {I, S, Y} per class
+template <int C> __device__ __forceinline__ void dice_coeffs(const float* d, DiceRule r, float qa[C], float qb[C]) {
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float D, alpha, beta;
+    dice_terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r.smooth, D, alpha, beta);
+    const float m = ((r.mask >> c) & 1) ? r.inv_gk : 0.f;
+    qa[c] = m * alpha; qb[c] = m * beta;
+  }
+}
+// group g's rows of dice_gc [G][C] and sums [G][C][3] from its folded sums (one thread); -> the sum of D over the classes of the mask
+template <int C> __device__ __forceinline__ float dice_group_out(const float d[3 * C], int g, DiceRule r, float* dice_gc, float* sums) {
+  float dsum = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float D, alpha, beta;
+    dice_terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r.smooth, D, alpha, beta);
+    dice_gc[g * C + c] = D;
+    sums[(g * C + c) * 3 + 0] = d[3 * c]; sums[(g * C + c) * 3 + 1] = d[3 * c + 1]; sums[(g * C + c) * 3 + 2] = d[3 * c + 2];
+    if ((r.mask >> c) & 1) dsum += D;
+  }
+  return dsum;
+}
+// out4, dice_gc and sums from the partial rows; the whole block calls it.  Under per_image wave w takes groups w, w + 4, ... and the four
+// waves' sums of D are added in order.
+template <int C>
+__device__ __forceinline__ void ce_dice_finish(const float* partial, int B, int fbx, DiceRule r, float* out4, float* dice_gc, float* sums, float* sm) {
+  constexpr int NS = 3 * C + 2;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float ce2[2], d[3 * C], dsum = 0.f;
+  if (!r.per_image) {
+    ce_dice_fold<C>(partial, B, fbx, 0, 0, sm, ce2, d);
+    if (threadIdx.x == 0) dsum = dice_group_out<C>(d, 0, r, dice_gc, sums);
+  } else {
+    fold_rows<NS, 0, 2>(partial, 0, B * fbx, sm, ce2);
+    for (int g = w; g < B; g += 4) {
+      wave_fold_rows<NS, 2, 3 * C>(partial, g * fbx, fbx, d);
+      if (lane == 0) dsum += dice_group_out<C>(d, g, r, dice_gc, sums);
+    }
+    __syncthreads();                     // (fold_rows' readers are done with sm)
+    if (lane == 0) sm[w] = dsum;
+    __syncthreads();
+    dsum = sm[0] + sm[1] + sm[2] + sm[3];
+  }
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    const float ce = ce2[0] / ce2[1];
+    const float dice = 1.f - dsum * r.inv_gk;
+    float total = 0.f;
+    if (r.ce_coef != 0.f) total = r.ce_coef * ce;            // a coefficient of exactly 0 removes its term (a NaN ce with it)
+    if (r.dice_coef != 0.f) total = total + r.dice_coef * dice;
+    out4[0] = total; out4[1] = ce; out4[2] = ce2[1]; out4[3] = dice;
+  }
+}
+// dl (=|+=) g (ce_coef (w_t / den)(p - y) + dice_coef p (q - sum_k p_k q_k)) over the block's pixels of image blockIdx.y
+template <int C>
+__device__ __forceinline__ void ce_dice_grad_pixels(const float* logits, const long long* tgt, long long PPI, int ignore, const float wr[C],
+                                                    float g, float den, DiceRule r, const float qa[C], const float qb[C], float* dl, int acc) {
+  const bool ce_on = r.ce_coef != 0.f, dice_on = r.dice_coef != 0.f;
+  const float gce = ce_on ? g * r.ce_coef / den : 0.f;
+  const float gd = g * r.dice_coef;
+  const long long base = (long long)blockIdx.y * PPI;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < PPI; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[base + pix];
+    const bool on = counted<C>(t, ignore);
+    float x[C], p[C], q[C], d[C];
+    load_px<C>(logits, base + pix, x);
+    softmax_px<C>(x, p);
+    const float gw = gce * weight_of<C>(t, wr);
+    float dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) { q[c] = qb[c] - (t == c ? qa[c] : 0.f); dot += p[c] * q[c]; }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float a = ce_on ? gw * (p[c] - (t == c ? 1.f : 0.f)) : 0.f;
+      const float b = dice_on ? gd * (p[c] * (q[c] - dot)) : 0.f;
+      d[c] = on ? a + b : 0.f;
+    }
+    store_px<C>(dl, base + pix, d, acc);
+  }
+}
+// one softmax per counted pixel feeds both terms: ce_w_fwd_kernel's {w l, w} and {p_t, p_c, [t == c]} per class
+template <int C>
+__global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
+                                                           const float* weight, float* partial) {
+  constexpr int NS = 3 * C + 2;
+  float wr[C];
+  load_weights<C>(weight, wr);
+  float a[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) a[s] = 0.f;
+  const long long base = (long long)blockIdx.y * PPI;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < PPI; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[base + pix];
+    if (!counted<C>(t, ignore)) continue;
+    float x[C], p[C];
+    load_px<C>(logits, base + pix, x);
+    const float lse = softmax_px<C>(x, p);
+    float xt = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) xt = (t == c) ? x[c] : xt;
+    const float w = weight_of<C>(t, wr);
+    a[0] += w * (lse - xt); a[1] += w;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      a[2 + 3 * c] += (t == c) ? p[c] : 0.f;
+      a[3 + 3 * c] += p[c];
+      a[4 + 3 * c] += (t == c) ? 1.f : 0.f;
+    }
+  }
+  block_partial_n<NS>(a, partial + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * NS);
+}
+template <int C>
+__global__ __launch_bounds__(256) void ce_dice_fin_kernel(const float* partial, int B, int fbx, DiceRule r, float* out4, float* dice_gc, float* sums) {
+  __shared__ float sm[4 * (3 * C + 2)];
+  ce_dice_finish<C>(partial, B, fbx, r, out4, dice_gc, sums, sm);
+}
+template <int C>
+__global__ __launch_bounds__(256) void ce_dice_bwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore, const float* weight,
+                                                           DiceRule r, const float* out4, const float* sums, const float* gscale, float gmul,
+                                                           float* dl, int acc) {
+  float wr[C], qa[C], qb[C];
+  load_weights<C>(weight, wr);
+  dice_coeffs<C>(sums + (r.per_image ? (long long)blockIdx.y * C * 3 : 0), r, qa, qb);
+  ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, out4[2], r, qa, qb, dl, acc);
+}
+// ce_bwd_fin_kernel's pattern: every block folds the forward rows it needs (all of them for sum w; its own group's for the Dice sums)
+// in ce_dice_fin_kernel's order, block (0, 0) also writes what that kernel writes, then the gradient
+template <int C>
+__global__ __launch_bounds__(256) void ce_dice_bwd_fin_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
+                                                               const float* weight, DiceRule r, const float* partial, int fbx, float* out4,
+                                                               float* dice_gc, float* sums, const float* gscale, float gmul, float* dl, int acc) {
+  __shared__ float sm[4 * (3 * C + 2)];
+  const int B = gridDim.y;
+  float ce2[2], d[3 * C];
+  ce_dice_fold<C>(partial, B, fbx, r.per_image, blockIdx.y, sm, ce2, d);
+  if (blockIdx.x == 0 && blockIdx.y == 0) ce_dice_finish<C>(partial, B, fbx, r, out4, dice_gc, sums, sm);
+  float wr[C], qa[C], qb[C];
+  load_weights<C>(weight, wr);
+  dice_coeffs<C>(d, r, qa, qb);
+  ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, ce2[1], r, qa, qb, dl, acc);
+}
+
 // ---- softmax / entropy (module API) -------------------------------------------------------------
 template <int C>
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* logits, float* probs, long long P) {
@@ -752,6 +978,72 @@ extern "C" int dct_ce_map_bwd(const float* logits, const int64_t* targets, int64
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_map_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, dmap, gmul,
                             dlogits, accumulate));
+  return dct_check_launch();
+}
+// blocks along x of one image: at most cap / B (at least one), so that B of them stay within cap rows (B rows when B > cap)
+static inline unsigned dice_grid_x(long long ppi, int B, int cap) {
+  long long b = (ppi + 255) / 256;
+  const long long c = cap / B < 1 ? 1 : cap / B;
+  return (unsigned)(b < c ? b : c);
+}
+static inline size_t dice_ws_bytes(int B, int C_) {
+  return (size_t)(B > kDiceFwdBlocks ? B : kDiceFwdBlocks) * (size_t)(3 * C_ + 2) * sizeof(float);
+}
+// the checks the three calls share (pointers apart) and the rule as the kernels take it
+static int dice_rule(int B, int64_t ppi, int C_, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, DiceRule& r) {
+  if (B < 1 || ppi < 1 || !(smooth >= 0.f) || __builtin_isinf(smooth) || (per_image != 0 && per_image != 1)) return DCT_ERR_BAD_ARG;
+  if (C_ < 2 || C_ > 8 || B > 65535) return DCT_ERR_UNSUPPORTED;
+  const int mask = class_mask & ((1 << C_) - 1);
+  if (!mask) return DCT_ERR_BAD_ARG;
+  const int G = per_image ? B : 1, K = __builtin_popcount((unsigned)mask);
+  r = DiceRule{mask, per_image, smooth, ce_coef, dice_coef, 1.f / (float)((long long)G * K)};
+  return DCT_OK;
+}
+extern "C" size_t dct_ce_dice_workspace_bytes(int B, int C_, int /*per_image*/) {
+  return dice_ws_bytes(B < 1 ? 1 : B, C_ < 2 ? 2 : (C_ > 8 ? 8 : C_));
+}
+extern "C" int dct_ce_dice_fwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
+                               const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, float* out4,
+                               float* dice_gc, float* sums, void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !out4 || !dice_gc || !sums) return DCT_ERR_BAD_ARG;
+  DiceRule r;
+  if (const int e = dice_rule(B, pixels_per_image, C_, class_mask, smooth, per_image, ce_coef, dice_coef, r)) return e;
+  if (!workspace || workspace_bytes < dice_ws_bytes(B, C_)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned fbx = dice_grid_x(pixels_per_image, B, kDiceFwdBlocks);
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fwd_kernel<C>, dim3(fbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
+                            ignore_index, weight, (float*)workspace));
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fin_kernel<C>, dim3(1), dim3(256), 0, st, (const float*)workspace, B, (int)fbx, r, out4, dice_gc, sums));
+  return dct_check_launch();
+}
+extern "C" int dct_ce_dice_bwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
+                               const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef,
+                               const float* out4, const float* sums, const float* gscale, float gmul, float* dlogits, int accumulate,
+                               dct_stream stream) {
+  if (!logits || !targets || !out4 || !sums || !dlogits) return DCT_ERR_BAD_ARG;
+  DiceRule r;
+  if (const int e = dice_rule(B, pixels_per_image, C_, class_mask, smooth, per_image, ce_coef, dice_coef, r)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned bbx = dice_grid_x(pixels_per_image, B, kDiceBwdBlocks);
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_bwd_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
+                            ignore_index, weight, r, out4, sums, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+extern "C" int dct_ce_dice_step(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
+                                const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, float* out4,
+                                float* dice_gc, float* sums, const float* gscale, float gmul, float* dlogits, int accumulate,
+                                void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !out4 || !dice_gc || !sums || !dlogits) return DCT_ERR_BAD_ARG;
+  DiceRule r;
+  if (const int e = dice_rule(B, pixels_per_image, C_, class_mask, smooth, per_image, ce_coef, dice_coef, r)) return e;
+  if (!workspace || workspace_bytes < dice_ws_bytes(B, C_)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned fbx = dice_grid_x(pixels_per_image, B, kDiceFwdBlocks);       // dct_ce_dice_fwd's grid: the same partial rows
+  const unsigned bbx = dice_grid_x(pixels_per_image, B, kDiceBwdBlocks);       // dct_ce_dice_bwd's grid
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fwd_kernel<C>, dim3(fbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
+                            ignore_index, weight, (float*)workspace));
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_bwd_fin_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
+                            ignore_index, weight, r, (const float*)workspace, (int)fbx, out4, dice_gc, sums, gscale, gmul, dlogits, accumulate));
   return dct_check_launch();
 }
 extern "C" int dct_softmax_fwd(const float* logits, float* probs, int64_t pixels, int C_, dct_stream stream) {

@@ -527,6 +527,57 @@ def ce_map_bwd(logits_pc, targets, C_, dmap, dlogits, weight=None, gmul=1.0, ign
     return dlogits
 
 
+def _ce_dice_args(logits_bpc, C_, class_mask, per_image):
+    """(B, pixels per image, mask, G) of fp32 logits [B, ..., C] (dense; the first dimension counts the images)."""
+    B = logits_bpc.shape[0]
+    return B, logits_bpc.numel() // (B * C_), (1 << C_) - 1 if class_mask is None else int(class_mask), B if per_image else 1
+
+
+def _ce_dice_ws(B, C_, per_image, device):
+    return torch.empty(_lib.load().dct_ce_dice_workspace_bytes(B, C_, int(per_image)), dtype=torch.uint8, device=device)
+
+
+def ce_dice_fwd(logits_bpc, targets, C_, weight=None, class_mask=None, smooth=1e-5, per_image=False, ce_coef=1.0, dice_coef=1.0,
+                ignore_index=255):
+    """Soft Dice / CE + Dice (dct_ce_dice_fwd; the rule: include/dct.h).  ``logits_bpc``: fp32 [B, ..., C] dense; ``targets``: int64, one per
+    pixel; ``class_mask``: bit c = class c is in the Dice mean (None: all).  Returns device tensors ``out4`` = (total, ce, sum w, dice),
+    ``dice_gc`` [G, C] and ``sums`` [G, C, 3] (G = B under ``per_image``, else 1)."""
+    B, ppi, mask, G = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
+    dev = logits_bpc.device
+    out4 = torch.empty(4, dtype=torch.float32, device=dev)
+    dice_gc = torch.empty(G, C_, dtype=torch.float32, device=dev)
+    sums = torch.empty(G, C_, 3, dtype=torch.float32, device=dev)
+    ws = _ce_dice_ws(B, C_, per_image, dev)
+    call("dct_ce_dice_fwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), int(per_image),
+         float(ce_coef), float(dice_coef), ptr(out4), ptr(dice_gc), ptr(sums), ptr(ws), ws.numel(), stream())
+    return out4, dice_gc, sums
+
+
+def ce_dice_bwd(logits_bpc, targets, C_, out4, sums, dlogits, weight=None, class_mask=None, smooth=1e-5, per_image=False, ce_coef=1.0,
+                dice_coef=1.0, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
+    """``out4`` and ``sums``: those of ce_dice_fwd under the same arguments."""
+    B, ppi, mask, _ = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
+    call("dct_ce_dice_bwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), int(per_image),
+         float(ce_coef), float(dice_coef), ptr(out4), ptr(sums), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), stream())
+    return dlogits
+
+
+def ce_dice_step(logits_bpc, targets, C_, dlogits, weight=None, class_mask=None, smooth=1e-5, per_image=False, ce_coef=1.0, dice_coef=1.0,
+                 gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
+    """ce_dice_fwd + ce_dice_bwd of the same logits in two launches (dct_ce_dice_step; bit for bit the two calls).  Returns
+    (out4, dice_gc, sums); ``dlogits`` is written (added to)."""
+    B, ppi, mask, G = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
+    dev = logits_bpc.device
+    out4 = torch.empty(4, dtype=torch.float32, device=dev)
+    dice_gc = torch.empty(G, C_, dtype=torch.float32, device=dev)
+    sums = torch.empty(G, C_, 3, dtype=torch.float32, device=dev)
+    ws = _ce_dice_ws(B, C_, per_image, dev)
+    call("dct_ce_dice_step", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), int(per_image),
+         float(ce_coef), float(dice_coef), ptr(out4), ptr(dice_gc), ptr(sums), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate),
+         ptr(ws), ws.numel(), stream())
+    return out4, dice_gc, sums
+
+
 def softmax_fwd(logits_pc, C_):
     probs = torch.empty_like(logits_pc)
     call("dct_softmax_fwd", ptr(logits_pc), ptr(probs), logits_pc.numel() // C_, C_, stream())

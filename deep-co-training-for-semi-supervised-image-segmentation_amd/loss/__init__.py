@@ -1,10 +1,12 @@
 """Loss registry (reference: generalframework/loss/__init__.py:6-16)."""
-from .loss import CrossEntropyLoss2d, JSD_2D, KL_Divergence_2D, Entropy_2D, softmax_channels  # noqa: F401
+from .loss import CrossEntropyLoss2d, CrossEntropyDiceLoss2d, DiceLoss, JSD_2D, KL_Divergence_2D, Entropy_2D, softmax_channels  # noqa: F401
 from . import loss as _loss_mod
 
 __all__ = ['get_loss_fn']
 
 LOSS = {'cross_entropy': CrossEntropyLoss2d,
+        'dice': DiceLoss,
+        'ce_dice': CrossEntropyDiceLoss2d,
         'jsd': JSD_2D}
 
 

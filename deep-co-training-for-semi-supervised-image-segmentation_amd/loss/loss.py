@@ -111,7 +111,38 @@ class _CEMapFn(torch.autograd.Function):
         return _nchw(dl), None, None, None
 
 
-class CrossEntropyLoss2d(nn.Module):
+class _ClassWeighted(nn.Module):
+    """The class weights of a criterion: kept on the module as passed, read by the kernels from an fp32 copy on the device that is made
+    once per device on first use (``device_weight``) and never refreshed from ``weight``."""
+
+    def _set_weight(self, weight):
+        self.weight = weight
+        self._host_weight = None if weight is None else [float(w) for w in weight]
+        self._unit = self._host_weight is None or all(w == 1.0 for w in self._host_weight)
+        self._device_weights = {}
+
+    def device_weight(self, device, C=None):
+        """The fp32 [C] buffer of the class weights on ``device`` that the kernels read (None when the weights are None or all ones:
+        the kernels then take every weight as 1)."""
+        name = type(self).__name__
+        if self._unit:
+            if C is not None and self._host_weight is not None and len(self._host_weight) != C:
+                raise ValueError(f"dct_amd {name}: {len(self._host_weight)} class weights for logits of {C} classes")
+            return None
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if C is not None and len(self._host_weight) != C:
+            raise ValueError(f"dct_amd {name}: {len(self._host_weight)} class weights for logits of {C} classes")
+        buf = self._device_weights.get(device)
+        if buf is None:
+            buf = self._device_weights[device] = torch.tensor(self._host_weight, dtype=torch.float32, device=device)
+        return buf
+
+
+class CrossEntropyLoss2d(_ClassWeighted):
     """``nn.NLLLoss(weight, reduce=, size_average=, ignore_index=)`` of the log-softmax, as the reference builds it: the class-weighted
     mean ``sum w_t l / sum w_t`` (default), the sum (``reduce=True, size_average=False``) or the [B, H, W] map ``w_t l``
     (``reduce=False``, whatever ``size_average`` is) -- torch's ``F.cross_entropy(weight=, ignore_index=, reduction=)``.
@@ -123,32 +154,10 @@ class CrossEntropyLoss2d(nn.Module):
 
     def __init__(self, weight=None, reduce=True, size_average=True, ignore_index=255):
         super().__init__()
-        self.weight = weight
+        self._set_weight(weight)
         self.reduce, self.size_average = reduce, size_average
         self.reduction = 'none' if not reduce else ('mean' if size_average else 'sum')
         self.ignore_index = ignore_index
-        self._host_weight = None if weight is None else [float(w) for w in weight]
-        self._unit = self._host_weight is None or all(w == 1.0 for w in self._host_weight)
-        self._device_weights = {}
-
-    def device_weight(self, device, C=None):
-        """The fp32 [C] buffer of the class weights on ``device`` that the kernels read (None when the weights are None or all ones:
-        the kernels then take every weight as 1)."""
-        if self._unit:
-            if C is not None and self._host_weight is not None and len(self._host_weight) != C:
-                raise ValueError(f"dct_amd CrossEntropyLoss2d: {len(self._host_weight)} class weights for logits of {C} classes")
-            return None
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        if C is not None and len(self._host_weight) != C:
-            raise ValueError(f"dct_amd CrossEntropyLoss2d: {len(self._host_weight)} class weights for logits of {C} classes")
-        buf = self._device_weights.get(device)
-        if buf is None:
-            buf = self._device_weights[device] = torch.tensor(self._host_weight, dtype=torch.float32, device=device)
-        return buf
 
     def forward(self, outputs, targets):
         assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
@@ -160,6 +169,77 @@ class CrossEntropyLoss2d(nn.Module):
         if self.reduction == 'mean' and w is None:
             return _CEFn.apply(outputs, targets, self.ignore_index)
         return _CEWeightedFn.apply(outputs, targets, w, K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM, self.ignore_index)
+
+
+class _CEDiceFn(torch.autograd.Function):
+    """``ce_coef`` ce + ``dice_coef`` dice on dct_ce_dice_*; ``rule``: the launch arguments of ``CrossEntropyDiceLoss2d.launch_args``.
+    Returns the total and, without a gradient, the [G, C] table of D_gc."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, rule, ignore_index):
+        lp = _pc(logits)
+        t = _targets(targets)
+        out4, dice_gc, sums = K.ce_dice_fwd(lp, t, lp.shape[3], weight, ignore_index=ignore_index, **rule)
+        ctx.save_for_backward(lp, t, out4, sums)
+        ctx.weight, ctx.rule, ctx.ignore_index = weight, rule, ignore_index
+        ctx.mark_non_differentiable(dice_gc)
+        return out4[0], dice_gc
+
+    @staticmethod
+    def backward(ctx, g, _):
+        lp, t, out4, sums = ctx.saved_tensors
+        dl = torch.empty_like(lp)
+        g = g.to(torch.float32).contiguous()
+        K.ce_dice_bwd(lp, t, lp.shape[3], out4, sums, dl, weight=ctx.weight, gscale=g, ignore_index=ctx.ignore_index, **ctx.rule)
+        return _nchw(dl), None, None, None, None
+
+
+class CrossEntropyDiceLoss2d(_ClassWeighted):
+    """``ce_coef`` * class-weighted mean cross entropy + ``dice_coef`` * soft Dice loss of the softmax (the rule: include/dct.h,
+    dct_ce_dice_*), in one forward and one backward launch pair.  ``classes``: the class indices of the Dice mean (None: all;
+    ``range(1, C)``: foreground only); ``per_image``: one Dice per image and class instead of one per class over the batch; ``weight``
+    and ``ignore_index`` as on ``CrossEntropyLoss2d``.  After a call ``last_dice`` is the [G, C] device tensor of D_gc of every class
+    (nothing synchronises).  A coefficient of exactly 0 removes its term."""
+
+    def __init__(self, weight=None, ce_coef=1.0, dice_coef=1.0, classes=None, smooth=1e-5, per_image=False, ignore_index=255):
+        super().__init__()
+        self._set_weight(weight)
+        self.ce_coef, self.dice_coef = float(ce_coef), float(dice_coef)
+        self.classes = None if classes is None else sorted({int(c) for c in classes})
+        if self.classes is not None and not self.classes:
+            raise ValueError(f"dct_amd {type(self).__name__}: classes is empty")
+        if self.classes is not None and self.classes[0] < 0:
+            raise ValueError(f"dct_amd {type(self).__name__}: class {self.classes[0]} is negative")
+        self.smooth = float(smooth)
+        if not (0.0 <= self.smooth < float('inf')):
+            raise ValueError(f"dct_amd {type(self).__name__}: smooth must be finite and >= 0, got {smooth}")
+        self.per_image = bool(per_image)
+        self.ignore_index = ignore_index
+        self.last_dice = None
+
+    def launch_args(self, C):
+        """The keyword arguments of hip_ops.ce_dice_* for logits of ``C`` classes (checks ``classes`` against C)."""
+        if self.classes is not None and self.classes[-1] >= C:
+            raise ValueError(f"dct_amd {type(self).__name__}: class {self.classes[-1]} outside [0, {C})")
+        mask = (1 << C) - 1 if self.classes is None else sum(1 << c for c in self.classes)
+        return dict(class_mask=mask, smooth=self.smooth, per_image=self.per_image, ce_coef=self.ce_coef, dice_coef=self.dice_coef)
+
+    def forward(self, outputs, targets):
+        assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
+        if not outputs.is_cuda:
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        rule = self.launch_args(outputs.shape[1])
+        w = self.device_weight(outputs.device, outputs.shape[1])
+        total, self.last_dice = _CEDiceFn.apply(outputs, targets, w, rule, self.ignore_index)
+        return total
+
+
+class DiceLoss(CrossEntropyDiceLoss2d):
+    """Soft Dice loss alone: ``1 - mean_{g, c in classes} (2 I + smooth) / (S + Y + smooth)`` of the softmax (``CrossEntropyDiceLoss2d``
+    with the cross-entropy term removed)."""
+
+    def __init__(self, classes=None, smooth=1e-5, per_image=False, ignore_index=255):
+        super().__init__(None, 0.0, 1.0, classes, smooth, per_image, ignore_index)
 
 
 class _SoftmaxFn(torch.autograd.Function):

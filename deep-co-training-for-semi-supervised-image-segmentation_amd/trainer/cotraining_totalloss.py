@@ -115,9 +115,9 @@ class ExecutionPlan:
 class _StepContext(object):
     """What one issue of the step carries from its forward passes to its optimizers; dropped when the step returns (the join closure
     holds this step's streams, the pass buffers' owners its tapes)."""
-    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight")
+    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice")
 
-    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None):
+    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None):
         self.sched, self.route = sched, route
         # the gradient exchange as far as it is issued from inside the step (between two graphs it is the replay's business)
         self.sync = grad_sync if any(e in ("model", "buckets") for e in route.exchange) else None
@@ -131,6 +131,7 @@ class _StepContext(object):
         self.g_adv = dict(gscale=lam_dev[1:2], gmul=gs) if lam_dev is not None else dict(gmul=lam[1] * gs)
         self.ignore = ignore
         self.ce_weight = ce_weight          # the supervised criterion's fp32 class weights on the device, or None (all ones)
+        self.ce_dice = ce_dice              # a Dice / CE + Dice criterion's launch arguments (CrossEntropyDiceLoss2d.launch_args), or None
 
     def on(self, streams, i):
         """Model i's stream of ``streams`` as the current one (no-op without streams, or for the joint backward of the generic step)."""
@@ -288,10 +289,11 @@ class CoTrainer(Trainer):
         gpu = self.device.type == 'cuda'
         fused_criteria = False
         if gpu:
-            from ..loss.loss import CrossEntropyLoss2d, JSD_2D
+            from ..loss.loss import CrossEntropyDiceLoss2d, CrossEntropyLoss2d, DiceLoss, JSD_2D
             sup = self.criterions['sup']
-            # (class weights ride the fused kernels; the sum and the per-pixel map go through the module: the generic step)
-            fused_criteria = type(sup) is CrossEntropyLoss2d and sup.reduction == 'mean' and type(self.criterions['jsd']) is JSD_2D
+            # (class weights, Dice and CE + Dice ride the fused kernels; the sum and the per-pixel map go through the module: the generic step)
+            fused_sup = (type(sup) is CrossEntropyLoss2d and sup.reduction == 'mean') or type(sup) in (CrossEntropyDiceLoss2d, DiceLoss)
+            fused_criteria = fused_sup and type(self.criterions['jsd']) is JSD_2D
         if self._group_max is None and gpu and all(n.plan_net and n.supports_pass_groups for n in nets):
             from .. import hip_ops as K
             self._group_max = K.group_max()
@@ -437,8 +439,11 @@ class CoTrainer(Trainer):
         return out[0], _nchw(lp)
 
     def _ce_step(self, ctx, lp, t, dl):
-        """The supervised criterion's value + logit gradient: class-weighted when it carries weights (dct_ce_weighted_step), else dct_ce_step."""
+        """The supervised criterion's value + logit gradient: Dice / CE + Dice (dct_ce_dice_step over the images of ``lp``: [B, H, W, C]),
+        class-weighted when it carries weights (dct_ce_weighted_step), else dct_ce_step."""
         from .. import hip_ops as K
+        if ctx.ce_dice is not None:
+            return K.ce_dice_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore, **ctx.ce_dice)[0]
         if ctx.ce_weight is not None:
             return K.ce_weighted_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
         return K.ce_step(lp, t, self.C, dl, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
@@ -602,8 +607,10 @@ class CoTrainer(Trainer):
         ``lam_dev`` (float32[2] device tensor holding lambda_cot, lambda_adv): the loss weights are then read on the
         device, as a captured graph needs."""
         nets = [s.torchnet for s in self.segmentators]
+        sup = self.criterions['sup']
         ctx = _StepContext(self._sched, route, self.grad_sync, (float(self.cot_scheduler.value), float(self.adv_scheduler.value)),
-                           lam_dev, self.criterions['sup'].ignore_index, self.criterions['sup'].device_weight(self.device, self.C))
+                           lam_dev, sup.ignore_index, sup.device_weight(self.device, self.C),
+                           sup.launch_args(self.C) if hasattr(sup, "launch_args") else None)
         streams = self._streams() if route.model_streams else None
         if route.kind in ("wide", "wide_grouped"):
             return self._run_step_wide(ctx, lab, unl, train_adv, adv_choice, nets)

@@ -87,11 +87,14 @@ class StepGraphCache(object):
                         opt._m.data_ptr() if getattr(opt, "_m", None) is not None else 0,
                         getattr(net, "external_dropout_masks", None) is None,
                         bool(getattr(net, "record_dropout_masks", False))))
-        # the supervised criterion's launch arguments: another criterion (ignore_index, weight buffer) is another capture; the weights
-        # themselves are read on the device, so changing them in place is not
+        # the supervised criterion's launch arguments: another criterion (ignore_index, weight buffer; for CE + Dice its module type, the
+        # two coefficients, mask, smooth and per_image) is another capture; the weights themselves are read on the device, so changing
+        # them in place is not
         sup = tr.criterions['sup']
         w = sup.device_weight(tr.device, tr.C)
-        sig.append((sup.ignore_index, w.data_ptr() if w is not None else 0))
+        rule = sup.launch_args(tr.C) if hasattr(sup, "launch_args") else None
+        sig.append((sup.ignore_index, w.data_ptr() if w is not None else 0, type(sup).__name__,
+                    tuple(sorted(rule.items())) if rule is not None else None))
         return tuple(sig)
 
     def _lam(self) -> torch.Tensor:

@@ -292,6 +292,46 @@ int dct_ce_map_fwd(const float* logits, const int64_t* targets, int64_t pixels, 
                    const float* weight /*nullable*/, float* map, dct_stream stream);
 int dct_ce_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
                    const float* weight, const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream);
+/* Soft Dice and CE + Dice as one supervised criterion (the reference's loss/dice.py, SURVEY 2 row 3, on logits).  logits: fp32 NHWC
+ * [B][pixels_per_image][C]; targets: int64 [B * pixels_per_image]; weight: the C fp32 class weights of the CE term on the device, nullable
+ * = all ones, exactly as in dct_ce_weighted_*; class_mask: bit c set = class c takes part in the Dice mean, K = the number of set bits
+ * below C; smooth >= 0; per_image 0: one group over the whole batch (G = 1), 1: one group per image (G = B); ce_coef, dice_coef: host floats.
+ * A pixel i is counted as in the weighted CE: t_i != ignore_index && 0 <= t_i < C.  Uncounted pixels take part in no sum and get a gradient
+ * of exactly 0 (exactly the old value under accumulate).  With p = softmax(x_i) and y the one-hot of t_i, per group g and class c over the
+ * counted pixels of g:
+ *   I = sum p_c y_c,  S = sum p_c,  Y = sum y_c,  D_gc = (2 I + smooth) / (S + Y + smooth);
+ *   a denominator of 0 (smooth = 0 and no counted pixel): D_gc = 1, and the class contributes no gradient.
+ *   dice  = 1 - (1 / (G K)) sum_g sum_{c in mask} D_gc
+ *   ce    = sum w_i l_i / sum w_i, the rule of dct_ce_weighted_fwd under reduction 0 (NaN when sum w_i == 0)
+ *   total = ce_coef ce + dice_coef dice; a coefficient that is exactly 0 removes its term from the total and from the gradient (a NaN ce
+ *           then does not reach total).
+ * dct_ce_dice_fwd writes out4 = {total, ce, sum w_i, dice}, dice_gc [G][C] = D_gc of every class, masked in or not (for logging), and
+ *   sums [G][C][3] = {I, S, Y}, which the backward call reads.
+ * Gradient, with g = gscale[0] * gmul (gscale nullable = 1):
+ *   dlogits[i][c] (=|+=) g (ce_coef (w_i / sum w)(p_c - y_c) + dice_coef p_c (q_c - sum_k p_k q_k)),
+ *   q_c = -(m_c / (G K)) (alpha_gc y_c - beta_gc),  alpha = 2 / (S + Y + smooth),  beta = (2 I + smooth) / (S + Y + smooth)^2,
+ *   m_c = 1 for the classes of the mask, else 0.
+ * dct_ce_dice_bwd reads out4 (its sum w_i) and sums of the forward call.  dct_ce_dice_step: fwd + bwd in two launches like dct_ce_step
+ *   (the backward kernel folds the forward kernel's block partials itself); out4, dice_gc, sums and dlogits are bit for bit those of
+ *   dct_ce_dice_fwd followed by dct_ce_dice_bwd.  All sums are folded in one fixed order without float atomics: bit-identical from run to
+ *   run, and under per_image a group's numbers depend on that image alone (a permutation of the images permutes the rows of dice_gc).
+ * Workspace: dct_ce_dice_workspace_bytes(B, C, per_image) (more than dct_loss_workspace_bytes: 3 C + 2 sums per block); no clearing needed.
+ * DCT_ERR_BAD_ARG: a null logits / targets / out4 / dice_gc / sums / dlogits pointer, pixels_per_image < 1, B < 1, smooth < 0 or not finite,
+ *   a class_mask with no bit below C, per_image outside {0, 1}; DCT_ERR_UNSUPPORTED: C outside 2..8, B > 65535; DCT_ERR_WORKSPACE: too
+ *   little workspace.
+ * Out of scope: the squared-denominator (V-Net) form, generalized (volume-weighted) Dice, and probabilities as input. */
+size_t dct_ce_dice_workspace_bytes(int B, int C, int per_image);
+int dct_ce_dice_fwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C, int ignore_index,
+                    const float* weight /*nullable*/, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef,
+                    float* out4, float* dice_gc, float* sums, void* workspace, size_t workspace_bytes, dct_stream stream);
+int dct_ce_dice_bwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C, int ignore_index,
+                    const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef,
+                    const float* out4, const float* sums, const float* gscale, float gmul, float* dlogits, int accumulate,
+                    dct_stream stream);
+int dct_ce_dice_step(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C, int ignore_index,
+                     const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, float* out4,
+                     float* dice_gc, float* sums, const float* gscale, float gmul, float* dlogits, int accumulate, void* workspace,
+                     size_t workspace_bytes, dct_stream stream);
 int dct_softmax_fwd(const float* logits, float* probs, int64_t pixels, int C, dct_stream stream);
 /* dlogits (=|+=) p * (dprobs - sum_c dprobs*p) */
 int dct_softmax_bwd(const float* probs, const float* dprobs, float* dlogits, int64_t pixels, int C,
