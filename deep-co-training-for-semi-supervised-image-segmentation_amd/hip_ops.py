@@ -733,6 +733,32 @@ def hausdorff(logits_bhwc, gt_bhw, method3d=False, spacing=(1., 1., 1.)):
     return hd2
 
 
+def largest_component(logits_bhwc, method3d=False, full=False, classes=None, background=0, want_cls=False):
+    """logits [B, H, W, C] fp32 dense -> (onehot fp32 [B, H, W, C], cls int64 [B, H, W] or None, stats int32 [rows, C, 3]): the
+    argmax map with only the largest connected component of every class in ``classes`` kept (None: every class but ``background``),
+    the rest of those classes moved to ``background``; rows = 1 for the batch as a volume, else B; ``full``: 8- / 26- instead of
+    4- / 6-connectivity; stats = {components, size of the largest, pixels} per class before cleaning (include/dct.h)."""
+    ptr(logits_bhwc)                    # (refuses a CPU tensor before anything is sized or copied)
+    B, H, W, C_ = logits_bhwc.shape
+    background = int(background)
+    classes = [c for c in range(C_) if c != background] if classes is None else [int(c) for c in classes]
+    if C_ <= 8 and (not 0 <= background < C_ or any(not 0 <= c < C_ for c in classes) or background in classes):
+        raise ValueError(f"largest_component: classes {classes} must lie in [0, {C_}) and may not hold the background class {background}")
+    mask = sum(1 << c for c in set(classes)) if C_ <= 8 else 0
+    # the kernels read 16 bytes at a time: a dense view that starts inside its storage (a slice of a larger batch) gets a copy of its own
+    if logits_bhwc.data_ptr() % 16:
+        logits_bhwc = logits_bhwc.clone()
+    dev = logits_bhwc.device
+    need = _lib.load().dct_components_workspace_bytes(B, H, W, C_, int(bool(method3d)))
+    ws = _ws(need, dev)
+    onehot = torch.empty(B, H, W, C_, dtype=torch.float32, device=dev)
+    cls = torch.empty(B, H, W, dtype=torch.int64, device=dev) if want_cls else None
+    stats = torch.empty(1 if method3d else B, C_, 3, dtype=torch.int32, device=dev)
+    call("dct_largest_component", ptr(logits_bhwc), B, H, W, C_, int(bool(method3d)), int(bool(full)), mask, background, ptr(onehot),
+         ptr(cls), ptr(stats), ptr(ws), ws.numel(), stream())
+    return onehot, cls, stats
+
+
 def confusion_counts(logits: List[torch.Tensor], gt: Optional[torch.Tensor] = None):
     """logits: S fp32 tensors [B, pix, C] (or [B, H, W, C]), the predictions of S raters on one batch; gt [B, pix] (or [B, H, W])
     int64 or None -> int32 [B, P, C, C]: the confusion matrix of every pair of raters per image, gt being the last rater, pairs

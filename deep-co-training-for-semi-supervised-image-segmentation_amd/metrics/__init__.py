@@ -3,7 +3,9 @@ averagemeter.py:3-48), kept on the device: ``add`` launches one counting kernel 
 synchronises; ``value`` is where the (tiny) results are read.  ``HausdorffMeter`` is the second column of the reference's
 result tables (Summary.py:70-252), which takes it from an external package: here ``dct_hausdorff`` (include/dct.h).
 ``AgreementMeter`` is the third: Cohen's kappa between every pair of raters (the models, an ensemble, gt), and the IoU of the
-reference's ``IoU`` / ``ConfusionMatrix`` meters, from the pairwise confusion matrices of ``dct_confusion_counts``."""
+reference's ``IoU`` / ``ConfusionMatrix`` meters, from the pairwise confusion matrices of ``dct_confusion_counts``.
+``keep_largest_component`` is the cleaning ACDC-style pipelines apply in front of all of them (``dct_largest_component``), and
+``ComponentMeter`` reports what it removed."""
 from __future__ import annotations
 
 import math
@@ -13,7 +15,8 @@ import torch
 
 from .. import hip_ops as K
 
-__all__ = ["DiceMeter", "HausdorffMeter", "AgreementMeter", "AverageValueMeter", "pair_index", "kappa_of", "iou_of"]
+__all__ = ["DiceMeter", "HausdorffMeter", "AgreementMeter", "ComponentMeter", "AverageValueMeter", "keep_largest_component", "pair_index",
+           "kappa_of", "iou_of"]
 
 
 class DiceMeter(object):
@@ -327,6 +330,76 @@ class AgreementMeter(object):
         """Mean (and std) over the rows of a row's mean kappa over the pairs that contain gt (all pairs without gt)."""
         (mean, std), _ = self.value()
         return {'mKappa': mean, 'mVars': std}
+
+
+def keep_largest_component(pred: torch.Tensor, method='2d', classes=None, background=0, full_connectivity=False, return_stats=False):
+    """pred [B,C,H,W] (logits or probabilities, any float dtype, any layout) -> the one-hot float32 map of its argmax with only the
+    largest connected component of every class in ``classes`` kept (None: all but ``background``) and the rest of those classes moved
+    to ``background`` (``dct_largest_component``, include/dct.h): per slice ('2d') or with the batch as a volume ('3d'); 4- / 6-
+    connectivity, 8- / 26- with ``full_connectivity``.  The result is a logical [B,C,H,W] view of an NHWC buffer, so the meters'
+    ``permute`` costs nothing.  ``return_stats``: also the int32 [rows, C, 3] tensor ``ComponentMeter.add`` takes."""
+    assert method in ('2d', '3d')
+    if not pred.is_cuda:
+        raise RuntimeError("dct_amd keep_largest_component labels on the HIP device only (no CPU fallback)")
+    lp = pred.detach().permute(0, 2, 3, 1)
+    if lp.dtype != torch.float32 or not lp.is_contiguous():
+        lp = lp.to(torch.float32).contiguous()
+    onehot, _, stats = K.largest_component(lp, method == '3d', full_connectivity, classes, background)
+    out = onehot.permute(0, 3, 1, 2)
+    return (out, stats) if return_stats else out
+
+
+class ComponentMeter(object):
+    """What ``keep_largest_component`` found, from the stats rows of ``dct_largest_component`` ([rows, C, 3] = components, size of the
+    largest, pixels per class before cleaning; '2d': a row per slice, '3d': a row per batch): per class the mean and std over the rows
+    where the class is present of the number of components and of the removed share (pixels - largest) / pixels.  A class that is never
+    present gives NaN.  ``add`` keeps the device tensor and waits for nothing; ``value`` makes one host copy."""
+
+    def __init__(self, method='2d', C=4) -> None:
+        assert method in ('2d', '3d')
+        self.method = method
+        self.C = C
+        self.reset()
+
+    def reset(self):
+        self.statLog = []
+        self._cache = None
+
+    def add(self, stats: torch.Tensor):
+        if stats.dim() != 3 or tuple(stats.shape[1:]) != (self.C, 3) or stats.is_floating_point():
+            raise RuntimeError(f"dct_amd ComponentMeter takes integer stats [rows, {self.C}, 3], got {tuple(stats.shape)} {stats.dtype}")
+        self.statLog.append(stats.detach())
+        self._cache = None
+
+    def value(self, **kwargs):
+        """((mean components [C], std), (mean removed share [C], std)) as float64 tensors."""
+        if self._cache is None:
+            if self.statLog:
+                rows = torch.cat(self.statLog).cpu().numpy().astype(np.float64)
+            else:
+                rows = np.zeros((0, self.C, 3))
+            present = rows[:, :, 2] > 0
+            with np.errstate(divide='ignore', invalid='ignore'):
+                comps = np.where(present, rows[:, :, 0], np.nan)
+                removed = np.where(present, (rows[:, :, 2] - rows[:, :, 1]) / rows[:, :, 2], np.nan)
+            cm, cs, n = _nan_moments(comps)
+            rm, rs, _ = _nan_moments(removed)
+            self._cache = ((torch.from_numpy(cm), torch.from_numpy(cs)), (torch.from_numpy(rm), torch.from_numpy(rs)), torch.from_numpy(n))
+        return self._cache[0], self._cache[1]
+
+    @property
+    def defined(self):
+        """Number of rows in which each class is present."""
+        self.value()
+        return self._cache[2]
+
+    def detailed_summary(self) -> dict:
+        (cm, _), (rm, _) = self.value()
+        d = {f'CC{j}': float(cm[j]) for j in range(self.C)}
+        d.update({f'removed{j}': float(rm[j]) for j in range(self.C)})
+        return d
+
+    summary = detailed_summary
 
 
 class AverageValueMeter(object):

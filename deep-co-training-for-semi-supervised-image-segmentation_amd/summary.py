@@ -10,8 +10,9 @@ medpy's ``metric.binary.hd`` rule as include/dct.h states it (``dct_hausdorff``)
 matrices that ``dct_confusion_counts`` leaves.
 
 Predictions come from the HIP networks; voting, the Dice counting (``dct_dice_counts``), the distance transform behind the
-Hausdorff distance (``dct_hausdorff``) and the confusion matrices behind kappa and IoU (``dct_confusion_counts``) run on the
-device."""
+Hausdorff distance (``dct_hausdorff``), the confusion matrices behind kappa and IoU (``dct_confusion_counts``) and, on request,
+the largest-connected-component cleaning of every prediction in front of a second set of tables (``dct_largest_component``) run on
+the device."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -19,7 +20,7 @@ from typing import Dict, List, Optional
 import torch
 from torch import Tensor
 
-from .metrics import AgreementMeter, DiceMeter, HausdorffMeter
+from .metrics import AgreementMeter, ComponentMeter, DiceMeter, HausdorffMeter, keep_largest_component
 from .models import Segmentator
 
 
@@ -67,7 +68,8 @@ class Ensembleway(object):
 @torch.no_grad()
 def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method: str = 'soft',
               report_axises: Optional[List[int]] = None, hausdorff: bool = False, spacing=None,
-              kappa: bool = False, iou: bool = False, kappa_classes: Optional[List[int]] = None) -> Dict[str, dict]:
+              kappa: bool = False, iou: bool = False, kappa_classes: Optional[List[int]] = None,
+              largest_component: Optional[str] = None, lcc_classes: Optional[List[int]] = None, lcc_full: bool = False) -> Dict[str, dict]:
     """Per-model and ensemble 2-D / 3-D Dice over a validation loader (batches ``[(img, gt), meta, names]``): tables ``'2d'`` and
     ``'3d'`` with keys ``DSC{j}``.  ``hausdorff=True`` adds the tables ``'hd_2d'`` and ``'hd_3d'`` with keys ``HD{j}``: mean (and
     for the ensemble the std) of the Hausdorff distance over the slices / patient batches where class j is in both the
@@ -77,7 +79,15 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
     Cohen's kappa between every pair of the raters model 0 .. (``S{i}``), the ensemble vote (``ensemble``) and ``gt`` -- pairs such
     as ``S0_S1``, ``S0_ensemble``, ``ensemble_gt`` -- over the slices / patient batches where it is defined; at most 7 models.
     ``kappa_classes`` restricts it to the pixels whose second rater lies in that class set.  ``iou=True`` adds ``'iou_2d'`` and
-    ``'iou_3d'`` in the layout of the Dice tables with keys ``IoU{j}``."""
+    ``'iou_3d'`` in the layout of the Dice tables with keys ``IoU{j}``.
+
+    ``largest_component='2d'`` / ``'3d'`` also scores every prediction and the ensemble vote with only the largest connected component
+    of each class in ``lcc_classes`` kept (default: every class but 0; the rest goes to class 0), found per slice / per loader batch as
+    a volume, with 4- / 6-connectivity (8- / 26- with ``lcc_full``): every table that is switched on gets a twin named ``..._lcc``
+    (``'2d_lcc'``, ``'hd_3d_lcc'``, ``'kappa_2d_lcc'``, ...), and ``'components'`` = ``{model_i | ensemble: {'CC{j}': mean number of
+    components of class j, 'removed{j}': mean share of its pixels that the cleaning removed}}`` over the slices / batches that hold the
+    class.  The tables without the suffix are what they are without the argument."""
+    assert largest_component in (None, '2d', '3d'), largest_component
     device = torch.device(device)
     C = models[0].arch_params['num_classes']
     axes = report_axises if report_axises is not None else list(range(C))
@@ -85,25 +95,26 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
     for m in models:
         m.to(device)
         m.eval()
-    d2 = [DiceMeter(method='2d', report_axises=axes, C=C) for _ in models]
-    d3 = [DiceMeter(method='3d', report_axises=axes, C=C) for _ in models]
-    e2, e3 = DiceMeter(method='2d', report_axises=axes, C=C), DiceMeter(method='3d', report_axises=axes, C=C)
-    groups = [(d2, e2), (d3, e3)]
-    if hausdorff:
-        sp = tuple(spacing) if spacing is not None else (1., 1., 1.)
-        for method in ('2d', '3d'):
-            groups.append(([HausdorffMeter(method=method, report_axises=axes, C=C, spacing=sp) for _ in models],
-                           HausdorffMeter(method=method, report_axises=axes, C=C, spacing=sp)))
-    agree = []
+    names = [f"S{i}" for i in range(len(models))] + ["ensemble"]
     if kappa or iou:
         assert len(models) <= 7, "kappa / iou tables: at most 7 models beside the ensemble (dct_confusion_counts takes 8 predictions)"
-        names = [f"S{i}" for i in range(len(models))] + ["ensemble"]
-        agree = [AgreementMeter(method=method, C=C, n_models=len(names), with_gt=True, considered_classes=kappa_classes,
-                                rater_names=names) for method in ('2d', '3d')]
-    for (img, gt), _, _ in val_dataloader:
-        img, gt = img.to(device), gt.to(device)
-        preds = [m.predict(img, logit=False) for m in models]
-        v = ens(preds)
+    sp = tuple(spacing) if spacing is not None else (1., 1., 1.)
+
+    def meter_set():
+        groups = [([DiceMeter(method=method, report_axises=axes, C=C) for _ in models], DiceMeter(method=method, report_axises=axes, C=C))
+                  for method in ('2d', '3d')]
+        if hausdorff:
+            for method in ('2d', '3d'):
+                groups.append(([HausdorffMeter(method=method, report_axises=axes, C=C, spacing=sp) for _ in models],
+                               HausdorffMeter(method=method, report_axises=axes, C=C, spacing=sp)))
+        agree = []
+        if kappa or iou:
+            agree = [AgreementMeter(method=method, C=C, n_models=len(names), with_gt=True, considered_classes=kappa_classes,
+                                    rater_names=names) for method in ('2d', '3d')]
+        return groups, agree
+
+    def feed(meters, preds, v, gt):
+        groups, agree = meters
         for a in agree:
             a.add(preds + [v], gt)
         for per_model, ensemble in groups:
@@ -111,26 +122,51 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
                 per_model[j].add(p, gt)
             ensemble.add(v, gt)
 
+    raw = meter_set()
+    cleaned = meter_set() if largest_component else None
+    comp = [ComponentMeter(method=largest_component, C=C) for _ in names] if largest_component else []
+    for (img, gt), _, _ in val_dataloader:
+        img, gt = img.to(device), gt.to(device)
+        preds = [m.predict(img, logit=False) for m in models]
+        v = ens(preds)
+        feed(raw, preds, v, gt)
+        if cleaned is not None:
+            kept = []
+            for meter, p in zip(comp, preds + [v]):
+                onehot, stats = keep_largest_component(p, method=largest_component, classes=lcc_classes, background=0,
+                                                       full_connectivity=lcc_full, return_stats=True)
+                meter.add(stats)
+                kept.append(onehot)
+            feed(cleaned, kept[:-1], kept[-1], gt)
+
     def table(meter, key):
         (_, _), (means, stds) = meter.value()
         return {f'{key}{j}': float(means[j]) for j in range(C)}, {f'{key}{j}': float(stds[j]) for j in range(C)}
 
     out: Dict[str, dict] = {}
-    for name, key, meters in zip(("2d", "3d", "hd_2d", "hd_3d"), ("DSC", "DSC", "HD", "HD"), groups):
-        res = {f'model_{i}': table(m, key)[0] for i, m in enumerate(meters[0])}
-        res['ensemble'] = table(meters[1], key)[0]
-        res['ensemble_std'] = table(meters[1], key)[1]
-        out[name] = res
-    for a in agree:
-        if kappa:
-            mean, std, n = a.kappa()
-            out[f'kappa_{a.method}'] = {'mean': {k: float(mean[p]) for p, k in enumerate(a.pairs)},
-                                        'std': {k: float(std[p]) for p, k in enumerate(a.pairs)},
-                                        'defined': {k: int(n[p]) for p, k in enumerate(a.pairs)}}
-        if iou:
-            mean, std = a.iou()
-            res = {f'model_{i}': {f'IoU{j}': float(mean[i][j]) for j in range(C)} for i in range(len(models))}
-            res['ensemble'] = {f'IoU{j}': float(mean[-1][j]) for j in range(C)}
-            res['ensemble_std'] = {f'IoU{j}': float(std[-1][j]) for j in range(C)}
-            out[f'iou_{a.method}'] = res
+
+    def tables(meters, suffix):
+        groups, agree = meters
+        for name, key, pair in zip(("2d", "3d", "hd_2d", "hd_3d"), ("DSC", "DSC", "HD", "HD"), groups):
+            res = {f'model_{i}': table(m, key)[0] for i, m in enumerate(pair[0])}
+            res['ensemble'] = table(pair[1], key)[0]
+            res['ensemble_std'] = table(pair[1], key)[1]
+            out[name + suffix] = res
+        for a in agree:
+            if kappa:
+                mean, std, n = a.kappa()
+                out[f'kappa_{a.method}{suffix}'] = {'mean': {k: float(mean[p]) for p, k in enumerate(a.pairs)},
+                                                    'std': {k: float(std[p]) for p, k in enumerate(a.pairs)},
+                                                    'defined': {k: int(n[p]) for p, k in enumerate(a.pairs)}}
+            if iou:
+                mean, std = a.iou()
+                res = {f'model_{i}': {f'IoU{j}': float(mean[i][j]) for j in range(C)} for i in range(len(models))}
+                res['ensemble'] = {f'IoU{j}': float(mean[-1][j]) for j in range(C)}
+                res['ensemble_std'] = {f'IoU{j}': float(std[-1][j]) for j in range(C)}
+                out[f'iou_{a.method}{suffix}'] = res
+
+    tables(raw, "")
+    if cleaned is not None:
+        tables(cleaned, "_lcc")
+        out['components'] = {(f'model_{i}' if i < len(models) else 'ensemble'): m.detailed_summary() for i, m in enumerate(comp)}
     return out

@@ -33,7 +33,7 @@ from torch import Tensor, nn
 
 from .. import ModelMode
 from .. import scheduler
-from ..metrics import AgreementMeter, AverageValueMeter, DiceMeter, HausdorffMeter
+from ..metrics import AgreementMeter, AverageValueMeter, DiceMeter, HausdorffMeter, keep_largest_component
 from ..models import Segmentator
 from ..utils import iterator_, map_, dict_merge, tqdm_
 from ..utils.AEGenerator import FSGMGenerator
@@ -164,8 +164,13 @@ class CoTrainer(Trainer):
                  grad_sync=None,
                  val_hausdorff: bool = False,
                  val_spacing=(1., 1., 1.),
-                 val_kappa: bool = False) -> None:
+                 val_kappa: bool = False,
+                 val_largest_component: bool = False) -> None:
         self.max_epoch = max_epoch
+        # opt-in: _eval_loop also scores every model's prediction with only the largest connected component of each class of `axises`
+        # kept (per batch as a volume, the rest to class 0) and uploads the 3-D Dice as 'val_lcc' (and, with val_hausdorff, the
+        # Hausdorff distance as 'val_hd_lcc'): the number an ACDC-style post-processing would report
+        self.val_largest_component = bool(val_largest_component)
         # opt-in: _eval_loop also measures Cohen's kappa between every pair of views and of each view with gt (3-D, restricted to the
         # pixels whose second rater lies in `axises`) and uploads it as 'val_kappa': the agreement that the JSD term drives
         self.val_kappa = bool(val_kappa)
@@ -1143,6 +1148,10 @@ class CoTrainer(Trainer):
                     for _ in range(S)] if self.val_hausdorff else []
         kappaMeter = AgreementMeter(method='3d', C=self.C, n_models=S, with_gt=True,
                                     considered_classes=list(self.axises)) if self.val_kappa else None
+        lcc = self.val_largest_component
+        lccDiceMeters = [DiceMeter(report_axises=self.axises, method='3d', C=self.C) for _ in range(S)] if lcc else []
+        lccHdMeters = [HausdorffMeter(report_axises=self.axises, method='3d', C=self.C, spacing=self.val_spacing)
+                       for _ in range(S)] if lcc and self.val_hausdorff else []
         val_iter = tqdm_(val_dataloader) if self.use_tqdm else val_dataloader
         for batch_num, [(img, gt), _, path] in enumerate(val_iter):
             img, gt = img.to(self.device), gt.to(self.device)
@@ -1156,6 +1165,11 @@ class CoTrainer(Trainer):
                 vallossMeters[i].add(loss[i].detach())
                 if hdMeters:
                     hdMeters[i].add(preds[i], gt)
+                if lcc:
+                    kept = keep_largest_component(preds[i], method='3d', classes=[a for a in self.axises if a != 0], background=0)
+                    lccDiceMeters[i].add(kept, gt)
+                    if lccHdMeters:
+                        lccHdMeters[i].add(kept, gt)
                 if save:
                     self._save_images(preds[i].max(1)[1], path, 'eval', epoch, str(i))
         dsc_dict = self._dsc_dict(batchdiceMeters)
@@ -1163,6 +1177,11 @@ class CoTrainer(Trainer):
         if hdMeters:
             vals = [m.value() for m in hdMeters]
             self.upload_dicts('val_hd', {f"S{i}": {f"HD{n}": float(vals[i][1][0][n]) for n in self.axises} for i in range(S)}, epoch)
+        if lcc:
+            self.upload_dicts('val_lcc', self._dsc_dict(lccDiceMeters), epoch)
+        if lccHdMeters:
+            vals = [m.value() for m in lccHdMeters]
+            self.upload_dicts('val_hd_lcc', {f"S{i}": {f"HD{n}": float(vals[i][1][0][n]) for n in self.axises} for i in range(S)}, epoch)
         if kappaMeter is not None:
             self.upload_dicts('val_kappa', {pair: {'kappa': k} for pair, k in kappaMeter.detailed_summary().items()}, epoch)
         nice_dict = self._report_dict(batchdiceMeters)

@@ -552,6 +552,35 @@ int dct_hausdorff(const float* logits /*[B][H][W][C]*/, const int64_t* gt /*[B][
                   int B, int H, int W, int C, int method3d, float sz, float sy, float sx,
                   float* hd2 /*[rows][C]*/, void* workspace, size_t workspace_bytes, dct_stream stream);
 
+/* ---- Largest connected component on device (the cleaning every ACDC-style pipeline applies before it scores: Hausdorff distance
+ * is a maximum, and one stray island far from the organ sets it) -------------------
+ * Row: one slice (2-D), or the whole batch taken as a volume with z = batch index (method3d) -- the convention of dct_hausdorff.
+ * Class of a pixel: the argmax of its logits, first maximum, exactly as dct_argmax / dct_dice_counts / dct_hausdorff.
+ * Connected: two pixels of the same class in the same row that are neighbours.  full = 0: face neighbours (4 in a plane, 6 in a
+ *   volume); full = 1: all neighbours that share a face, an edge or a corner (8 / 26).  Nothing outside the array is a neighbour.  (A
+ *   volume's 18-neighbourhood is not offered.)
+ * Component: a maximal connected set of pixels of one class.
+ * Kept: for every row and every class c with bit c set in class_mask, the component with the most pixels; ties go to the component
+ *   whose first pixel in raster order (z, y, x) comes first -- what np.argmax over the sizes of scipy.ndimage.label's labels gives,
+ *   scipy numbering components in that order.  Every pixel of class c outside the kept component becomes class `background`; pixels
+ *   of classes outside class_mask are left alone.  `background` itself may not be in class_mask.
+ * Outputs: onehot[B][H][W][C] (nullable) = 1.0 at the cleaned class, 0.0 elsewhere (the form every meter takes: for them only the
+ *   argmax matters); cls[B][H][W] (nullable) = the cleaned class map; stats[rows][C][3] (nullable, rows = method3d ? 1 : B) =
+ *   {components of class c before cleaning, size of the largest, pixels of class c before cleaning}, for every class, in class_mask
+ *   or not; 0, 0, 0 for an absent class.
+ * Union-find over pixels with 32-bit labels (csrc/components.hip); integer sums, maxima and minima only: exact, and bit-identical
+ * from run to run.  Everything runs on the caller's stream, nothing waits for the device; the workspace needs no clearing by the
+ * caller.  logits, onehot and workspace 16-byte aligned, cls 8-byte, stats 4-byte.
+ * DCT_ERR_BAD_ARG: a null logits or workspace, onehot and cls both null, a size < 1, full not 0 or 1, background outside [0, C),
+ * class_mask with a bit at background or at C and above, a misaligned pointer; DCT_ERR_UNSUPPORTED: C > 8, a row of 2^31 pixels or
+ * more (labels are 32-bit pixel indices), B >= 2^27; DCT_ERR_WORKSPACE: workspace too small.  dct_components_workspace_bytes returns 0
+ * for a shape dct_largest_component refuses. */
+size_t dct_components_workspace_bytes(int B, int H, int W, int C, int method3d);
+int dct_largest_component(const float* logits /*[B][H][W][C]*/, int B, int H, int W, int C, int method3d, int full,
+                          uint32_t class_mask, int background,
+                          float* onehot /*[B][H][W][C], nullable*/, int64_t* cls /*[B][H][W], nullable*/,
+                          int32_t* stats /*[rows][C][3], nullable*/, void* workspace, size_t workspace_bytes, dct_stream stream);
+
 /* ---- Agreement between raters on device: pairwise confusion matrices (the kappa table of Summary.py:70-252, which takes
  * cohen_kappa_score from scikit-learn; the same counts give the reference's ConfusionMatrix and IoU meters) -------------------
  * Raters: the S predictions are raters 0..S-1; the class of a pixel is the argmax of its logits, first maximum, exactly as
