@@ -415,16 +415,17 @@ template <typename T> __device__ __forceinline__ void ld8(const View& v, long lo
 }
 
 // ---- MFMA form of the small-channel convolution (bf16 / f16 compute modes) -----------------------
-// The VALU kernel above gives one thread a whole reduction (taps x Cin multiply-adds in sequence: 288 for a 3x3 on 32 channels)
-// and a stage-3 tensor (8 x 25 x 25 pixels) only ~80 blocks: 50 us per launch at 1.7 TFLOP/s, latency-bound (tools/
-// bench_enet_layers.py).  Where the contraction is MFMA-shaped -- Cin a multiple of 8 and taps x Cin a multiple of 16, i.e.
-// every convolution of stages 1-3 -- a wave instead owns 32 output pixels x all output channels and walks K = taps x Cin in
-// steps of 16 on v_mfma_f32_32x32x16_{bf16,f16}: lane (r, h) loads the 8 consecutive input channels [c0 + 8h, +8) of ITS pixel
-// at the tap's offset straight from HBM/L2 (NHWC: one 16- or 32-byte load; the producer's BatchNorm + activation is applied on
-// load as before, out-of-image taps are zeros), which IS its A fragment; the B fragment is 8 consecutive K of weight row
-// o = 32 j + r (one 32-byte load where the weights are K-major for this role, eight coalesced scalar loads otherwise).  No
-// LDS, no barrier.  The operands are rounded to the compute dtype (mixed precision, fp32 accumulate); fp32 mode keeps the
-// VALU kernel.  D[pixel][channel]: a lane holds one output channel of 16 pixels, so 32 lanes store 128 contiguous bytes.
+// The VALU kernel above gives one thread a whole reduction (taps x Cin multiply-adds in sequence: 288 for a 3x3 on 32
+// channels) and a stage-3 tensor (8 x 25 x 25 pixels) only ~80 blocks: 50 us per launch at 1.7 TFLOP/s, latency-bound (tools/
+// bench_enet_layers.py).  Where the contraction is MFMA-shaped -- at least 16 input channels in whole groups of 16 (the host
+// check of enet_conv_impl), i.e. every convolution of stages 1-3 -- a wave instead owns 32 output pixels x all output channels
+// and walks K = taps x Cin in steps of 16 on v_mfma_f32_32x32x16_{bf16,f16}: lane (r, h) loads the 8 consecutive input
+// channels [c0 + 8h, +8) of ITS pixel at the tap's offset straight from HBM/L2 (NHWC: one 16- or 32-byte load; the producer's
+// BatchNorm + activation is applied on load as before, out-of-image taps are zeros), which IS its A fragment; the B fragment
+// is 8 consecutive K of weight row o = 32 j + r (one 32-byte load where the weights are K-major for this role, eight coalesced
+// scalar loads otherwise).  No LDS, no barrier.  The operands are rounded to the compute dtype (mixed precision, fp32
+// accumulate); fp32 mode keeps the VALU kernel.  D[pixel][channel]: a lane holds one output channel of 16 pixels, so 32 lanes
+// store 128 contiguous bytes.
 template <typename T> struct LowMfma;
 template <> struct LowMfma<bf16_t> {
   typedef bf16x8 frag;
@@ -1425,6 +1426,8 @@ static int enet_conv_impl(const dct_view* x, const float* w, const float* bias, 
     if (nt == 1) ENET_T(dtype, (enet_launch<MconvK<T, 1>>(DCT_PROF_OTHER, dim3(gridm), dim3(64 * MC_W), 0, st0, p)));
     else if (nt == 2) ENET_T(dtype, (enet_launch<MconvK<T, 2>>(DCT_PROF_OTHER, dim3(gridm), dim3(64 * MC_W), 0, st0, p)));
     else if constexpr (MC_W <= 4) ENET_T(dtype, (enet_launch<MconvK<T, 4>>(DCT_PROF_OTHER, dim3(gridm), dim3(64 * MC_W), 0, st0, p)));
+    DCT_PLAN_NOTE("enet mconv %s NT %d: %d groups, grid %u, wvec %d, stats rows %d", p.bwd_in ? "bwd-in" : (p.transposed ? "gather" : "direct"), nt,
+                  ngroups, gridm, p.wvec, p.stats ? (p.bn_bwd ? 2 : 1) : 0);
     return dct_check_launch();
   }
   if (bin) return DCT_ERR_UNSUPPORTED;        // (the VALU kernel has no de-normalise-on-load form: the caller materialises draw)
@@ -1435,6 +1438,7 @@ static int enet_conv_impl(const dct_view* x, const float* w, const float* bias, 
   hipStream_t st = (hipStream_t)stream;
   p.ngroups = 0;
   ENET_T(dtype, enet_launch<ConvK<T>>(DCT_PROF_OTHER, dim3(grid), dim3(256), lds, st, p));
+  DCT_PLAN_NOTE("enet conv valu G %d: grid %u, lds %zu", Gp, grid, lds);
   return dct_check_launch();
 }
 
@@ -1714,6 +1718,7 @@ extern "C" int dct_enet_wgrad(const dct_view* a, const dct_enet_tf* tfa, const d
     ENET_T(dtype, enet_launch<MwgradK<T>>(DCT_PROF_OTHER, dim3((unsigned)(nsl * mtiles * ntiles)), dim3(64), 0, st, p));
     const WRedP wr = {(const float*)workspace, dw, E, (int)nsl};
     enet_launch<WgradRedK>(DCT_PROF_OTHER, dim3(div_up(E, 16)), dim3(256), 0, st, wr);
+    DCT_PLAN_NOTE("enet mwgrad %d x %d tiles: pps %lld, %lld slices", mtiles, ntiles, pps, nsl);
     return dct_check_launch();
   }
   const int CaP = (a->c + 3) & ~3, kbP = (d->R * d->S * b->c + 7) & ~7;
@@ -1745,6 +1750,7 @@ extern "C" int dct_enet_wgrad(const dct_view* a, const dct_enet_tf* tfa, const d
   else ENET_T(dtype, (enet_launch<WgradK<T, 1>>(DCT_PROF_OTHER, dim3(nb), dim3(256), lds, st, p)));
   const WRedP wr = {(const float*)workspace, dw, E, nb};
   enet_launch<WgradRedK>(DCT_PROF_OTHER, dim3(div_up(E, 16)), dim3(256), 0, st, wr);
+  DCT_PLAN_NOTE("enet wgrad valu SL %d: ppb %lld, %d blocks", SL, ppb, nb);
   return dct_check_launch();
 }
 

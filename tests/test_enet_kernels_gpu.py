@@ -59,10 +59,10 @@ def make_tf(K, C, mode, g):
 
 
 def mfma_form(dt, cin, cout, taps):
-    """dct_enet_conv's MFMA form (csrc/enet.hip::enet_mconv_kernel): low-precision modes, >= 16 input channels in whole 8-channel
-    groups, K = taps * cin in whole steps of 16.  It rounds BOTH operands of the contraction to the compute dtype (fp32 accumulate);
+    """dct_enet_conv's MFMA form (csrc/enet.hip::enet_conv_impl's host check): low-precision modes, >= 16 input channels in whole
+    groups of 16 (every K-step of 16 stays inside one tap).  It rounds BOTH operands of the contraction to the compute dtype (fp32 accumulate);
     the VALU form multiplies the stored values in fp32.  dct_enet_wgrad's MFMA form (enet_mwgrad_kernel) takes every shape."""
-    return dt != torch.float32 and cin >= 16 and cin % 8 == 0 and (taps * cin) % 16 == 0 and cout <= 128
+    return dt != torch.float32 and cin >= 16 and cin % 16 == 0 and cout <= 128
 
 
 def set_mfma(on):
@@ -78,7 +78,7 @@ def set_mfma(on):
     (32, 32, 5, 1, 1, (2, 0), 1, True, 3),       # asymmetric 5x1
     (16, 64, 1, 1, 1, (0, 0), 1, True, 2),       # block1x1_2: two 32-channel MFMA column tiles
     (32, 128, 1, 1, 1, (0, 0), 1, True, 3),      # ... four
-    (24, 40, 3, 3, 1, (1, 1), 1, False, 0),      # ragged: K = 216 is not a multiple of 16 (VALU form), 40 channels out
+    (24, 40, 3, 3, 1, (1, 1), 1, False, 0),      # ragged: 24 channels are not whole groups of 16 (VALU form), 40 channels out
     (32, 24, 3, 3, 2, (1, 1), 1, False, 0),      # strided 3x3, a partly filled column tile
     (32, 40, 1, 1, 2, (0, 0), 1, False, 0),      # strided 1x1, a partly filled second column tile
     (14, 16, 2, 2, 2, (0, 0), 1, False, 0),      # down-sampling 2x2 s2
