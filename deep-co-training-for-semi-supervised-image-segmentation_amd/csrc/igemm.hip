@@ -553,6 +553,78 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void igemm2_kernel(IgemmPar
   }
 }
 
+// One tap x 64 channels of the 16 x 16-patch form of igemm3m (below): TR x PXB accumulators of a wave on ONE fragment set.  The two
+// sets of the 8 x 16 form (a[2][TR] + b[2][PXB]) are 64 registers at PXB = 4; with 64 accumulators that is 148 VGPRs, three waves per
+// SIMD.  Here half-step 0 runs column by column, and a column's pixel fragment of half-step 1 is read into the column's registers
+// as soon as its MFMAs are issued; the weight fragments follow inside the last column.  Half-step 1 then runs row by row behind
+// counted waits (LDS reads return in order), its last column at the end.  Every accumulator sees half-step 0, then half-step 1.
+__device__ __forceinline__ void lgkm_wait_n(int n) {      // n is a constant once the loops around the call are unrolled
+  switch (n) {
+    case 0: lgkm_wait3<0>(); break;
+    case 1: lgkm_wait3<1>(); break;
+    case 2: lgkm_wait3<2>(); break;
+    case 3: lgkm_wait3<3>(); break;
+    case 4: lgkm_wait3<4>(); break;
+    case 5: lgkm_wait3<5>(); break;
+    case 6: lgkm_wait3<6>(); break;
+    default: lgkm_wait3<7>(); break;
+  }
+}
+template <int TR, int PXB, int HW>
+__device__ __forceinline__ void tall_tap(unsigned wa0, unsigned Xs, unsigned rho0, int tap_rows, int kq, f32x4 (&acc)[TR][PXB]) {
+  static_assert(TR <= 4 && PXB <= 4, "immediate offsets and wait counts");
+  const unsigned wa1 = wa0 ^ 64u;
+  unsigned rho_t = rho0;
+  asm volatile("" : "+v"(rho_t));
+  const unsigned pi0 = rho_t + tap_rows;
+  const unsigned xrow = Xs + (pi0 << 7);
+  unsigned xj[PXB];
+#pragma unroll
+  for (int j = 0; j < PXB; ++j) xj[j] = xrow | (((kq ^ ((pi0 + j * HW) >> 1)) & 7) << 4);
+  bf16x8 a[TR], b[PXB];
+  RdRows<0, TR, 16 * 128>::run(wa0, a);
+  RdCols<0, PXB, HW * 128>::run(xj, 0u, b);
+#pragma unroll
+  for (int j = 0; j < PXB; ++j) {
+    lgkm_wait_n(PXB - 1);                      // b[j] is PXB reads back: b[j + 1 ..] and the second halves of the columns before it are behind it
+    if (j == 0) {
+#pragma unroll
+      for (int i = 0; i < TR; ++i) touch8(a[i]);
+    }
+    touch8(b[j]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < TR; ++i) {
+      acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+      if (j == PXB - 1) {                      // last column: row i's weight fragment is free
+        __builtin_amdgcn_sched_barrier(0);
+        rd128o_dyn(wa1, i * 16 * 128, a[i]);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    rd128o_dyn(xj[j] ^ 64u, j * HW * 128, b[j]);
+  }
+  // outstanding, in order: b[0 .. PXB - 2], a[0 .. TR - 1], b[PXB - 1]
+#pragma unroll
+  for (int i = 0; i < TR; ++i) {
+    lgkm_wait_n(TR - i);
+    touch8(a[i]);
+    if (i == 0) {
+#pragma unroll
+      for (int j = 0; j < PXB - 1; ++j) touch8(b[j]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < PXB - 1; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  lgkm_wait_n(0);
+  touch8(b[PXB - 1]);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < TR; ++i) acc[i][PXB - 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[PXB - 1], acc[i][PXB - 1], 0, 0, 0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // bf16 3x3 stride-1 kernel with a shared input halo ("v3").  At 128 x 128 x 64 per K-step the v2 kernel moves
 // 32 KiB from L2 through the CU's vector-memory path into LDS per 2.1 MFLOP = 64 FLOP/B, which is exactly the
@@ -571,16 +643,20 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void igemm2_kernel(IgemmPar
 // Variants of this tile that were measured and removed: a four-slot ring of 32-channel weight half-stages with
 // counted vmcnt and raw barriers (-15 %: twice the barriers for the same MFMAs), four waves of 64 x 64 instead of eight of
 // 32 x 64 (-8 %), three unrolled taps per loop trip (-13 %), an XCD-aware tile order (level), amdgpu_waves_per_eu(4) (-1 %).
-template <int BN, int NWM, int NWN, int ABUFS>
-__global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, int tiles_x, int tiles_y) {
+// TH: patch height.  8 is the tile described above.  16 is a 16 x 16 patch on ONE halo stage for any number of channel
+// slices: 324 halo rows (41 KiB) + two weight stages keep two BN = 128 blocks on a CU, a wave owns four patch rows (32 MFMAs per barrier
+// round, a tap's weight stage serves 256 pixels), and the halo of the next slice is staged in the open, between two barriers, behind
+// tap 8.  Same MFMA sequence per output element: bit-identical to TH = 8.
+template <int BN, int NWM, int NWN, int ABUFS, int TH>
+__device__ __forceinline__ void igemm3m_body(const IgemmParams& p, int tiles_x, int tiles_y) {
   constexpr int NW = NWM * NWN;
-  constexpr int TH = 8, TW = 16, BM = TH * TW, HW = TW + 2, HROWS = (TH + 2) * HW;   // 180 halo rows of 128 B
-  constexpr int APIECES = (HROWS + 7) / 8, A_BYTES = APIECES * 8 * 128;              // 23 pieces, 23552 B
+  constexpr int TW = 16, BM = TH * TW, HW = TW + 2, HROWS = (TH + 2) * HW;           // 180 (TH = 8) / 324 (16) halo rows of 128 B
+  constexpr int APIECES = (HROWS + 7) / 8, A_BYTES = APIECES * 8 * 128;              // 23 pieces, 23552 B / 41 pieces, 41984 B
   constexpr int B_BYTES = BN * 128, BPIECES = BN / 8;
   constexpr int NPA = (APIECES + NW - 1) / NW, NPB = BPIECES / NW;
   constexpr int WTN = BN / NWN, TN = WTN / 32;
-  static_assert(NWM == 4 && BPIECES % NW == 0 && TN >= 1, "tile/wave mismatch");
-  constexpr int PXB = 8 / NWM;             // 16-pixel column blocks (patch rows) per wave: 2
+  static_assert(NWM == 4 && BPIECES % NW == 0 && TN >= 1 && (TH == 8 || (TH == 16 && ABUFS == 1)), "tile/wave mismatch");
+  constexpr int PXB = TH / NWM;            // 16-pixel column blocks (patch rows) per wave: 2 / 4
   extern __shared__ __attribute__((aligned(128))) char smem[];
   char* Abuf = smem;                       // halo stage(s)
   char* Bbuf = smem + ABUFS * A_BYTES;     // two weight stages
@@ -616,7 +692,9 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
     for (int i = 0; i < NPA; ++i) {
       const int piece = wave + i * NW;
       if (piece < APIECES) {
-        const char* src = aoff[i] >= 0 ? reinterpret_cast<const char*>(xb + aoff[i] + c0) : zero;
+        int ao = aoff[i];
+        if constexpr (TH == 16) asm volatile("" : "+v"(ao));      // six 64-bit source addresses kept across the K loop are twelve registers this form does not have
+        const char* src = ao >= 0 ? reinterpret_cast<const char*>(xb + ao + c0) : zero;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(buf + piece * 1024), 16, 0, 0);
       }
     }
@@ -631,8 +709,11 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
   auto stageB = [&](char* buf, int tap, int c0) {
     const long long woff = (long long)tap * p.Cin + c0;
 #pragma unroll
-    for (int i = 0; i < NPB; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(wsrc[i] + woff), (lptr_t)(buf + (wave + i * NW) * 1024), 16, 0, 0);
+    for (int i = 0; i < NPB; ++i) {
+      // TH = 16: piece i's rows are NW * 8 rows behind piece 0's with the same swizzle -- one lane address and a scalar offset instead of NPB addresses
+      const bf16_t* src = TH == 16 ? wsrc[0] + (woff + (long long)i * (NW * 8) * Ktot) : wsrc[i] + woff;
+      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(buf + (wave + i * NW) * 1024), 16, 0, 0);
+    }
   };
 
   constexpr int TR = WTN / 16;                 // 16-channel row blocks per wave
@@ -698,6 +779,9 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
       else if (c + 1 < nch) stageB(Bbuf + (bb ^ 1) * B_BYTES, 0, (c + 1) * 64);
       if (ABUFS == 2 && t == 0 && c + 1 < nch) stageA(Abuf + (ab ^ 1) * A_BYTES, (c + 1) * 64);
       if (wave_live) {
+      if constexpr (TH == 16) {
+        tall_tap<TR, PXB, HW>(Wb0 + bb * B_BYTES, Xs, rho0, rr * HW + sx, kq, acc);
+      } else {
       const unsigned wa0 = Wb0 + bb * B_BYTES, wa1 = wa0 ^ 64u;
       unsigned rho_t = rho0;
       asm volatile("" : "+v"(rho_t));                        // recompute the tap's two addresses here (6 VALU) instead of keeping hoisted ones in registers
@@ -726,15 +810,23 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[k2][i], b[k2][j], acc[i][j], 0, 0, 0);
       }
       }
+      }
       __syncthreads();
       bb ^= 1;
     }
-    ab ^= 1;
+    if constexpr (ABUFS == 2) ab ^= 1;
+    if constexpr (TH == 16) if (c + 1 < nch) {
+      // one halo stage, more slices (TH = 16): the barrier above ended every wave's reads of this slice's halo, so the next slice is
+      // staged over it in the open -- as long as a prologue -- while tap 0's weight stage, issued at tap 8, is already in flight
+      stageA(Abuf, (c + 1) * 64);
+      __syncthreads();
+    }
   }
 
   // ---- epilogue (staged through LDS as in v2): tile row = patch pixel py * 16 + px
   constexpr int CPR = BN / 8;
-  static_assert(BM * BN * 2 <= ABUFS * A_BYTES + (BN * 128 * 2 - BM * 8), "epilogue tile does not fit");
+  static_assert(BM * BN * 2 <= ABUFS * A_BYTES + (BN * 128 * 2 - BM * 8),
+                "epilogue tile does not fit (TH = 16, BN = 128: 64 KiB in 41 KiB of halo stage + 32 KiB of weight stages - 2 KiB of row tables)");
   char* tile = smem;                                   // BM * BN * 2 bytes: the halo stage(s) and, if needed, the head of the weight stages
   if constexpr (BN == 64 && NWN == 1 && ABUFS == 1) {
     if (p.stem_x) {
@@ -817,16 +909,18 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
       return;
     }
   }
+  // (TH = 16: the thread index is rebuilt from the wave and the lane, so that its register is free across the K loop)
+  const int tid_e = TH == 16 ? wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : tid;
   int* rowY = reinterpret_cast<int*>(smem + ABUFS * A_BYTES + 2 * B_BYTES - BM * 8);   // tail of the weight stages
   int* rowM = rowY + BM;
-  if (tid < BM) {
-    const int oy = y0 + (tid >> 4), ox = x0 + (tid & 15);
+  if (tid_e < BM) {
+    const int oy = y0 + (tid_e >> 4), ox = x0 + (tid_e & 15);
     int oy_ = -1, om_ = -1;
     if (oy < p.Ho && ox < p.Wo) {
       oy_ = (int)(img * p.ysN + oy * p.ysH + ox * p.ysW);
       om_ = (int)(img * p.msN + oy * p.msH + ox * p.msW);
     }
-    rowY[tid] = oy_; rowM[tid] = om_;
+    rowY[tid_e] = oy_; rowM[tid_e] = om_;
   }
   {
     // accumulator (i, j): channels wn * WTN + 16 * i + 4 * kq + {0..3} of pixel (patch row PXB * wm + j, column l15)
@@ -855,10 +949,19 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, 
   __syncthreads();
   if (p.pool_y) {
     asm volatile("" ::: "memory");       // a real branch (the forward launches of three encoder levels take it, nobody else)
-    staged_pool_out<BN, NW>(p, tile, img, y0, x0, n0, tid);
+    staged_pool_out<BN, NW, TH>(p, tile, img, y0, x0, n0, tid_e);
     if (p.pool_only) return;
   }
-  staged_rows_out<BM, BN, NW>(p, tile, rowY, rowM, n0, tid);
+  staged_rows_out<BM, BN, NW>(p, tile, rowY, rowM, n0, tid_e);
+}
+template <int BN, int NWM, int NWN, int ABUFS>
+__global__ __launch_bounds__(NWM * NWN * 64) void igemm3m_kernel(IgemmParams p, int tiles_x, int tiles_y) {
+  igemm3m_body<BN, NWM, NWN, ABUFS, 8>(p, tiles_x, tiles_y);
+}
+// 16 x 16 patches: two 8-wave blocks per CU are four waves per SIMD, 128 registers per lane
+template <int BN, int NWM, int NWN>
+__global__ __launch_bounds__(NWM * NWN * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void igemm3m_tall_kernel(IgemmParams p, int tiles_x, int tiles_y) {
+  igemm3m_body<BN, NWM, NWN, 1, 16>(p, tiles_x, tiles_y);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1202,6 +1305,11 @@ int g_tune_igemm_split_min_kiters = 4;    // ... and so do layers with fewer K-s
 int g_tune_igemm_halo_cover = 75;      // percent of the image the 8 x 16 patches must cover
 int g_tune_igemm_halo_min_blocks = 400;
 int g_tune_igemm_pool = 1;      // diagnostic (1005): 0 = a requested pooling always runs as its own launch behind the conv
+int g_tune_igemm_halo_tall = 1;              // 16 x 16 patches (igemm3m_tall_kernel): 0 never, 1 planner's choice, 2 every layer the form can run (the tests)
+int g_tune_igemm_halo_tall_min_blocks = 512; // fewest 16 x 16 blocks for planner's choice.  Sweep on the captured cfg2 step, six alternating fresh processes per
+                                             // arm on one box (profiles/halo16_step_ab.txt): 1000 (dec2a / dec2b only) -1.0 %, 512 (+ dec3a fwd, dec3b, enc1a's data
+                                             // gradient) -2.5 %, 280 (+ enc2a's data gradient, 288 blocks) level with 512; at 256 blocks (dec3a / enc3a data gradients)
+                                             // the tall patches LOSE 8-15 % per layer (profiles/halo16_conv_per_layer.txt): one block per CU has nobody to cover its re-stages
 int g_tune_igemm_halo = 1;      // 3x3 stride-1 layers with large images: shared-halo kernel (igemm3m_kernel); 0: always the per-tap kernel
 
 // the channel counts every route needs (dct_conv2d asks this among its argument checks, where the status codes have it)
@@ -1278,6 +1386,19 @@ static void launch_v3(const IgemmParams& p, int tiles_x, int tiles_y, int images
   }
   const dim3 grid((unsigned)(images * tiles_y * tiles_x), p.N / BN, 1);
   DCT_LAUNCH_FAM(DCT_FAM_IGEMM3M, DCT_PROF_IGEMM, (igemm3m_kernel<BN, 4, NWN, ABUFS>), grid, dim3(4 * NWN * 64), lds, st, p, tiles_x, tiles_y);
+}
+
+template <int BN, int NWN>
+static void launch_v3_tall(const IgemmParams& p, int tiles_x, int tiles_y, int images, hipStream_t st) {
+  constexpr size_t lds = (size_t)(41 * 1024) + 2 * (size_t)BN * 128 + (size_t)BN * 4;   // ONE 18 x 18-row halo stage, two weight stages, bias
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm3m_tall_kernel<BN, 4, NWN>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  const dim3 grid((unsigned)(images * tiles_y * tiles_x), p.N / BN, 1);
+  DCT_LAUNCH_FAM(DCT_FAM_IGEMM3M, DCT_PROF_IGEMM, (igemm3m_tall_kernel<BN, 4, NWN>), grid, dim3(4 * NWN * 64), lds, st, p, tiles_x, tiles_y);
 }
 
 // Packed-rows shared-halo kernel (igemm3p_kernel) for small images: geometry and split over channel slices.
@@ -1397,7 +1518,8 @@ struct ConvPlan {
   Route route;
   Plan tap;                   // per-tap tile and split-K: what ROUTE_TAP launches, and the K-step fields of IgemmParams on every route
   PlanP packed;               // ROUTE_PACKED
-  int bn, tiles_x, tiles_y; long long blocks; double cover;   // ROUTE_HALO*: channel tile, 8 x 16 patches over an image, blocks, image part of the patches
+  int bn, tiles_x, tiles_y; long long blocks; double cover;   // ROUTE_HALO*: channel tile, th x 16 patches over an image, blocks, image part of the patches
+  int th;                     // ROUTE_HALO: patch height, 8 or 16
   int staged;                 // LDS-staged epilogue (16-byte row stores)
   int fused_pool;             // the requested pooling happens in the epilogue; if not, the pooling kernel runs behind the conv
   int bits_after;             // neither an epilogue nor a fold of this launch leaves the ReLU bits: relu_bits_kernel runs behind it
@@ -1428,8 +1550,22 @@ static int plan_conv(const dct_view* x, const dct_view* y, const dct_conv_desc* 
   // 32-bit addressing inside the kernel: x within 2^31 elements, a weight tile's rows within 2^32 bytes of its first
   const bool x32 = (long long)x->n * x->sn < (1ll << 31) && (long long)cp.bn * 9 * x->c * 2 < (1ll << 32);
   // measured (tools/bench_conv.py --ab): the 64-channel tile only pays with a single channel slice (four blocks per CU)
-  const bool halo = pl.v2 && pl.splits == 1 && g_tune_igemm_halo && d->R == 3 && d->S == 3 && d->stride == 1 && d->dil == 1 && !d->scatter2x2 &&
-                    x32 && cp.cover >= g_tune_igemm_halo_cover * 0.01 && cp.blocks >= g_tune_igemm_halo_min_blocks && (cp.bn == 128 || x->c == 64);
+  const bool halo_form = pl.v2 && pl.splits == 1 && g_tune_igemm_halo && d->R == 3 && d->S == 3 && d->stride == 1 && d->dil == 1 && !d->scatter2x2 && x32;
+  bool halo = halo_form && cp.cover >= g_tune_igemm_halo_cover * 0.01 && cp.blocks >= g_tune_igemm_halo_min_blocks && (cp.bn == 128 || x->c == 64);
+  // 16 x 16 patches on one halo stage (igemm3m_tall_kernel), for the layers of the 128-channel tile.  Planner's choice (1) takes them where
+  // the 8 x 16 patches are taken today, the taller patches still cover the image as well as the cover knob asks, and there are enough of
+  // them for two blocks per CU; 2 takes every layer the form can run, whatever its cover and block count (the tests).
+  // (The 64-channel layers with more than one channel slice -- dec2a's data gradient, enc1a forward -- stay on the per-tap kernel: its K
+  // order is tap-major, so moving them would change their results in the last bits)
+  cp.th = 8;
+  if (g_tune_igemm_halo_tall && halo_form && !d->stem_x && cp.bn == 128 && (halo || g_tune_igemm_halo_tall == 2)) {
+    const int ty16 = (Ho + 15) / 16;
+    const long long blocks16 = (long long)y->n * ty16 * cp.tiles_x * (N / 128);
+    const double cover16 = (double)Ho * Wo / ((double)ty16 * 16 * cp.tiles_x * 16);
+    if (g_tune_igemm_halo_tall == 2 || (cover16 >= g_tune_igemm_halo_cover * 0.01 && blocks16 >= g_tune_igemm_halo_tall_min_blocks)) {
+      cp.th = 16; cp.tiles_y = ty16; cp.blocks = blocks16; cp.cover = cover16; halo = true;
+    }
+  }
   // the stem's weight gradient: one [64][10] fp32 record per patch (its layers have one channel tile) and the scratch of their fold
   const size_t stem_need = d->stem_x ? (size_t)patches * 640 * sizeof(float) + dct_split_dw_db_scratch(64, 9) : 0;
   cp.packed = make_plan_p(x, y, d, dtype, N);
@@ -1541,10 +1677,12 @@ extern "C" int dct_conv2d(const dct_view* x, const void* w_packed, const float* 
       break;
     case ROUTE_HALO:
       if (cp.fused_pool) { p.pool_y = (char*)d->pool_out; p.pool_codes = d->pool_codes; p.pool_only = d->pool_only ? 1 : 0; }
-      if (cp.bn == 128) {
+      if (cp.th == 16) {
+        launch_v3_tall<128, 2>(p, cp.tiles_x, cp.tiles_y, y->n, st);
+      } else if (cp.bn == 128) {
         if (x->c == 64) launch_v3<128, 2, 1>(p, cp.tiles_x, cp.tiles_y, y->n, st); else launch_v3<128, 2, 2>(p, cp.tiles_x, cp.tiles_y, y->n, st);
       } else launch_v3<64, 1, 1>(p, cp.tiles_x, cp.tiles_y, y->n, st);
-      DCT_PLAN_NOTE("igemm3m shared-halo 8x16 patches x %d ch: %lld blocks, cover %.0f %%, %d K-steps%s", cp.bn, cp.blocks, cp.cover * 100, 9 * x->c / 64,
+      DCT_PLAN_NOTE("igemm3m shared-halo %dx16 patches x %d ch: %lld blocks, cover %.0f %%, %d K-steps%s", cp.th, cp.bn, cp.blocks, cp.cover * 100, 9 * x->c / 64,
                     p.pool_y ? (p.pool_only ? ", pooled in the epilogue, y not stored" : ", pooled in the epilogue") : "");
       break;
     case ROUTE_PACKED:
@@ -1586,6 +1724,8 @@ extern "C" int dct_tune_set(int knob, int value) {
     case DCT_TUNE_IGEMM_PACKED: g_tune_igemm_packed = value; return DCT_OK;
     case DCT_TUNE_IGEMM_HALO_MIN_BLOCKS: g_tune_igemm_halo_min_blocks = value; return DCT_OK;
     case DCT_TUNE_IGEMM_HALO_COVER: g_tune_igemm_halo_cover = value; return DCT_OK;
+    case DCT_TUNE_IGEMM_HALO_TALL: if (value < 0 || value > 2) return DCT_ERR_BAD_ARG; g_tune_igemm_halo_tall = value; return DCT_OK;
+    case DCT_DIAG_IGEMM_HALO_TALL_MIN_BLOCKS: if (value < 1) return DCT_ERR_BAD_ARG; g_tune_igemm_halo_tall_min_blocks = value; return DCT_OK;
     case DCT_TUNE_IGEMM_SPLIT_TARGET: if (value < 64) return DCT_ERR_BAD_ARG; g_tune_igemm_split_target = value; return DCT_OK;
     case DCT_TUNE_ENET_MWGRAD_WAVES: if (value < 64) return DCT_ERR_BAD_ARG; g_enet_mwgrad_waves = value; return DCT_OK;
     case DCT_TUNE_ENET_MFMA: if (value < 0 || value > 3) return DCT_ERR_BAD_ARG; g_enet_mfma = value; return DCT_OK;

@@ -139,10 +139,10 @@ __device__ __forceinline__ void staged_rows_out(const IgemmParams& p, const char
 // reads it): the patch starts at even image coordinates, so it holds whole windows -- 4 x 8 pooled pixels x BN / 8 chunks, one
 // item per thread.  Same scan order, comparisons and codes as maxpool_fwd_codes_kernel (pointwise.hip), on the same bf16 values
 // that go to y: bit-identical to pooling y afterwards, without re-reading it (130 MB per network and step at the first UNet level).
-template <int BN, int NW>
+template <int BN, int NW, int TH = 8>
 __device__ __forceinline__ void staged_pool_out(const IgemmParams& p, const char* tile, int img, int y0, int x0, int n0, int tid) {
   constexpr int CPR = BN / 8;
-  for (int id = tid; id < 32 * CPR; id += NW * 64) {
+  for (int id = tid; id < TH * 4 * CPR; id += NW * 64) {      // TH / 2 x 8 pooled pixels (a 16-row patch holds whole windows as well)
     const int cc = id % CPR, q = id / CPR;
     const int qy = q >> 3, qx = q & 7;
     const int oy = y0 + 2 * qy, ox = x0 + 2 * qx;
@@ -210,6 +210,9 @@ typedef __attribute__((address_space(3))) const char* lptr_c;
 __device__ __forceinline__ void rd128(unsigned addr, bf16x8& dst) { asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr)); }
 template <int OFF> __device__ __forceinline__ void rd128o(unsigned addr, bf16x8& dst) {     // ds_read_b128 with an immediate byte offset
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+}
+__device__ __forceinline__ void rd128o_dyn(unsigned addr, int off, bf16x8& dst) {      // the same where the offset is a constant only after unrolling
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off));
 }
 template <int I, int N, int STRIDE> struct RdRows {      // dst[i] <- 16 bytes at addr + i * STRIDE, i = I .. N - 1 (immediate offsets)
   __device__ static __forceinline__ void run(unsigned addr, bf16x8 (&dst)[N]) {

@@ -15,7 +15,7 @@ import sys
 
 
 def cls(name):
-    for k in ("igemm3m", "igemm3p", "igemm3", "igemm2", "wgrad3", "wgrad2"):
+    for k in ("igemm3m_tall", "igemm3m", "igemm3p", "igemm3", "igemm2", "wgrad3", "wgrad2"):
         if k + "_kernel" in name:
             return k
     return None
