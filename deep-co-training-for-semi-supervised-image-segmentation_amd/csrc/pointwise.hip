@@ -608,10 +608,13 @@ __global__ __launch_bounds__(256) void maxpool_bwd_codes_kernel(const unsigned c
   if (!id.ok) return;
   float g[VEC];
   VecIO<T, VEC>::load(reinterpret_cast<const T*>(dy.ptr) + voff(dy, id.n, id.y, id.x) + id.cv * VEC, g);
-  union { unsigned char b[VEC]; unsigned w[VEC / 4]; } cu;
-  const unsigned* cp = reinterpret_cast<const unsigned*>(codes + t * VEC);
-  if constexpr (VEC == 8) { const uint2 q = *reinterpret_cast<const uint2*>(cp); cu.w[0] = q.x; cu.w[1] = q.y; }
-  else cu.w[0] = cp[0];
+  union { unsigned char b[VEC]; unsigned w[VEC >= 4 ? VEC / 4 : 1]; } cu;
+  if constexpr (VEC == 1) cu.b[0] = codes[t];                           // the scalar form: one element, one code byte
+  else {
+    const unsigned* cp = reinterpret_cast<const unsigned*>(codes + t * VEC);
+    if constexpr (VEC == 8) { const uint2 q = *reinterpret_cast<const uint2*>(cp); cu.w[0] = q.x; cu.w[1] = q.y; }
+    else cu.w[0] = cp[0];
+  }
   const unsigned char* cd = cu.b;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
@@ -1147,9 +1150,15 @@ extern "C" int dct_maxpool2x2_bwd_codes(const uint8_t* codes, const dct_view* dy
   if (dy->h != (dx->h + 1) / 2 || dy->w != (dx->w + 1) / 2) return DCT_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, {
-    if (!vec_ok(dy, VEC, sizeof(T)) || !vec_ok(dx, VEC, sizeof(T)) || ((uintptr_t)codes % VEC)) return DCT_ERR_UNSUPPORTED;
-    const long long total = (long long)dy->n * dy->h * dy->w * (dy->c / VEC);
-    DCT_LAUNCH(DCT_PROF_POINTWISE, (maxpool_bwd_codes_kernel<T, VEC>), dim3(div_up(total, 256)), dim3(256), 0, st, codes, to_view(dy), to_view(dx), relu_mask, scale);
+    if (vec_ok(dy, VEC, sizeof(T)) && vec_ok(dx, VEC, sizeof(T)) && ((uintptr_t)codes % VEC) == 0) {
+      const long long total = (long long)dy->n * dy->h * dy->w * (dy->c / VEC);
+      DCT_LAUNCH(DCT_PROF_POINTWISE, (maxpool_bwd_codes_kernel<T, VEC>), dim3(div_up(total, 256)), dim3(256), 0, st, codes, to_view(dy), to_view(dx), relu_mask, scale);
+    } else {
+      // views off the 16-byte width (channel counts, slice offsets): one element per thread -- what the fall-back of the un-pooling
+      // with a skip gather (hip_ops.maxpool_bwd) runs behind the scalar bilinear backward
+      const long long total = (long long)dy->n * dy->h * dy->w * dy->c;
+      DCT_LAUNCH(DCT_PROF_POINTWISE, (maxpool_bwd_codes_kernel<T, 1>), dim3(div_up(total, 256)), dim3(256), 0, st, codes, to_view(dy), to_view(dx), relu_mask, scale);
+    }
   });
   return dct_check_launch();
 }

@@ -361,9 +361,9 @@ def maxpool_bwd(x, dy, dx, relu_mask=False, scale=1.0, codes=None, skip=None):
                                                        _dt(dy), stream())
         if rc == _lib.ERR_UNSUPPORTED:
             # views the 16-byte kernel cannot take (channel counts / slice offsets off the vector width): the sum formed in memory,
-            # as before the fusion -- bilinear backward (which has a scalar form) into a buffer, + dy, then the plain un-pooling
-            total = bilinear_bwd(skip, torch.empty_like(dy))
-            total += dy
+            # as before the fusion -- bilinear backward (which has a scalar form) accumulating onto a copy of dy (the sum formed in fp32 and
+            # rounded to the storage type once), then the plain un-pooling, which has a scalar form too
+            total = bilinear_bwd(skip, dy.clone(), accumulate=True)
             vt = view(total)
             call("dct_maxpool2x2_bwd_codes", ptr(codes), C.byref(vt), C.byref(vdx), int(relu_mask), float(scale), _dt(dy), stream())
             return dx

@@ -192,7 +192,8 @@ int dct_maxpool2x2_bwd(const dct_view* x, const dct_view* dy, const dct_view* dx
 
 /* The same pair with the routing kept from the forward pass instead of re-derived from x: codes (uint8, dense
  * [N][y.h][y.w][C], 8-byte aligned) receives per pooled element bits 0-1 = window position (2*dy+dx) of the first maximum,
- * bit 2 = "maximum > 0" (the ReLU / dropout gate), bit 3 = no maximum; the backward pass reads dy and codes only. */
+ * bit 2 = "maximum > 0" (the ReLU / dropout gate), bit 3 = no maximum; the backward pass reads dy and codes only.
+ * dct_maxpool2x2_bwd_codes also takes views off the 16-byte vector width (one element per thread; codes then need no alignment). */
 int dct_maxpool2x2_fwd_codes(const dct_view* x, const dct_view* y, uint8_t* codes, int dtype, dct_stream stream);
 int dct_maxpool2x2_bwd_codes(const uint8_t* codes, const dct_view* dy, const dct_view* dx, int relu_mask,
                              float scale, int dtype, dct_stream stream);
