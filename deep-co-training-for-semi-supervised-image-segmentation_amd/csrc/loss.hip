@@ -258,6 +258,74 @@ __global__ __launch_bounds__(256) void ce_map_bwd_kernel(const float* logits, co
   ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, gmul, dmap, dl, acc);
 }
 
+// ---- boundary loss: the softmax weighted by the signed distance map (the rule: include/dct.h, dct_boundary_*) --------------------------
+// phi has the layout of the logits: both are read with the same loads (16 bytes at C = 4, two of them at C = 8).
+template <int C> __device__ __forceinline__ void load_px16(const float* p, long long pix, float v[C]) {
+  if constexpr (C == 8) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p + pix * 8), u = *reinterpret_cast<const f32x4*>(p + pix * 8 + 4);
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; v[4] = u[0]; v[5] = u[1]; v[6] = u[2]; v[7] = u[3];
+  } else {
+    load_px<C>(p, pix, v);
+  }
+}
+// partial[2b] = the block's sum over counted pixels of sum_{c in mask} s_c phi_c, partial[2b + 1] = its number of counted pixels
+template <int C>
+__global__ __launch_bounds__(256) void bd_fwd_kernel(const float* logits, const long long* tgt, const float* phi, long long P, int ignore, int mask,
+                                                      float* partial) {
+  float sum = 0.f, cnt = 0.f;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    if (!counted<C>(tgt[pix], ignore)) continue;
+    float x[C], p[C], f[C];
+    load_px16<C>(logits, pix, x);
+    load_px16<C>(phi, pix, f);
+    softmax_px<C>(x, p);
+    float a = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) if (mask >> c & 1) a = fmaf(p[c], f[c], a);
+    sum += a; cnt += 1.f;
+  }
+  block_partial2(sum, cnt, partial);
+}
+// finalize_kernel's fold; out[0] = sum / (N K), 0 when nothing is counted; out[1] = N
+__global__ __launch_bounds__(256) void bd_finalize_kernel(const float* partial, int blocks, float* out, float K) {
+  __shared__ float sa[256], sb[256];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
+  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[0] = sb[0] > 0.f ? sa[0] / (sb[0] * K) : 0.f;
+    out[1] = sb[0];
+  }
+}
+// dl (=|+=) (g s_c) (q_c - sum_k s_k q_k), q_c = m_c phi_c / (N K); an uncounted pixel gets 0 (N = 0: every pixel is uncounted)
+template <int C>
+__global__ __launch_bounds__(256) void bd_bwd_kernel(const float* logits, const long long* tgt, const float* phi, long long P, int ignore, int mask,
+                                                      float K, const float* count, const float* gscale, float gmul, float* dl, int acc) {
+  const float g = (gscale ? gscale[0] : 1.f) * gmul;
+  const float nk = count[0] * K;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const bool on = counted<C>(tgt[pix], ignore);
+    float x[C], p[C], q[C], d[C];
+    load_px16<C>(logits, pix, x);
+    load_px16<C>(phi, pix, q);
+    softmax_px<C>(x, p);
+    float dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      q[c] = (mask >> c & 1) ? q[c] / nk : 0.f;
+      dot = fmaf(p[c], q[c], dot);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) d[c] = on ? (g * p[c]) * (q[c] - dot) : 0.f;
+    store_px<C>(dl, pix, d, acc);
+  }
+}
+
 // ---- soft Dice and CE + Dice (the rule: include/dct.h) ---------------------------------------------------------------------------------
 // Grid: x walks one image's pixels, y is the image (dice_kernel's choice), so a block's partial row is one image's and a group's sums
 // depend on that group's pixels alone.  A row is NS = 3 C + 2 floats: {sum w l, sum w, then I, S, Y per class}.  A sum is folded in one
@@ -978,6 +1046,43 @@ extern "C" int dct_ce_map_bwd(const float* logits, const int64_t* targets, int64
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_map_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, dmap, gmul,
                             dlogits, accumulate));
+  return dct_check_launch();
+}
+// K of a boundary mask (the number of its bits below C), or a status
+static inline int boundary_k(int64_t pixels, int C_, int class_mask, float& K) {
+  if (pixels < 1) return DCT_ERR_BAD_ARG;
+  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
+  const int k = __builtin_popcount((unsigned)class_mask & ((1u << C_) - 1u));
+  if (k == 0) return DCT_ERR_BAD_ARG;
+  K = (float)k;
+  return DCT_OK;
+}
+extern "C" int dct_boundary_fwd(const float* logits, const int64_t* targets, const float* phi, int64_t pixels, int C_, int ignore_index,
+                                int class_mask, float* out2, void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !phi || !out2 || !workspace) return DCT_ERR_BAD_ARG;
+  if (((uintptr_t)logits | (uintptr_t)phi) & 15) return DCT_ERR_BAD_ARG;
+  float K;
+  const int status = boundary_k(pixels, C_, class_mask, K);
+  if (status != DCT_OK) return status;
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, bd_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, phi, (long long)pixels, ignore_index, class_mask,
+                            (float*)workspace));
+  DCT_LAUNCH(DCT_PROF_LOSS, bd_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, K);
+  return dct_check_launch();
+}
+extern "C" int dct_boundary_bwd(const float* logits, const int64_t* targets, const float* phi, int64_t pixels, int C_, int ignore_index,
+                                int class_mask, const float* count, const float* gscale, float gmul, float* dlogits, int accumulate,
+                                dct_stream stream) {
+  if (!logits || !targets || !phi || !count || !dlogits) return DCT_ERR_BAD_ARG;
+  if (((uintptr_t)logits | (uintptr_t)phi | (uintptr_t)dlogits) & 15) return DCT_ERR_BAD_ARG;
+  float K;
+  const int status = boundary_k(pixels, C_, class_mask, K);
+  if (status != DCT_OK) return status;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, bd_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, phi, (long long)pixels, ignore_index,
+                            class_mask, K, count, gscale, gmul, dlogits, accumulate));
   return dct_check_launch();
 }
 // blocks along x of one image: at most cap / B (at least one), so that B of them stay within cap rows (B rows when B > cap)

@@ -207,7 +207,198 @@ inline int hd_shape_status(int B, int H, int W, int C, int method3d) {
   return DCT_OK;
 }
 
+// ---- signed distance maps of the boundary loss (the rule: include/dct.h, dct_signed_distance) -------------------------------------------
+// The same separable transform, dense and per class.  A pixel belongs to exactly one of C + 1 sets: the C classes and "none" (a target
+// outside [0, C)), so the pixels NOT in class c are the union of the other C sets, and the distance to the nearest of them is the minimum
+// of the distances to those sets.  One to-set map per set therefore carries both sides of every class:
+//   outside G_c:  d2 = best[c];      inside G_c:  d2 = min_{c' != c} best[c']      (best[c'] = min_x' (sx (x - x'))^2 + g[c'][x'])
+// and that minimum is bit for bit the row pass over the column map of "not c" (which is min_{c' != c} g[c']): fma(d, d, .) is monotone
+// in its addend and a minimum does not round.  C + 1 column maps and row scans instead of 2 C, and no select in the inner loop.
+// Launch chain (the caller's stream, everything between the launches in the caller's workspace):
+//   1. sd_classify   targets -> one class byte per pixel (255 = none); clears the per-(image, set) pixel counters
+//   2. sd_columns    hd_columns with the predicate on the class byte, for the C + 1 sets; a thread counts its column's pixels of the set on
+//                    the way down and a wave adds its sum to cnt[b][set] with ONE integer atomic (integers: the same counts every run)
+//   3. sd_rows       a block owns one image row and holds the row of all C + 1 column maps in LDS; a thread scans the full row for all sets
+//                    at once (every LDS read is a 16-byte broadcast of four x'; d = (x - x') sx is formed once per x' for all sets), then
+//                    takes the root, the sign and the - 1 (inside: in fp64, rounded once), applies the zero rule from the counters and stores its pixel's C values together.
+// The row scan is not bounded by the running minimum: the bound differs from lane to lane and a wave runs as long as its slowest lane.
+struct SdWs { size_t cnt, cls, g, total; };
+inline SdWs sd_layout(int B, int H, int W, int C) {
+  const size_t px = (size_t)B * H * W;
+  SdWs w;
+  w.cnt = 0;
+  w.cls = hd_round((size_t)B * (C + 1) * 4);
+  w.g = w.cls + hd_round(px);
+  w.total = w.g + hd_round(px * (C + 1) * 4);
+  return w;
+}
+
+// four pixels per thread: 16-byte target loads, one 4-byte class store (cls is 256-byte aligned in the workspace)
+__global__ __launch_bounds__(256) void sd_classify(const long long* gt, long long px, int C, uint8_t* cls, unsigned* cnt, int ncnt) {
+  if (blockIdx.x == 0) for (int i = threadIdx.x; i < ncnt; i += 256) cnt[i] = 0u;
+  for (long long q = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; q < px; q += (long long)gridDim.x * 1024) {
+    if (q + 4 <= px) {
+      typedef __attribute__((ext_vector_type(2))) long long i64x2;
+      const i64x2 t0 = *reinterpret_cast<const i64x2*>(gt + q), t1 = *reinterpret_cast<const i64x2*>(gt + q + 2);
+      *reinterpret_cast<unsigned*>(cls + q) = hd_gt_class(t0[0], C) | hd_gt_class(t0[1], C) << 8 | hd_gt_class(t1[0], C) << 16 | hd_gt_class(t1[1], C) << 24;
+    } else {
+      for (long long i = q; i < px; ++i) cls[i] = (uint8_t)hd_gt_class(gt[i], C);
+    }
+  }
+}
+
+// One thread per (b, set, column); blockIdx.y = set, C = "none".  g[b][set][y][x] = (sy (y - y'))^2 to the nearest pixel y' of the set in
+// column x, +inf where the column has none.
+// (__restrict__: the class bytes and the map do not overlap, so the unrolled scans may take their loads ahead of the stores between them
+// instead of one memory round trip per row)
+__global__ __launch_bounds__(64) void sd_columns(const uint8_t* __restrict__ cls, float* __restrict__ g, unsigned* cnt, int B, int H, int W, int C, float sy) {
+  const int xchunks = (W + 63) / 64;
+  const int b = blockIdx.x / xchunks, x = (blockIdx.x - b * xchunks) * 64 + threadIdx.x, set = blockIdx.y;
+  const unsigned key = set == C ? HD_NONE : set;
+  int n = 0;
+  if (x < W) {
+    const uint8_t* __restrict__ sp = cls + (size_t)b * H * W + x;
+    float* __restrict__ gp = g + ((size_t)b * (C + 1) + set) * H * W + x;
+    float run = INFINITY;
+#pragma unroll 16
+    for (int y = 0; y < H; ++y) {
+      const bool hit = sp[(size_t)y * W] == key;
+      n += hit;
+      run = hit ? 0.f : run + 1.f;
+      const float t = run * sy;
+      gp[(size_t)y * W] = t * t;
+    }
+    run = INFINITY;
+    for (int y0 = H - 1; y0 >= 0; y0 -= 16) {   // sixteen rows a trip: their loads first (a store to gp in between would hold the next load back)
+      unsigned k[16];
+      float down[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int y = y0 - j;
+        if (y >= 0) { k[j] = sp[(size_t)y * W]; down[j] = gp[(size_t)y * W]; }
+      }
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int y = y0 - j;
+        if (y >= 0) {
+          run = k[j] == key ? 0.f : run + 1.f;
+          const float t = run * sy;
+          gp[(size_t)y * W] = fminf(down[j], t * t);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+  if (threadIdx.x == 0 && n) atomicAdd(cnt + b * (C + 1) + set, (unsigned)n);
+}
+
+// blockIdx.x = b * H + y; dynamic LDS: (C + 1) rows of W rounded up to 4 floats (the pad holds +inf)
+template <int C>
+__global__ __launch_bounds__(256) void sd_rows(const float* g, const uint8_t* cls, const unsigned* cnt, int H, int W, float sx, int class_mask,
+                                               float* phi) {
+  extern __shared__ __attribute__((aligned(16))) float sd_row[];
+  constexpr int CP = C + 1;
+  const int b = blockIdx.x / H, y = blockIdx.x - b * H;
+  const int W4 = (W + 3) & ~3;
+  const size_t plane = (size_t)H * W;
+#pragma unroll
+  for (int c = 0; c < CP; ++c) {
+    const float* gp = g + ((size_t)b * CP + c) * plane + (size_t)y * W;
+    for (int x = threadIdx.x; x < W4; x += 256) sd_row[c * W4 + x] = x < W ? gp[x] : INFINITY;
+  }
+  unsigned live = 0;                      // bit c: class c is in the mask and has a contour in this image (neither absent nor filling it)
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const unsigned n = cnt[b * CP + c];
+    if ((class_mask >> c & 1) && n != 0u && n != (unsigned)(H * W)) live |= 1u << c;
+  }
+  __syncthreads();
+  const uint8_t* cp = cls + ((size_t)b * H + y) * W;
+  float* out = phi + ((size_t)b * H + y) * W * C;
+  for (int x = threadIdx.x; x < W; x += 256) {
+    float best[CP];
+#pragma unroll
+    for (int c = 0; c < CP; ++c) best[c] = INFINITY;
+    float df = (float)x;                  // x - x', an exact integer all the way down
+    for (int x4 = 0; x4 < W4; x4 += 4) {
+      float d[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { d[j] = df * sx; df -= 1.f; }
+#pragma unroll
+      for (int c = 0; c < CP; ++c) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(sd_row + c * W4 + x4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) best[c] = fminf(best[c], fmaf(d[j], d[j], v[j]));
+      }
+    }
+    const unsigned t = cp[x];
+    float other = INFINITY;               // the nearest pixel that is not in the pixel's own set
+#pragma unroll
+    for (int c = 0; c < CP; ++c) other = fminf(other, t == (c == C ? (unsigned)HD_NONE : (unsigned)c) ? INFINITY : best[c]);
+    // Inside, the root and the "- 1" are taken in fp64 and rounded to fp32 ONCE: 1.f - sqrtf(d2) rounds the root at the root's magnitude
+    // and lands up to an ulp of the smaller difference away from the rounded exact value (seen on the device against float64: 1 - sqrt(2)).
+    // One fp64 root per pixel, beside a row scan of W x (C + 1) candidates.
+    const float inside = (float)(1.0 - sqrt((double)other));
+    float v[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float s = t == (unsigned)c ? inside : sqrtf(best[c]);
+      v[c] = (live >> c & 1) ? s : 0.f;
+    }
+    float* o = out + (size_t)x * C;
+    if constexpr (C == 4) *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+    else if constexpr (C == 8) {
+      *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+      *reinterpret_cast<f32x4*>(o + 4) = f32x4{v[4], v[5], v[6], v[7]};
+    } else if constexpr (C == 2) *reinterpret_cast<f32x2*>(o) = f32x2{v[0], v[1]};
+    else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) o[c] = v[c];
+    }
+  }
+}
+
+inline int sd_shape_status(int B, int H, int W, int C) {
+  if (B < 1 || H < 1 || W < 1) return DCT_ERR_BAD_ARG;
+  if (C < 2 || C > 8 || H > HD_MAX_EXTENT || W > HD_MAX_EXTENT || B > 65535) return DCT_ERR_UNSUPPORTED;
+  return DCT_OK;
+}
+
 }  // namespace
+
+extern "C" size_t dct_signed_distance_workspace_bytes(int B, int H, int W, int C) {
+  if (sd_shape_status(B, H, W, C) != DCT_OK) return 0;
+  return sd_layout(B, H, W, C).total;
+}
+
+extern "C" int dct_signed_distance(const int64_t* targets, int B, int H, int W, int C_, int class_mask, float sy, float sx, float* phi,
+                                   void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!targets || !phi || !workspace) return DCT_ERR_BAD_ARG;
+  if (!(sy > 0.f) || !(sx > 0.f) || __builtin_isinf(sy) || __builtin_isinf(sx)) return DCT_ERR_BAD_ARG;
+  if (((uintptr_t)targets | (uintptr_t)phi | (uintptr_t)workspace) & 15) return DCT_ERR_BAD_ARG;
+  const int shape = sd_shape_status(B, H, W, C_);
+  if (shape != DCT_OK) return shape;
+  if (!(class_mask & ((1 << C_) - 1))) return DCT_ERR_BAD_ARG;
+  const SdWs w = sd_layout(B, H, W, C_);
+  if (workspace_bytes < w.total) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  unsigned* cnt = (unsigned*)(ws + w.cnt);
+  uint8_t* cls = (uint8_t*)(ws + w.cls);
+  float* g = (float*)(ws + w.g);
+  const long long px = (long long)B * H * W;
+  long long blocks = (px + 1023) / 1024;
+  if (blocks > 4096) blocks = 4096;
+  DCT_LAUNCH(DCT_PROF_LOSS, sd_classify, dim3((unsigned)blocks), dim3(256), 0, st, (const long long*)targets, px, C_, cls, cnt, B * (C_ + 1));
+  DCT_LAUNCH(DCT_PROF_LOSS, sd_columns, dim3((unsigned)(B * ((W + 63) / 64)), (unsigned)(C_ + 1)), dim3(64), 0, st, (const uint8_t*)cls, g, cnt, B, H, W, C_, sy);
+  const size_t lds = (size_t)(C_ + 1) * ((W + 3) & ~3) * sizeof(float);
+#define SD_ROWS(Cv) case Cv: DCT_LAUNCH(DCT_PROF_LOSS, sd_rows<Cv>, dim3((unsigned)(B * H)), dim3(256), lds, st, (const float*)g, (const uint8_t*)cls, \
+                                        (const unsigned*)cnt, H, W, sx, class_mask, phi); break;
+  switch (C_) { SD_ROWS(2) SD_ROWS(3) SD_ROWS(4) SD_ROWS(5) SD_ROWS(6) SD_ROWS(7) SD_ROWS(8) }
+#undef SD_ROWS
+  return dct_check_launch();
+}
 
 extern "C" size_t dct_hausdorff_workspace_bytes(int B, int H, int W, int C, int method3d) {
   if (hd_shape_status(B, H, W, C, method3d) != DCT_OK) return 0;

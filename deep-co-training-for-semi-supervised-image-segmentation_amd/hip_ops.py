@@ -527,6 +527,46 @@ def ce_map_bwd(logits_pc, targets, C_, dmap, dlogits, weight=None, gmul=1.0, ign
     return dlogits
 
 
+def _i64_dense(t):
+    """int64, contiguous and on the 16-byte grid (a dense view that starts inside its storage gets a copy of its own)."""
+    if t.dtype != torch.int64 or not t.is_contiguous():
+        t = t.to(torch.int64).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def signed_distance(targets_bhw, C_, classes=None, spacing=(1., 1.)):
+    """targets [B, H, W] (int64 made if needed), spacing (sy, sx) -> fp32 [B, H, W, C]: the signed distance of every pixel to the contour
+    of every class in ``classes`` (None: all), negative inside, 0 for a class that is absent from its image, fills it or is not in
+    ``classes`` (dct_signed_distance; the rule: include/dct.h).  Every element is written."""
+    ptr(targets_bhw)                    # (refuses a CPU tensor before anything is sized or copied)
+    B, H, W = targets_bhw.shape
+    mask = (1 << C_) - 1 if classes is None else sum(1 << int(c) for c in set(classes))
+    sy, sx = (float(s) for s in spacing)
+    t = _i64_dense(targets_bhw)
+    need = _lib.load().dct_signed_distance_workspace_bytes(B, H, W, C_)
+    ws = _ws(need, t.device)
+    phi = torch.empty(B, H, W, C_, dtype=torch.float32, device=t.device)
+    call("dct_signed_distance", ptr(t), B, H, W, C_, mask, sy, sx, ptr(phi), ptr(ws), ws.numel(), stream())
+    return phi
+
+
+def boundary_fwd(logits_pc, targets, phi, C_, class_mask=None, ignore_index=255):
+    """Boundary loss (dct_boundary_fwd).  ``logits_pc`` and ``phi``: fp32 [..., C] dense, one row per pixel; ``targets``: int64, one per
+    pixel; ``class_mask``: bit c = class c is in the loss (None: all).  Returns the device tensor [2] = (loss, counted pixels)."""
+    out = torch.empty(2, dtype=torch.float32, device=logits_pc.device)
+    ws = _loss_ws(logits_pc.device)
+    call("dct_boundary_fwd", ptr(logits_pc), ptr(targets), ptr(phi), logits_pc.numel() // C_, C_, int(ignore_index),
+         (1 << C_) - 1 if class_mask is None else int(class_mask), ptr(out), ptr(ws), ws.numel(), stream())
+    return out
+
+
+def boundary_bwd(logits_pc, targets, phi, C_, count, dlogits, class_mask=None, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
+    """``count``: ``out[1:2]`` of boundary_fwd under the same arguments."""
+    call("dct_boundary_bwd", ptr(logits_pc), ptr(targets), ptr(phi), logits_pc.numel() // C_, C_, int(ignore_index),
+         (1 << C_) - 1 if class_mask is None else int(class_mask), ptr(count), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), stream())
+    return dlogits
+
+
 def _ce_dice_args(logits_bpc, C_, class_mask, per_image):
     """(B, pixels per image, mask, G) of fp32 logits [B, ..., C] (dense; the first dimension counts the images)."""
     B = logits_bpc.shape[0]

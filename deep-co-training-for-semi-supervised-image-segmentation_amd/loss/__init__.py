@@ -1,5 +1,6 @@
 """Loss registry (reference: generalframework/loss/__init__.py:6-16)."""
 from .loss import CrossEntropyLoss2d, CrossEntropyDiceLoss2d, DiceLoss, JSD_2D, KL_Divergence_2D, Entropy_2D, softmax_channels  # noqa: F401
+from .loss import BoundaryLoss, CrossEntropyBoundaryLoss2d, signed_distance_map  # noqa: F401
 from . import loss as _loss_mod
 
 __all__ = ['get_loss_fn']
@@ -7,6 +8,8 @@ __all__ = ['get_loss_fn']
 LOSS = {'cross_entropy': CrossEntropyLoss2d,
         'dice': DiceLoss,
         'ce_dice': CrossEntropyDiceLoss2d,
+        'boundary': BoundaryLoss,
+        'ce_boundary': CrossEntropyBoundaryLoss2d,
         'jsd': JSD_2D}
 
 

@@ -242,6 +242,147 @@ class DiceLoss(CrossEntropyDiceLoss2d):
         super().__init__(None, 0.0, 1.0, classes, smooth, per_image, ignore_index)
 
 
+def _spacing2(spacing, who):
+    try:
+        sy, sx = (float(s) for s in spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"dct_amd {who}: spacing must be two numbers (sy, sx), got {spacing!r}")
+    if not (0.0 < sy < float('inf') and 0.0 < sx < float('inf')):
+        raise ValueError(f"dct_amd {who}: spacing must be positive and finite, got {spacing!r}")
+    return sy, sx
+
+
+def _class_list(classes, who):
+    """``classes`` as a sorted list of distinct ints, None for all; empty and negative are refused here, ``>= C`` by ``_class_mask``."""
+    if classes is None:
+        return None
+    classes = sorted({int(c) for c in classes})
+    if not classes:
+        raise ValueError(f"dct_amd {who}: classes is empty")
+    if classes[0] < 0:
+        raise ValueError(f"dct_amd {who}: class {classes[0]} is negative")
+    return classes
+
+
+def _class_mask(classes, C, who):
+    if classes is not None and classes[-1] >= C:
+        raise ValueError(f"dct_amd {who}: class {classes[-1]} outside [0, {C})")
+    return (1 << C) - 1 if classes is None else sum(1 << c for c in classes)
+
+
+def signed_distance_map(gt, C, classes=None, spacing=(1., 1.)):
+    """The signed Euclidean distance maps of the boundary loss (Kervadec's ``one_hot2dist``) on the device: ``gt`` [B, H, W] or
+    [B, 1, H, W] class indices -> fp32 [B, C, H, W] (the logical view of the NHWC buffer the kernels write), per image and class the
+    distance to the class's contour in units of ``spacing`` = (sy, sx), negative inside (the rule: include/dct.h).  A class that is
+    absent from an image, fills it, or is not in ``classes`` (None: all) has an all-zero map.  Not differentiable."""
+    who = "signed_distance_map"
+    mask_classes = _class_list(classes, who)
+    _class_mask(mask_classes, C, who)
+    if not gt.is_cuda:
+        raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+    if gt.dim() == 4 and gt.shape[1] == 1:
+        gt = gt[:, 0]
+    assert gt.dim() == 3, gt.shape
+    with torch.no_grad():
+        return _nchw(K.signed_distance(gt, C, mask_classes, _spacing2(spacing, who)))
+
+
+class _BoundaryFn(torch.autograd.Function):
+    """The boundary term on dct_boundary_*; ``phi``: the fp32 NHWC map [B, H, W, C]."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, phi, mask, ignore_index):
+        lp = _pc(logits)
+        if lp.data_ptr() % 16:              # (a dense view that starts inside its storage: the kernels read 16 bytes at a time)
+            lp = lp.clone()
+        t = _targets(targets)
+        out = K.boundary_fwd(lp, t, phi, lp.shape[3], mask, ignore_index)
+        ctx.save_for_backward(lp, t, phi, out)
+        ctx.mask, ctx.ignore_index = mask, ignore_index
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lp, t, phi, out = ctx.saved_tensors
+        dl = torch.empty_like(lp)
+        g = g.to(torch.float32).contiguous()
+        K.boundary_bwd(lp, t, phi, lp.shape[3], out[1:2], dl, class_mask=ctx.mask, gscale=g, ignore_index=ctx.ignore_index)
+        return _nchw(dl), None, None, None, None
+
+
+class BoundaryLoss(nn.Module):
+    """Boundary loss of Kervadec et al.: the mean over counted pixels and ``classes`` of softmax x signed distance to the ground-truth
+    contour (the rule: include/dct.h, dct_boundary_*).  ``classes``: the class indices of the mean (None: all; the paper leaves the
+    background out: pass ``range(1, C)``); ``spacing`` = (sy, sx): the pixel size the distances are measured in.
+
+    ``forward(outputs, targets, dist_map=None)``: a caller that holds the map of this batch (``signed_distance_map`` under the same
+    ``classes`` and ``spacing``) passes it and the distance chain is skipped; otherwise the map is computed from ``targets`` on the
+    spot, on the device.  The loss can be negative; it is meant to be added to a regional loss (``CrossEntropyBoundaryLoss2d``)."""
+
+    def __init__(self, classes=None, spacing=(1., 1.), ignore_index=255):
+        super().__init__()
+        self.classes = _class_list(classes, type(self).__name__)
+        self.spacing = _spacing2(spacing, type(self).__name__)
+        self.ignore_index = ignore_index
+
+    def _phi(self, outputs, targets, dist_map):
+        """The fp32 NHWC map [B, H, W, C] of this batch: ``dist_map`` (logical [B, C, H, W]) if given, else computed from ``targets``."""
+        B, C, H, W = outputs.shape
+        if dist_map is None:
+            with torch.no_grad():
+                return K.signed_distance(targets, C, self.classes, self.spacing)
+        assert tuple(dist_map.shape) == (B, C, H, W), (dist_map.shape, outputs.shape)
+        phi = _pc(dist_map.detach())
+        return phi.clone() if phi.data_ptr() % 16 else phi
+
+    def forward(self, outputs, targets, dist_map=None):
+        assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
+        mask = _class_mask(self.classes, outputs.shape[1], type(self).__name__)
+        if not outputs.is_cuda:
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        return _BoundaryFn.apply(outputs, targets, self._phi(outputs, targets, dist_map), mask, self.ignore_index)
+
+
+class CrossEntropyBoundaryLoss2d(_ClassWeighted):
+    """``ce_coef`` * class-weighted mean cross entropy (``CrossEntropyLoss2d(weight)``) + ``boundary_coef`` * ``BoundaryLoss(classes,
+    spacing)``, composed of the two criteria's own kernels.  A coefficient of exactly 0 removes its term (a NaN cross entropy then does
+    not reach the total).  ``boundary_coef`` is a plain attribute read at every call: the paper's rebalancing schedule is the user
+    raising it per epoch.  After a call ``last_terms`` holds the two device scalars (ce, boundary), None for a removed term; nothing
+    synchronises."""
+
+    def __init__(self, weight=None, ce_coef=1.0, boundary_coef=0.01, classes=None, spacing=(1., 1.), ignore_index=255):
+        super().__init__()
+        self._set_weight(weight)
+        self.ce_coef, self.boundary_coef = float(ce_coef), float(boundary_coef)
+        self.boundary = BoundaryLoss(classes, spacing, ignore_index)
+        self.ignore_index = ignore_index
+        self.last_terms = None
+
+    classes = property(lambda self: self.boundary.classes)
+    spacing = property(lambda self: self.boundary.spacing)
+
+    def forward(self, outputs, targets, dist_map=None):
+        assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
+        _class_mask(self.boundary.classes, outputs.shape[1], type(self).__name__)
+        if self.ce_coef == 0.0 and self.boundary_coef == 0.0:
+            raise ValueError(f"dct_amd {type(self).__name__}: ce_coef and boundary_coef are both 0")
+        if not outputs.is_cuda:
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        w = self.device_weight(outputs.device, outputs.shape[1])
+        ce = bd = None
+        if self.ce_coef != 0.0:
+            ce = (_CEFn.apply(outputs, targets, self.ignore_index) if w is None
+                  else _CEWeightedFn.apply(outputs, targets, w, K.CE_MEAN, self.ignore_index))
+        if self.boundary_coef != 0.0:
+            bd = self.boundary(outputs, targets, dist_map)
+        self.last_terms = (None if ce is None else ce.detach(), None if bd is None else bd.detach())
+        if bd is None:
+            return ce if self.ce_coef == 1.0 else self.ce_coef * ce
+        if ce is None:
+            return self.boundary_coef * bd
+        return self.ce_coef * ce + self.boundary_coef * bd
+
+
 class _SoftmaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits):

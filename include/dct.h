@@ -333,6 +333,42 @@ int dct_ce_dice_step(const float* logits, const int64_t* targets, int B, int64_t
                      const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, float* out4,
                      float* dice_gc, float* sums, const float* gscale, float gmul, float* dlogits, int accumulate, void* workspace,
                      size_t workspace_bytes, dct_stream stream);
+/* Boundary loss (Kervadec et al., "Boundary loss for highly unbalanced segmentation"): the softmax weighted by the signed Euclidean
+ * distance to the ground-truth contour, here on the device from the targets to the gradient.
+ * Targets t [B][H][W] int64; classes 0..C-1, 2 <= C <= 8; spacing (sy, sx), both > 0 and finite; G_c = {t == c}.  A target outside [0, C)
+ * is in no class: it is background for every c (that covers ignore_index; the rule of dct_hausdorff).
+ * Distances are per image (2-D), centre to centre: d2(p, q) = (sy dy)^2 + (sx dx)^2.  The signed distance phi_c:
+ *   p not in G_c:  phi_c(p) = + min_{q in G_c} sqrt(d2(p, q))
+ *   p in G_c:      phi_c(p) = -(min_{q not in G_c} sqrt(d2(p, q)) - 1)
+ *   The "- 1" is the one of Kervadec's one_hot2dist, kept literally, in units of the spacing.
+ *   phi_c = 0 over the whole image when G_c is empty in that image or fills it (no contour inside the image: one_hot2dist writes zeros
+ *   for an absent class, scipy's answer for a full mask is arbitrary), or when c is not in class_mask.
+ * dct_signed_distance writes phi [B][H][W][C] fp32, the layout of the logits -- EVERY element, the zeros included: the caller clears
+ *   nothing.  Exact separable transform (csrc/surface.hip): with unit spacing every squared distance is an integer below 2^24 and the
+ *   root is the correctly rounded one, so phi is the float64 result rounded once; no float atomics, bit-identical from run to run.
+ *   targets, phi and workspace 16-byte aligned.  dct_signed_distance_workspace_bytes returns 0 for a shape dct_signed_distance refuses.
+ * The loss reads s = softmax(x_p) of logits [pixels][C] fp32.  A pixel is counted as in dct_ce_weighted_*: t != ignore_index &&
+ * 0 <= t < C; N = the number of counted pixels; K = the number of bits of class_mask below C:
+ *   L = (1 / (N K)) sum_{p counted} sum_{c in mask} s_c(p) phi_c(p);     N = 0: L = 0 and every gradient is exactly 0.
+ *   (With nothing ignored: one_hot2dist followed by SurfaceLoss's .mean() over B x K x H x W.)
+ * dct_boundary_fwd writes out2 = {L, N}; its workspace is dct_loss_workspace_bytes.
+ * Gradient, with g = gscale[0] * gmul (gscale nullable = 1, as in dct_ce_bwd):
+ *   q_c = m_c phi_c(p) / (N K),  m_c = 1 for the classes of the mask, else 0;
+ *   dlogits[p][c] (=|+=) g s_c (q_c - sum_k s_k q_k).
+ *   Uncounted pixels get exactly 0 (exactly the old value under accumulate).  All sums are folded in one fixed order: bit-identical from
+ *   run to run.  logits, phi and dlogits 16-byte aligned (the kernels read them 16 bytes at a time).
+ * DCT_ERR_BAD_ARG: a null pointer, a spacing that is not positive and finite, a class_mask with no bit below C, pixels < 1 or B / H / W < 1,
+ *   a misaligned pointer; DCT_ERR_UNSUPPORTED: C outside 2..8, H or W > 1024, B > 65535; DCT_ERR_WORKSPACE: too little workspace.
+ *   Every check runs before the first launch.
+ * Out of scope: 3-D maps with the batch as a volume, a fused fwd + bwd step, probabilities as input. */
+size_t dct_signed_distance_workspace_bytes(int B, int H, int W, int C);
+int dct_signed_distance(const int64_t* targets /*[B][H][W]*/, int B, int H, int W, int C, int class_mask, float sy, float sx,
+                        float* phi /*[B][H][W][C]*/, void* workspace, size_t workspace_bytes, dct_stream stream);
+int dct_boundary_fwd(const float* logits, const int64_t* targets, const float* phi, int64_t pixels, int C, int ignore_index,
+                     int class_mask, float* out2 /*{L, N}*/, void* workspace, size_t workspace_bytes, dct_stream stream);
+int dct_boundary_bwd(const float* logits, const int64_t* targets, const float* phi, int64_t pixels, int C, int ignore_index,
+                     int class_mask, const float* count /*out2 + 1*/, const float* gscale, float gmul, float* dlogits, int accumulate,
+                     dct_stream stream);
 int dct_softmax_fwd(const float* logits, float* probs, int64_t pixels, int C, dct_stream stream);
 /* dlogits (=|+=) p * (dprobs - sum_c dprobs*p) */
 int dct_softmax_bwd(const float* probs, const float* dprobs, float* dlogits, int64_t pixels, int C,
