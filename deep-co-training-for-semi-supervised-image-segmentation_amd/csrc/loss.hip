@@ -774,6 +774,196 @@ __global__ __launch_bounds__(256) void jsd_step_kernel(PtrPack pk, PtrPack probs
   block_partial2(sum, 0.f, partial);
 }
 
+// ---- pseudo-label consistency: cross pseudo supervision / voted pseudo-label (the rule: include/dct.h, dct_pl_*) --------------------
+// The teachers of one pixel, as constants.  cross: every view j names k_j = first maximum of p_j and is kept when p_j[k_j] >= tau;
+// ensemble: one teacher, the first maximum of the fp32 sums taken in view order, kept when sum[k] * invS >= tau.  Out: cnt[c] = the kept
+// teachers that name class c, own[s] = the class view s named itself as a kept teacher (-1: none; a view is no teacher of itself), so
+// that student s meets n = cnt[c] - (own[s] == c) teacher terms of class c.  Returns the number of kept teachers.
+// The mode is a uniform branch (a kernel argument), not a template parameter: the two derivations are a few compares per pixel of an
+// HBM-bound pass, and everything behind them (logs, gradients, stores) is one code path.
+template <int C, int SMAX>
+__device__ __forceinline__ int pl_teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, float (&cnt)[C], int (&own)[SMAX]) {
+#pragma clang fp contract(off)    // the sums and q are formed from the ROUNDED probabilities, as the rule states them: no product of softmax_px may fold into an add here
+  int kept = 0;
+#pragma unroll
+  for (int c = 0; c < C; ++c) cnt[c] = 0.f;
+  if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      own[s] = -1;
+      if (s < S) {
+        float bv = p[s][0];
+        int best = 0;
+#pragma unroll
+        for (int c = 1; c < C; ++c) if (p[s][c] > bv) { bv = p[s][c]; best = c; }
+        if (bv >= tau) {
+          own[s] = best;
+          ++kept;
+#pragma unroll
+          for (int c = 0; c < C; ++c) cnt[c] = cnt[c] + (best == c ? 1.f : 0.f);
+        }
+      }
+    }
+  } else {
+    float sum[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) sum[c] = p[0][c];
+#pragma unroll
+    for (int s = 1; s < SMAX; ++s) {
+      own[s] = -1;
+      if (s < S) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) sum[c] = sum[c] + p[s][c];
+      }
+    }
+    own[0] = -1;
+    float bv = sum[0];
+    int best = 0;
+#pragma unroll
+    for (int c = 1; c < C; ++c) if (sum[c] > bv) { bv = sum[c]; best = c; }   // on the unscaled sums: scaling cannot create a tie
+    const float q = bv * invS;
+    if (q >= tau) {
+      kept = 1;
+#pragma unroll
+      for (int c = 0; c < C; ++c) cnt[c] = best == c ? 1.f : 0.f;
+    }
+  }
+  return kept;
+}
+// student s of one pixel: returns sum_c n * -log(p[c] + eps) over its n = cnt[c] - (own == c) teacher terms (the pixel's map value is wgt
+// times the sum over s) and d[c] = d map / d p[c] = -(wgt n) / (p[c] + eps).  No term: no log, and d[c] = 0 exactly.
+template <int C>
+__device__ __forceinline__ float pl_student(const float (&p)[C], const float (&cnt)[C], int own, float eps, float wgt, float (&d)[C]) {
+  float a = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const float n = cnt[c] - (own == c ? 1.f : 0.f);
+    d[c] = 0.f;
+    if (n != 0.f) {
+      const float pe = p[c] + eps;
+      a -= n * logf(pe);
+      d[c] = -(wgt * n) / pe;
+    }
+  }
+  return a;
+}
+// kden: the teacher terms of a pixel (cross: S, ensemble: 1); wgt: 1 / (S (S - 1)) resp. 1 / S
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void pl_map_fwd_kernel(PtrPack pk, int S, int teacher, float tau, float eps, float invS, float wgt, float kden,
+                                                          float* map, float* keptmap, long long P) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float p[SMAX][C], cnt[C];
+    int own[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
+    }
+    const int kept = pl_teachers<C, SMAX>(p, S, teacher, tau, invS, cnt, own);
+    float a = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float d[C];
+        a += pl_student<C>(p[s], cnt, own[s], eps, wgt, d);
+      }
+    }
+    map[pix] = wgt * a;
+    if (keptmap) keptmap[pix] = (float)kept / kden;
+  }
+}
+// dprobs_s = dmap[pix] * d map / d p_s, the teachers recomputed from the probabilities
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void pl_map_bwd_kernel(PtrPack pk, int S, int teacher, float tau, float eps, float invS, float wgt,
+                                                          const float* dmap, long long P) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float p[SMAX][C], cnt[C];
+    int own[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
+    }
+    pl_teachers<C, SMAX>(p, S, teacher, tau, invS, cnt, own);
+    const float gp = dmap[pix];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float d[C];
+        pl_student<C>(p[s], cnt, own[s], eps, wgt, d);
+#pragma unroll
+        for (int c = 0; c < C; ++c) d[c] = d[c] != 0.f ? gp * d[c] : 0.f;     // a masked entry is 0 whatever dmap holds
+        store_px<C>(pk.out[s], pix, d, false);
+      }
+    }
+  }
+}
+// The step's consistency section from logits in one pass, on jsd_step_kernel's structure and grid: block partials of (map value, kept
+// teachers), the S softmax maps (softmax_fwd_kernel's bits) and the S logit gradients g p (d - sum_c' d p) (jsd_bwd_kernel<_, true>'s
+// form; accumulate: round, then add).  One pixel per trip, every load of the pixel issued before its first store.
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void pl_step_kernel(PtrPack pk, PtrPack probs, int S, int teacher, float tau, float eps, float invS, float wgt,
+                                                       long long P, const float* gscale, float gmul, int acc, int want_grad, float* partial) {
+  const float g = (gscale ? gscale[0] : 1.f) * gmul / (float)P;
+  float sum = 0.f, keptsum = 0.f;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float x[SMAX][C], old[SMAX][C];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        load_px<C>(pk.in[s], pix, x[s]);
+        if (want_grad && acc) load_px<C>(pk.out[s], pix, old[s]);
+      }
+    }
+    float p[SMAX][C], cnt[C];
+    int own[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        softmax_px<C>(x[s], p[s]);
+        if (probs.out[s]) store_px<C>(probs.out[s], pix, p[s], false);
+      }
+    }
+    keptsum += (float)pl_teachers<C, SMAX>(p, S, teacher, tau, invS, cnt, own);
+    float a = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float d[C];
+        a += pl_student<C>(p[s], cnt, own[s], eps, wgt, d);
+        if (want_grad) {
+          float dot = 0.f;
+#pragma unroll
+          for (int c = 0; c < C; ++c) dot += d[c] * p[s][c];
+          float o[C];
+#pragma unroll
+          for (int c = 0; c < C; ++c) o[c] = g * p[s][c] * (d[c] - dot);
+          if (acc) {
+#pragma clang fp contract(off)    // store_px's accumulate: round, then add
+#pragma unroll
+            for (int c = 0; c < C; ++c) o[c] = o[c] + old[s][c];
+          }
+          store_px<C>(pk.out[s], pix, o, false);
+        }
+      }
+    }
+    sum += wgt * a;
+  }
+  block_partial2(sum, keptsum, partial);
+}
+// finalize_kernel's fold with a denominator of its own for each sum: out[0] = mean map value, out[1] = kept teacher terms / all of them
+// (the kept counts are whole numbers held in floats: exact up to 2^24 terms)
+__global__ __launch_bounds__(256) void pl_finalize_kernel(const float* partial, int blocks, float* out, float denom_a, float denom_b) {
+  __shared__ float sa[256], sb[256];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
+  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = sa[0] / denom_a; out[1] = sb[0] / denom_b; }
+}
+
 // ---- KL(y || p) -----------------------------------------------------------------------------------
 template <int C, bool FROM_LOGITS>
 __global__ __launch_bounds__(256) void kl_fwd_kernel(const float* pin, const float* yin, long long P, float eps, float* map, float* partial) {
@@ -1241,6 +1431,62 @@ extern "C" int dct_jsd_logits_step(const float* const* logits, int S, int64_t pi
   else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (jsd_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
   else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (jsd_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
   DCT_LAUNCH(DCT_PROF_LOSS, finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out1, 0, (float)pixels, 0);
+  return dct_check_launch();
+}
+
+// ---- pseudo-label consistency -------------------------------------------------------------------------
+namespace {
+// the rule's host-side constants: 1 / S as the ensemble confidence scales by it, the weight of one teacher term in the map, the teacher
+// terms of a pixel
+struct PlRule { float invS, wgt, kden; };
+bool pl_rule(int S, int teacher, float tau, float eps, PlRule& r) {
+  if (teacher != DCT_PL_CROSS && teacher != DCT_PL_ENSEMBLE) return false;
+  if (S < (teacher == DCT_PL_CROSS ? 2 : 1) || S > MAXS) return false;
+  if (!(tau >= 0.f) || !(eps > 0.f)) return false;          // (a NaN fails both)
+  r.invS = 1.f / (float)S;
+  r.wgt = teacher == DCT_PL_CROSS ? 1.f / (float)(S * (S - 1)) : r.invS;
+  r.kden = teacher == DCT_PL_CROSS ? (float)S : 1.f;
+  return true;
+}
+}  // namespace
+
+extern "C" int dct_pl_map_fwd(const float* const* probs, int S, int teacher, float tau, float eps, float* map, float* kept,
+                              int64_t pixels, int C_, dct_stream stream) {
+  PtrPack pk;
+  PlRule r;
+  if (!pl_rule(S, teacher, tau, eps, r) || !fill_pack(pk, probs, nullptr, S) || !map || pixels < 1) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = wide_grid(pixels);
+  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_map_fwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, eps, r.invS, r.wgt, r.kden, map, kept, (long long)pixels)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_map_fwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, eps, r.invS, r.wgt, r.kden, map, kept, (long long)pixels)); }
+  return dct_check_launch();
+}
+extern "C" int dct_pl_map_bwd(const float* const* probs, int S, int teacher, float tau, float eps, const float* dmap, float* const* dprobs,
+                              int64_t pixels, int C_, dct_stream stream) {
+  PtrPack pk;
+  PlRule r;
+  if (!pl_rule(S, teacher, tau, eps, r) || !dprobs || !fill_pack(pk, probs, dprobs, S) || !dmap || pixels < 1) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = wide_grid(pixels);
+  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_map_bwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, eps, r.invS, r.wgt, dmap, (long long)pixels)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_map_bwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, eps, r.invS, r.wgt, dmap, (long long)pixels)); }
+  return dct_check_launch();
+}
+extern "C" int dct_pl_logits_step(const float* const* logits, int S, int teacher, float tau, float eps, int64_t pixels, int C_, float* out2,
+                                  float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
+                                  void* workspace, size_t workspace_bytes, dct_stream stream) {
+  PtrPack pk, pp;
+  PlRule r;
+  if (!pl_rule(S, teacher, tau, eps, r) || !fill_pack(pk, logits, dlogits, S) || !out2 || pixels < 1) return DCT_ERR_BAD_ARG;
+  for (int s = 0; s < MAXS; ++s) { pp.in[s] = nullptr; pp.out[s] = (probs && s < S) ? probs[s] : nullptr; }
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);
+  const int want = dlogits ? 1 : 0;
+  if (S <= 2) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, 2>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * r.kden);
   return dct_check_launch();
 }
 

@@ -1,6 +1,7 @@
 """Loss registry (reference: generalframework/loss/__init__.py:6-16)."""
 from .loss import CrossEntropyLoss2d, CrossEntropyDiceLoss2d, DiceLoss, JSD_2D, KL_Divergence_2D, Entropy_2D, softmax_channels  # noqa: F401
 from .loss import BoundaryLoss, CrossEntropyBoundaryLoss2d, signed_distance_map  # noqa: F401
+from .loss import PseudoLabel_2D, CrossPseudoSupervision_2D, EnsemblePseudoLabel_2D  # noqa: F401
 from . import loss as _loss_mod
 
 __all__ = ['get_loss_fn']
@@ -10,7 +11,9 @@ LOSS = {'cross_entropy': CrossEntropyLoss2d,
         'ce_dice': CrossEntropyDiceLoss2d,
         'boundary': BoundaryLoss,
         'ce_boundary': CrossEntropyBoundaryLoss2d,
-        'jsd': JSD_2D}
+        'jsd': JSD_2D,
+        'cps': CrossPseudoSupervision_2D,
+        'pseudo_label': EnsemblePseudoLabel_2D}
 
 
 def get_loss_fn(name: str, **kwargs):

@@ -487,3 +487,87 @@ class JSD_2D(nn.Module):
             for inprob in input:
                 assert _simplex(inprob, 1)
         return _JSDMapFn.apply(*input)
+
+
+class _PLMapFn(torch.autograd.Function):
+    """The pseudo-label consistency map on dct_pl_map_*; ``rule``: ``PseudoLabel_2D.launch_args()``.  Returns the [B,H,W] map and, without a
+    gradient, the per-pixel kept map.  Nothing but the inputs is saved: the backward recomputes the teachers."""
+
+    @staticmethod
+    def forward(ctx, rule, *probs):
+        pps = [_pc(p) for p in probs]
+        ctx.save_for_backward(*pps)
+        ctx.rule = rule
+        out, kept = K.pl_map_fwd(pps, pps[0].shape[3], **rule)
+        kept = kept.view(pps[0].shape[:3])
+        ctx.mark_non_differentiable(kept)
+        return out.view(pps[0].shape[:3]), kept
+
+    @staticmethod
+    def backward(ctx, g, _):
+        pps = list(ctx.saved_tensors)
+        dps = K.pl_map_bwd(pps, g.to(torch.float32).contiguous().view(-1), pps[0].shape[3], **ctx.rule)
+        return (None,) + tuple(_nchw(d) for d in dps)
+
+
+class PseudoLabel_2D(nn.Module):
+    """Hard pseudo-label consistency of S views (the rule: include/dct.h, dct_pl_*), with ``JSD_2D``'s call shape: a list of [B,C,H,W]
+    probabilities in, a [B,H,W] map out, whose mean over ALL pixels is the loss.  ``teacher='cross'``: cross pseudo supervision, every
+    view learns the argmax of every other view (2 or more views); ``teacher='ensemble'``: every view learns the argmax of the summed
+    probabilities.  ``threshold``: a teacher whose confidence (its maximum probability; for the ensemble the mean of the views') is below
+    it is masked out; 0 keeps every teacher.  Teachers are constants: no gradient flows through argmax, confidence or mask.  After a
+    call ``last_kept`` is a device scalar, the kept fraction of the teacher terms (nothing synchronises)."""
+
+    def __init__(self, teacher='cross', threshold=0.0, eps=1e-10):
+        super().__init__()
+        name = type(self).__name__
+        if teacher not in K.PL_TEACHERS:
+            raise ValueError(f"dct_amd {name}: teacher must be 'cross' or 'ensemble', got {teacher!r}")
+        self.teacher = teacher
+        try:
+            self.threshold, self.eps = float(threshold), float(eps)
+        except (TypeError, ValueError):
+            raise ValueError(f"dct_amd {name}: threshold and eps must be numbers, got {threshold!r}, {eps!r}")
+        if not (0.0 <= self.threshold <= float('inf')):
+            raise ValueError(f"dct_amd {name}: threshold must be >= 0, got {threshold}")
+        # (eps is handed to the kernels as fp32: one that rounds to 0 there would put log(0) back)
+        if not (0.0 < self.eps < float('inf')) or float(torch.tensor(self.eps, dtype=torch.float32)) == 0.0:
+            raise ValueError(f"dct_amd {name}: eps must be finite and > 0 in fp32, got {eps}")
+        self.last_kept = None
+
+    def launch_args(self):
+        """The keyword arguments of hip_ops.pl_* (and what a captured step is valid for)."""
+        return dict(teacher=K.PL_TEACHERS[self.teacher], tau=self.threshold, eps=self.eps)
+
+    def min_views(self):
+        return 2 if self.teacher == 'cross' else 1
+
+    def forward(self, input: List[torch.Tensor]):
+        input = list(input)
+        name = type(self).__name__
+        if len(input) < self.min_views():
+            raise ValueError(f"dct_amd {name}: teacher='{self.teacher}' needs at least {self.min_views()} views, got {len(input)}")
+        if len(input) > MAX_VIEWS:
+            raise ValueError(f"dct_amd {name} handles up to {MAX_VIEWS} views per call, got {len(input)}")
+        if not all(p.is_cuda for p in input):
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        if DEBUG_ASSERTS:
+            for inprob in input:
+                assert _simplex(inprob, 1)
+        out, kept = _PLMapFn.apply(self.launch_args(), *input)
+        self.last_kept = kept.mean()
+        return out
+
+
+class CrossPseudoSupervision_2D(PseudoLabel_2D):
+    """Cross pseudo supervision (Chen et al., CVPR 2021): ``PseudoLabel_2D(teacher='cross')``."""
+
+    def __init__(self, threshold=0.0, eps=1e-10):
+        super().__init__('cross', threshold, eps)
+
+
+class EnsemblePseudoLabel_2D(PseudoLabel_2D):
+    """The voted pseudo-label with a confidence threshold: ``PseudoLabel_2D(teacher='ensemble')``."""
+
+    def __init__(self, threshold=0.0, eps=1e-10):
+        super().__init__('ensemble', threshold, eps)

@@ -115,9 +115,9 @@ class ExecutionPlan:
 class _StepContext(object):
     """What one issue of the step carries from its forward passes to its optimizers; dropped when the step returns (the join closure
     holds this step's streams, the pass buffers' owners its tapes)."""
-    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice")
+    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice", "pl")
 
-    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None):
+    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None, pl=None):
         self.sched, self.route = sched, route
         # the gradient exchange as far as it is issued from inside the step (between two graphs it is the replay's business)
         self.sync = grad_sync if any(e in ("model", "buckets") for e in route.exchange) else None
@@ -132,6 +132,7 @@ class _StepContext(object):
         self.ignore = ignore
         self.ce_weight = ce_weight          # the supervised criterion's fp32 class weights on the device, or None (all ones)
         self.ce_dice = ce_dice              # a Dice / CE + Dice criterion's launch arguments (CrossEntropyDiceLoss2d.launch_args), or None
+        self.pl = pl                        # a pseudo-label consistency criterion's launch arguments (PseudoLabel_2D.launch_args), or None: JSD
 
     def on(self, streams, i):
         """Model i's stream of ``streams`` as the current one (no-op without streams, or for the joint backward of the generic step)."""
@@ -294,11 +295,16 @@ class CoTrainer(Trainer):
         gpu = self.device.type == 'cuda'
         fused_criteria = False
         if gpu:
-            from ..loss.loss import CrossEntropyDiceLoss2d, CrossEntropyLoss2d, DiceLoss, JSD_2D
+            from ..loss.loss import (CrossEntropyDiceLoss2d, CrossEntropyLoss2d, CrossPseudoSupervision_2D, DiceLoss,
+                                     EnsemblePseudoLabel_2D, JSD_2D, PseudoLabel_2D)
             sup = self.criterions['sup']
             # (class weights, Dice and CE + Dice ride the fused kernels; the sum and the per-pixel map go through the module: the generic step)
             fused_sup = (type(sup) is CrossEntropyLoss2d and sup.reduction == 'mean') or type(sup) in (CrossEntropyDiceLoss2d, DiceLoss)
-            fused_criteria = fused_sup and type(self.criterions['jsd']) is JSD_2D
+            cons = self.criterions['jsd']
+            # (the pseudo-label criteria ride dct_pl_logits_step; cross pseudo supervision of a single network goes through the module, which refuses it)
+            fused_cons = type(cons) is JSD_2D or (type(cons) in (PseudoLabel_2D, CrossPseudoSupervision_2D, EnsemblePseudoLabel_2D)
+                                                  and len(nets) >= cons.min_views())
+            fused_criteria = fused_sup and fused_cons
         if self._group_max is None and gpu and all(n.plan_net and n.supports_pass_groups for n in nets):
             from .. import hip_ops as K
             self._group_max = K.group_max()
@@ -464,9 +470,14 @@ class CoTrainer(Trainer):
 
     def _jsd(self, ctx, lps, dl_outs):
         """Value, the S softmax maps and the S logit gradients in ONE pass over the logits (dct_jsd_logits_step: bit for bit the five
-        separate launches).  -> (value, NCHW softmax maps)."""
+        separate launches; dct_pl_logits_step when the consistency criterion is a pseudo-label one, whose ``last_kept`` is set to the
+        kept fraction on the device).  -> (value, NCHW softmax maps)."""
         from .. import hip_ops as K
         from ..loss.loss import _nchw
+        if ctx.pl is not None:
+            out2, probs = K.pl_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot, **ctx.pl)
+            self.criterions['jsd'].last_kept = out2[1]
+            return out2[0], [_nchw(p_) for p_ in probs]
         jsd1, probs = K.jsd_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot)
         return jsd1[0], [_nchw(p_) for p_ in probs]
 
@@ -612,10 +623,11 @@ class CoTrainer(Trainer):
         ``lam_dev`` (float32[2] device tensor holding lambda_cot, lambda_adv): the loss weights are then read on the
         device, as a captured graph needs."""
         nets = [s.torchnet for s in self.segmentators]
-        sup = self.criterions['sup']
+        sup, cons = self.criterions['sup'], self.criterions['jsd']
         ctx = _StepContext(self._sched, route, self.grad_sync, (float(self.cot_scheduler.value), float(self.adv_scheduler.value)),
                            lam_dev, sup.ignore_index, sup.device_weight(self.device, self.C),
-                           sup.launch_args(self.C) if hasattr(sup, "launch_args") else None)
+                           sup.launch_args(self.C) if hasattr(sup, "launch_args") else None,
+                           cons.launch_args() if hasattr(cons, "launch_args") else None)
         streams = self._streams() if route.model_streams else None
         if route.kind in ("wide", "wide_grouped"):
             return self._run_step_wide(ctx, lab, unl, train_adv, adv_choice, nets)

@@ -95,6 +95,10 @@ class StepGraphCache(object):
         rule = sup.launch_args(tr.C) if hasattr(sup, "launch_args") else None
         sig.append((sup.ignore_index, w.data_ptr() if w is not None else 0, type(sup).__name__,
                     tuple(sorted(rule.items())) if rule is not None else None))
+        # the consistency criterion: a pseudo-label one's type and launch arguments (teacher, threshold, eps: another value is another
+        # capture); JSD_2D has none to tell apart, its entry is a constant
+        cons = tr.criterions['jsd']
+        sig.append((type(cons).__name__, tuple(sorted(cons.launch_args().items()))) if hasattr(cons, "launch_args") else None)
         return tuple(sig)
 
     def _lam(self) -> torch.Tensor:

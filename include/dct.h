@@ -396,6 +396,41 @@ int dct_jsd_logits_bwd(const float* const* logits, int S, int64_t pixels, int C,
 int dct_jsd_logits_step(const float* const* logits, int S, int64_t pixels, int C, float* out1, float* const* probs,
                         const float* gscale, float gmul, float* const* dlogits, int accumulate,
                         void* workspace, size_t workspace_bytes, dct_stream stream);
+/* ---- pseudo-label consistency: every view is trained on the hard pseudo-labels of the others ----
+ * Per pixel: S views (1 <= S <= 8) with probabilities p_s[0..C), a confidence threshold tau >= 0 and eps > 0 (1e-10 as for KL).
+ * Teachers are constants: no gradient flows through an argmax, a confidence or a mask.  All comparisons and the sums below are fp32.
+ *
+ * teacher = DCT_PL_CROSS (cross pseudo supervision, Chen et al. 2021), S >= 2
+ *   k_j = first maximum of p_j (dct_argmax's rule: v[c] > v[best], starting at 0)       q_j = p_j[k_j]       m_j = (q_j >= tau)
+ *   l_i = -(1 / (S - 1)) * sum_{j != i} m_j * log(p_i[k_j] + eps)                       map = (1 / S) * sum_i l_i
+ * teacher = DCT_PL_ENSEMBLE (the voted pseudo-label), S >= 1
+ *   sum[c] = ((p_0[c] + p_1[c]) + ...), added in view order        k = first maximum of sum (of the unscaled sums: scaling cannot create a tie)
+ *   q = sum[k] * (1.f / (float)S)       m = (q >= tau)             l_i = -m * log(p_i[k] + eps)              map = (1 / S) * sum_i l_i
+ * d map / d p_i[c]:   cross     -(1 / (S (S - 1))) * sum_{j != i, k_j == c} m_j / (p_i[c] + eps)
+ *                     ensemble  -(1 / S) * m * [k == c] / (p_i[c] + eps)
+ * The kernels evaluate both as  map = w * sum_i sum_c n_ic * -log(p_i[c] + eps)  and  d map / d p_i[c] = -(w * n_ic) / (p_i[c] + eps),  with n_ic the
+ * number of kept teacher terms of class c that student i meets and w = 1 / (S (S - 1)) resp. 1 / S; where n_ic = 0 nothing is evaluated and the
+ * entry is 0 exactly.
+ * From logits: p_s = softmax(x_s) with dct_softmax_fwd's bits; d / d x_i[c] = g * p_i[c] * (d_i[c] - sum_c' d_i[c'] p_i[c']), g = gscale[0] * gmul / P
+ * (gscale NULL: 1), the form of dct_jsd_logits_bwd.
+ * The mean is over all P pixels, never over the kept ones: with everything masked the loss and every gradient are exactly 0 and no 0/0 arises.
+ * kept = the fraction of teacher terms with m = 1: of the P * S terms (one per teacher view) for cross, of the P terms for ensemble; the kept
+ * map holds that fraction per pixel (kept teachers of the pixel / S resp. / 1).
+ * DCT_ERR_BAD_ARG: S outside the mode's range, an unknown mode, a negative or NaN tau, eps <= 0 (or NaN), null pointers, pixels < 1;
+ * DCT_ERR_UNSUPPORTED: C outside 2..8; DCT_ERR_WORKSPACE as dct_jsd_logits_step. */
+#define DCT_PL_CROSS 0
+#define DCT_PL_ENSEMBLE 1
+/* probs in (the module API: PseudoLabel_2D()(list_of_probs) -> [B,H,W] map); kept (nullable): the per-pixel kept map.  The backward
+ * recomputes the teachers from the probabilities: dprobs[s] = dmap[pix] * d map / d p_s. */
+int dct_pl_map_fwd(const float* const* probs, int S, int teacher, float tau, float eps, float* map, float* kept, int64_t pixels, int C,
+                   dct_stream stream);
+int dct_pl_map_bwd(const float* const* probs, int S, int teacher, float tau, float eps, const float* dmap, float* const* dprobs,
+                   int64_t pixels, int C, dct_stream stream);
+/* The step's consistency section in one pass over the logits + a finalize: out2 = (mean map value, kept fraction), probs[s] (nullable array /
+ * entries) = softmax of logits[s], dlogits[s] (nullable array: no gradients) (=|+=) the logit gradient; accumulate rounds, then adds. */
+int dct_pl_logits_step(const float* const* logits, int S, int teacher, float tau, float eps, int64_t pixels, int C, float* out2,
+                       float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
+                       void* workspace, size_t workspace_bytes, dct_stream stream);
 /* out[0] = mean_pix sum_c y*(log(y+eps)-log(p+eps)), p = softmax(p_logits), y = softmax(y_logits) */
 int dct_kl_logits_fwd(const float* p_logits, const float* y_logits, int64_t pixels, int C, float eps,
                       float* out1, void* workspace, size_t workspace_bytes, dct_stream stream);
