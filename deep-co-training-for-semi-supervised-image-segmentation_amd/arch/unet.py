@@ -221,6 +221,13 @@ class UNet(nn.Module):
         self._pack_key = None
         self._shadow_fresh = bool(shadow_fresh)
 
+    def repack_in_next_pass(self):
+        """The next pass launches the weight packs even if they are current (it is captured, and its replays follow weight updates).
+        Current packs were built from a current bf16 shadow, which that pass therefore need not rewrite."""
+        fp = self.flat_params
+        if fp.is_flat() and self._pack_key == (fp.version, self.compute_dtype, tuple(p._version for p in fp.params)):
+            self.mark_weights_updated(shadow_fresh=True)
+
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
         self.mark_weights_updated()         # (also drops "the bf16 shadow is fresh": it mirrors the weights before the call)

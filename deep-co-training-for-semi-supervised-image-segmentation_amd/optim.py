@@ -33,6 +33,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._import_steps = False
         self._flat_version = -1
         self._on_step = on_step
+        self._shadow_written = False    # what the last step() told on_step (repeat_step_callback)
         self.grad_scale = 1.0       # multiplies the gradients inside the update: the inverse loss scale of an fp16 step
         # {step count, lr} as float64[2] ON THE DEVICE: the kernel forms the bias corrections itself
         # (dct_adam_flat_dev), so step() has no per-step host scalar and can be replayed from a HIP graph.
@@ -135,12 +136,22 @@ class FusedAdam(torch.optim.Optimizer):
         shadow = f.ensure_shadow() if f.want_shadow else None
         hip_ops.adam_flat_dev(f.flat, f.gflat, self._m, self._v, state, self._dev_table, b1, b2, g["eps"],
                               g["weight_decay"], bf16_shadow=shadow, grad_scale=self.grad_scale)
+        self._shadow_written = shadow is not None
+        self._notify_step()
+        return loss
+
+    def _notify_step(self):
         if self._on_step is not None:
             try:
-                self._on_step(shadow_fresh=shadow is not None)
+                self._on_step(shadow_fresh=self._shadow_written)
             except TypeError:
                 self._on_step()
-        return loss
+
+    def repeat_step_callback(self):
+        """A captured graph containing step() was replayed: the weights (and the bf16 shadow) were rewritten on the device, but
+        no Python of step() ran.  Repeat the callback of the captured step() so that the network's host bookkeeping (UNet: the
+        key of its weight packs) does not take the packs of an evaluation between two replays for current.  Host attributes only."""
+        self._notify_step()
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)

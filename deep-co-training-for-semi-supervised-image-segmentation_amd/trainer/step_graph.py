@@ -13,7 +13,8 @@ What makes the step replayable -- nothing in a launch may depend on a per-step h
     backward kernels), refreshed only when a scheduler changes them;
   * the mini-batches are copied into static input buffers before each replay.
 Host-side counters that the captured Python code advanced once (optimizer step count, dropout calls) are advanced
-by the same amount after every replay.
+by the same amount after every replay, and the optimizers' "weights updated" callback to the networks is repeated (the UNet's
+weight packs are keyed on the host: an evaluation or an eager step of another shape between two replays must repack).
 
 A signature is captured after WARMUP eager steps (which are ordinary training steps), so lazy initialisation
 (flat buffers, weight packs, kernel attributes) has happened and the capture sees the steady-state sequence.
@@ -170,6 +171,13 @@ class StepGraphCache(object):
         if not first:                     # the capture pass already advanced the host counters once
             for (obj, name), d in zip(self._counters(), cap.counters):
                 setattr(obj, name, getattr(obj, name) + d)
+            # ... and told the networks that their weights were rewritten (UNet: drops the key of its weight packs).  The replay repacked
+            # in front of its forward passes and updated the weights behind them: without this, packs that an evaluation between two
+            # replays built (and keyed) would pass for current after the next replay -- in the following evaluation, and in an eager
+            # step of another shape.  Host attributes only: nothing is launched between two replays.
+            for seg in tr.segmentators:
+                if hasattr(seg.optimizer, "repeat_step_callback"):
+                    seg.optimizer.repeat_step_callback()
         o = cap.out
         # the small results are copied out (callers may keep them across steps) -- as ONE stacked tensor: one launch between two replays
         # instead of one per scalar; the prediction maps are the graph's static buffers, valid until the next step
@@ -192,6 +200,9 @@ class StepGraphCache(object):
         for seg in tr.segmentators:          # a fork nested inside a forked stream crashes hipStreamEndCapture (ROCm 7.2)
             if (tr.model_streams or tr._use_segments()) and hasattr(seg.torchnet, "wgrad_side_stream"):   # (nor may a segment end with unjoined work)
                 seg.torchnet.wgrad_side_stream = False
+        for seg in tr.segmentators:          # the replays follow weight updates: the captured pass must pack the weights even if an
+            if hasattr(seg.torchnet, "repack_in_next_pass"):     # evaluation has just done so (and a pass of its own would find them current)
+                seg.torchnet.repack_in_next_pass()
         torch.cuda.synchronize(tr.device)
         graph = torch.cuda.CUDAGraph()
         cap.graph_opt = None
