@@ -864,6 +864,51 @@ def confusion_counts(logits: List[torch.Tensor], gt: Optional[torch.Tensor] = No
     return cnt
 
 
+def calibration_counts(probs: List[torch.Tensor], gt: torch.Tensor, n_bins: int = 15, classes=None, with_ensemble: bool = False,
+                       from_logits: bool = False):
+    """probs: S fp32 tensors [B, pix, C] (or [B, H, W, C]), the probabilities (``from_logits``: the logits) of S views on one batch;
+    gt [B, pix] (or [B, H, W]) int64 -> (bins int64 [B, R, n_bins, 3], scores int64 [B, R, 2]), R = S + with_ensemble, the last rater
+    being the mean of the views' probabilities: per image, rater and confidence bin {pixels, correct pixels, sum of conf * 2^24}, and
+    per image and rater {sum of brier * 2^24, sum of nll * 2^24}, over the pixels whose gt lies in ``classes`` (None: every class)
+    (``dct_calibration_counts``, include/dct.h)."""
+    if not isinstance(probs, (list, tuple)) or len(probs) < 1:
+        raise ValueError("calibration_counts needs a list of at least one tensor")
+    shape = probs[0].shape
+    if len(shape) not in (3, 4) or any(t.shape != shape for t in probs):
+        raise ValueError(f"calibration_counts needs tensors of one shape [B, pix, C] or [B, H, W, C], got {[tuple(t.shape) for t in probs]}")
+    B, C_ = shape[0], shape[-1]
+    ppi = 1
+    for d in shape[1:-1]:
+        ppi *= d
+    if gt is None or gt.numel() != B * ppi:
+        raise ValueError(f"calibration_counts: gt {None if gt is None else tuple(gt.shape)} does not match the predictions {tuple(shape)}")
+    classes = list(range(min(C_, 32))) if classes is None else [int(c) for c in classes]
+    if any(not 0 <= c < C_ for c in classes):
+        raise ValueError(f"calibration_counts: classes {classes} must lie in [0, {C_})")
+    mask = sum(1 << c for c in set(classes))
+
+    def dense(t, dtype):
+        ptr(t)                              # (refuses a CPU tensor before anything is copied)
+        if t.dtype != dtype or not t.is_contiguous():
+            t = t.to(dtype).contiguous()
+        # the kernel reads a pixel at a time, 16 bytes at C = 4: a dense view that starts inside its storage gets a copy of its own
+        return t.clone() if t.data_ptr() % 16 else t
+
+    ps = [dense(t.detach(), torch.float32) for t in probs]
+    g = dense(gt, torch.int64)
+    R = len(ps) + int(bool(with_ensemble))
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= 32:
+        raise ValueError(f"calibration_counts: n_bins {n_bins} must lie in [1, 32]")
+    # one allocation, one zeroing launch: bins in front, scores behind (both int64)
+    nb = B * R * n_bins * 3
+    buf = torch.zeros(nb + B * R * 2, dtype=torch.int64, device=ps[0].device)
+    bins, scores = buf[:nb].view(B, R, n_bins, 3), buf[nb:].view(B, R, 2)
+    call("dct_calibration_counts", _ptr_array(ps), len(ps), ptr(g), B, ppi, C_, n_bins, mask, int(bool(with_ensemble)),
+         int(bool(from_logits)), ptr(bins), ptr(scores), stream())
+    return bins, scores
+
+
 # ------------------------------------------------------------------------------ Enet family
 class Tf(object):
     """Producer transform act(scale*x + shift) applied by consumers on load (include/dct.h dct_enet_tf)."""

@@ -5,7 +5,9 @@ result tables (Summary.py:70-252), which takes it from an external package: here
 ``AgreementMeter`` is the third: Cohen's kappa between every pair of raters (the models, an ensemble, gt), and the IoU of the
 reference's ``IoU`` / ``ConfusionMatrix`` meters, from the pairwise confusion matrices of ``dct_confusion_counts``.
 ``keep_largest_component`` is the cleaning ACDC-style pipelines apply in front of all of them (``dct_largest_component``), and
-``ComponentMeter`` reports what it removed."""
+``ComponentMeter`` reports what it removed.  ``CalibrationMeter`` is the first that uses the values of the probabilities and not only
+their argmax: ECE, MCE, Brier score, NLL, the reliability diagram and the coverage-accuracy curve of every view and of their mean,
+from the integer tables of ``dct_calibration_counts``."""
 from __future__ import annotations
 
 import math
@@ -16,7 +18,7 @@ import torch
 from .. import hip_ops as K
 
 __all__ = ["DiceMeter", "HausdorffMeter", "AgreementMeter", "ComponentMeter", "AverageValueMeter", "keep_largest_component", "pair_index",
-           "kappa_of", "iou_of"]
+           "kappa_of", "iou_of", "CalibrationMeter", "ece_of", "mce_of"]
 
 
 class DiceMeter(object):
@@ -330,6 +332,171 @@ class AgreementMeter(object):
         """Mean (and std) over the rows of a row's mean kappa over the pairs that contain gt (all pairs without gt)."""
         (mean, std), _ = self.value()
         return {'mKappa': mean, 'mVars': std}
+
+
+CONF_UNIT = float(1 << 24)      # the fixed-point unit of the confidence, Brier and NLL sums of dct_calibration_counts
+
+
+def _gaps_of(bins):
+    """bins [..., n_bins, 3] -> (n [..., n_bins], N [...], |acc_k - conf_k| [..., n_bins] with 0 in the empty bins) in float64."""
+    b = np.asarray(bins, dtype=np.float64)
+    assert b.ndim >= 2 and b.shape[-1] == 3, b.shape
+    n = b[..., 0]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        gap = np.where(n > 0, np.abs(b[..., 1] / n - b[..., 2] / (CONF_UNIT * n)), 0.0)
+    return n, n.sum(-1), gap
+
+
+def ece_of(bins):
+    """Expected calibration error of reliability tables bins [..., n_bins, 3] = {pixels, correct pixels, sum of conf * 2^24} per bin
+    (``dct_calibration_counts``, include/dct.h) in float64: sum_k (n_k / N) |acc_k - conf_k|; NaN where N = 0."""
+    n, N, gap = _gaps_of(bins)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(N > 0, (n * gap).sum(-1) / N, np.nan)
+
+
+def mce_of(bins):
+    """Maximum calibration error of reliability tables bins [..., n_bins, 3]: the largest |acc_k - conf_k| over the non-empty bins;
+    NaN where there is none."""
+    n, N, gap = _gaps_of(bins)
+    return np.where(N > 0, gap.max(-1), np.nan)
+
+
+class CalibrationMeter(object):
+    """Calibration of ``n_models`` views and, ``with_ensemble``, of the mean of their probabilities (always the soft vote: a hard
+    vote has no confidence), from the reliability tables of ``dct_calibration_counts`` (one launch per ``add``): '2d' = one row per
+    slice, '3d' = one row for the batch.  Only the pixels whose gt lies in ``considered_classes`` count when that is set (on a
+    segmentation slice ~90 % of the pixels are background that is confidently right, and every aggregate over them looks
+    perfect).  ``from_logits``: ``add`` is given logits and the kernel takes their softmax.  A row without a counted pixel has
+    no ECE, MCE, Brier score or NLL: NaN, left out of every statistic and not counted in ``defined``.  ``rater_names`` renames the
+    views (default ``S{i}``); the mean of the views is ``ensemble``."""
+
+    def __init__(self, method='2d', C=4, n_models=2, with_ensemble=True, n_bins=15, considered_classes=None, from_logits=False,
+                 rater_names=None) -> None:
+        assert method in ('2d', '3d')
+        assert 1 <= n_models <= 8, n_models
+        assert 1 <= C <= 8, C
+        assert 1 <= int(n_bins) <= 32, n_bins
+        assert considered_classes is None or all(0 <= int(c) < C for c in considered_classes), considered_classes
+        self.method = method
+        self.C = C
+        self.n_models = n_models
+        self.with_ensemble = bool(with_ensemble)
+        self.n_bins = int(n_bins)
+        self.considered_classes = None if considered_classes is None else [int(c) for c in considered_classes]
+        self.from_logits = bool(from_logits)
+        names = list(rater_names) if rater_names is not None else [f"S{i}" for i in range(n_models)]
+        assert len(names) == n_models, names
+        self.raters = names + (["ensemble"] if self.with_ensemble else [])
+        self.reset()
+
+    def reset(self):
+        self.countLog = []
+        self._cache = None
+
+    def add(self, preds, gt):
+        """preds: ``n_models`` tensors [B,C,H,W], probabilities (logits with ``from_logits``); gt [B,1,H,W] integer."""
+        if not isinstance(preds, (list, tuple)) or len(preds) != self.n_models:
+            raise RuntimeError(f"dct_amd CalibrationMeter was built for a list of {self.n_models} predictions")
+        if gt is None:
+            raise RuntimeError("dct_amd CalibrationMeter: gt is required")
+        if any(not p.is_cuda for p in preds) or not gt.is_cuda:
+            raise RuntimeError("dct_amd CalibrationMeter counts on the HIP device only (no CPU fallback)")
+        B = preds[0].shape[0]
+        ps = [p.detach().permute(0, 2, 3, 1) for p in preds]
+        bins, scores = K.calibration_counts(ps, gt.reshape(B, -1), n_bins=self.n_bins, classes=self.considered_classes,
+                                            with_ensemble=self.with_ensemble, from_logits=self.from_logits)
+        row = torch.cat((bins.flatten(2), scores), dim=2)       # [B, R, n_bins * 3 + 2]: one log, one host copy per reading
+        if self.method == '3d':
+            row = row.sum(0, keepdim=True)
+        self.countLog.append(row)                               # nothing here waits for the device
+        self._cache = None
+
+    def _rows(self):
+        # ONE device->host copy of the log per reading (cached until the next add); everything derived is float64 host arithmetic
+        # on rows x R x (n_bins x 3 + 2) integers
+        if self._cache is None:
+            R, nb = len(self.raters), self.n_bins
+            if self.countLog:
+                rows = torch.cat(self.countLog).cpu().numpy()
+            else:
+                rows = np.zeros((0, R, nb * 3 + 2), dtype=np.int64)
+            self._cache = {'bins': rows[:, :, :nb * 3].reshape(-1, R, nb, 3), 'scores': rows[:, :, nb * 3:]}
+        return self._cache['bins'], self._cache['scores']
+
+    def _stats(self):
+        bins, scores = self._rows()
+        if 'stats' not in self._cache:
+            N = bins[..., 0].sum(-1).astype(np.float64)                              # [rows, R]
+            with np.errstate(divide='ignore', invalid='ignore'):
+                per_row = {'ECE': ece_of(bins), 'MCE': mce_of(bins),
+                           'Brier': np.where(N > 0, scores[..., 0] / (CONF_UNIT * N), np.nan),
+                           'NLL': np.where(N > 0, scores[..., 1] / (CONF_UNIT * N), np.nan)}
+                stats = {k: _nan_moments(v) for k, v in per_row.items()}
+                rep = _nan_moments(per_row['ECE'].T)[0]          # a row's report value: the mean ECE over its raters
+            rmean, rstd, _ = _nan_moments(rep[:, None])
+            stats['report'] = (float(rmean[0]), float(rstd[0]))
+            self._cache['stats'] = stats
+        return self._cache['stats']
+
+    def _triple(self, key):
+        mean, std, n = self._stats()[key]
+        return torch.from_numpy(mean), torch.from_numpy(std), torch.from_numpy(n)
+
+    def ece(self):
+        """(mean [R], std [R], defined [R]) of the per-row expected calibration error of every rater, in the order of ``raters``."""
+        return self._triple('ECE')
+
+    def mce(self):
+        """(mean [R], std [R], defined [R]) of the per-row maximum calibration error."""
+        return self._triple('MCE')
+
+    def brier(self):
+        """(mean [R], std [R], defined [R]) of the per-row Brier score (mean over the counted pixels of sum_c (p_c - [c == gt])^2)."""
+        return self._triple('Brier')
+
+    def nll(self):
+        """(mean [R], std [R], defined [R]) of the per-row negative log-likelihood (mean of -log(p_gt + 1e-10))."""
+        return self._triple('NLL')
+
+    def tables(self):
+        """int64 [R, n_bins, 3]: the reliability table of every rater over everything added."""
+        return torch.from_numpy(self._rows()[0].sum(0))
+
+    def reliability(self):
+        """(count int64 [R, n_bins], accuracy [R, n_bins], confidence [R, n_bins]) over everything added; NaN in an empty bin."""
+        t = self._rows()[0].sum(0)
+        n = t[..., 0].astype(np.float64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            acc = np.where(n > 0, t[..., 1] / n, np.nan)
+            conf = np.where(n > 0, t[..., 2] / (CONF_UNIT * n), np.nan)
+        return torch.from_numpy(t[..., 0].copy()), torch.from_numpy(acc), torch.from_numpy(conf)
+
+    def coverage_accuracy(self):
+        """(coverage [R, n_bins], kept_accuracy [R, n_bins]) over everything added: at a bin's lower edge k / n_bins, the share of
+        the counted pixels whose confidence lies in the bins >= k and the accuracy of those pixels -- what a pseudo-label
+        ``threshold=k / n_bins`` would keep, and how right it would be.  NaN where nothing is counted / kept."""
+        t = self._rows()[0].sum(0).astype(np.float64)
+        kept = t[..., 0][:, ::-1].cumsum(-1)[:, ::-1]
+        right = t[..., 1][:, ::-1].cumsum(-1)[:, ::-1]
+        N = t[..., 0].sum(-1, keepdims=True)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            cov = np.where(N > 0, kept / N, np.nan)
+            acc = np.where(kept > 0, right / kept, np.nan)
+        return torch.from_numpy(cov), torch.from_numpy(acc)
+
+    def value(self, **kwargs):
+        s = self._stats()
+        return s['report'], (torch.from_numpy(s['ECE'][0]), torch.from_numpy(s['ECE'][1]))
+
+    def detailed_summary(self) -> dict:
+        s = self._stats()
+        return {name: {k: float(s[k][0][r]) for k in ('ECE', 'MCE', 'Brier', 'NLL')} for r, name in enumerate(self.raters)}
+
+    def summary(self) -> dict:
+        """Mean (and std) over the rows of a row's mean ECE over its raters."""
+        (mean, std), _ = self.value()
+        return {'mECE': mean, 'mVars': std}
 
 
 def keep_largest_component(pred: torch.Tensor, method='2d', classes=None, background=0, full_connectivity=False, return_stats=False):

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional
 import torch
 from torch import Tensor
 
-from .metrics import AgreementMeter, ComponentMeter, DiceMeter, HausdorffMeter, keep_largest_component
+from .metrics import AgreementMeter, CalibrationMeter, ComponentMeter, DiceMeter, HausdorffMeter, keep_largest_component
 from .models import Segmentator
 
 
@@ -69,7 +69,8 @@ class Ensembleway(object):
 def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method: str = 'soft',
               report_axises: Optional[List[int]] = None, hausdorff: bool = False, spacing=None,
               kappa: bool = False, iou: bool = False, kappa_classes: Optional[List[int]] = None,
-              largest_component: Optional[str] = None, lcc_classes: Optional[List[int]] = None, lcc_full: bool = False) -> Dict[str, dict]:
+              largest_component: Optional[str] = None, lcc_classes: Optional[List[int]] = None, lcc_full: bool = False,
+              calibration: bool = False, calibration_bins: int = 15, calibration_classes: Optional[List[int]] = None) -> Dict[str, dict]:
     """Per-model and ensemble 2-D / 3-D Dice over a validation loader (batches ``[(img, gt), meta, names]``): tables ``'2d'`` and
     ``'3d'`` with keys ``DSC{j}``.  ``hausdorff=True`` adds the tables ``'hd_2d'`` and ``'hd_3d'`` with keys ``HD{j}``: mean (and
     for the ensemble the std) of the Hausdorff distance over the slices / patient batches where class j is in both the
@@ -86,7 +87,17 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
     a volume, with 4- / 6-connectivity (8- / 26- with ``lcc_full``): every table that is switched on gets a twin named ``..._lcc``
     (``'2d_lcc'``, ``'hd_3d_lcc'``, ``'kappa_2d_lcc'``, ...), and ``'components'`` = ``{model_i | ensemble: {'CC{j}': mean number of
     components of class j, 'removed{j}': mean share of its pixels that the cleaning removed}}`` over the slices / batches that hold the
-    class.  The tables without the suffix are what they are without the argument."""
+    class.  The tables without the suffix are what they are without the argument.
+
+    ``calibration=True`` adds ``'calibration_2d'`` and ``'calibration_3d'`` = ``{model_i | ensemble: {'ECE', 'MCE', 'Brier', 'NLL'}}``
+    plus ``ensemble_std``: expected and maximum calibration error over ``calibration_bins`` equal confidence bins, Brier score and
+    negative log-likelihood (include/dct.h, ``dct_calibration_counts``), mean over the slices / patient batches that hold a counted
+    pixel; ``calibration_classes`` counts only the pixels whose gt lies in that class set.  It also adds ``'reliability'`` =
+    ``{model_i | ensemble: {'count': [...], 'accuracy': [...], 'confidence': [...], 'coverage': [...], 'kept_accuracy': [...]}}``, one
+    entry per bin, pooled over the loader: the reliability diagram, and at each bin's lower edge the share of the counted pixels at
+    or above it and their accuracy (the curve a pseudo-label ``threshold=`` is read from).  The ensemble rater of these tables is
+    always the MEAN of the models' probabilities, whatever ``ensemble_method`` is: a hard vote has no confidence.  They get no
+    ``_lcc`` twin: the cleaned maps are one-hot."""
     assert largest_component in (None, '2d', '3d'), largest_component
     device = torch.device(device)
     C = models[0].arch_params['num_classes']
@@ -96,6 +107,8 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
         m.to(device)
         m.eval()
     names = [f"S{i}" for i in range(len(models))] + ["ensemble"]
+    if calibration:
+        assert len(models) <= 8, "calibration tables: at most 8 models (dct_calibration_counts takes 8 views)"
     if kappa or iou:
         assert len(models) <= 7, "kappa / iou tables: at most 7 models beside the ensemble (dct_confusion_counts takes 8 predictions)"
     sp = tuple(spacing) if spacing is not None else (1., 1., 1.)
@@ -123,6 +136,9 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
             ensemble.add(v, gt)
 
     raw = meter_set()
+    calib = [CalibrationMeter(method=method, C=C, n_models=len(models), with_ensemble=True, n_bins=calibration_bins,
+                              considered_classes=calibration_classes, from_logits=False, rater_names=names[:-1])
+             for method in ('2d', '3d')] if calibration else []
     cleaned = meter_set() if largest_component else None
     comp = [ComponentMeter(method=largest_component, C=C) for _ in names] if largest_component else []
     for (img, gt), _, _ in val_dataloader:
@@ -130,6 +146,8 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
         preds = [m.predict(img, logit=False) for m in models]
         v = ens(preds)
         feed(raw, preds, v, gt)
+        for c in calib:
+            c.add(preds, gt)
         if cleaned is not None:
             kept = []
             for meter, p in zip(comp, preds + [v]):
@@ -166,6 +184,17 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
                 out[f'iou_{a.method}{suffix}'] = res
 
     tables(raw, "")
+    keys = [f'model_{i}' for i in range(len(models))] + ['ensemble']
+    for c in calib:
+        stats = {k: fn() for k, fn in (('ECE', c.ece), ('MCE', c.mce), ('Brier', c.brier), ('NLL', c.nll))}
+        res = {key: {k: float(stats[k][0][r]) for k in stats} for r, key in enumerate(keys)}
+        res['ensemble_std'] = {k: float(stats[k][1][-1]) for k in stats}
+        out[f'calibration_{c.method}'] = res
+    if calib:
+        count, acc, conf = calib[0].reliability()
+        cov, kept = calib[0].coverage_accuracy()
+        out['reliability'] = {key: {'count': count[r].tolist(), 'accuracy': acc[r].tolist(), 'confidence': conf[r].tolist(),
+                                    'coverage': cov[r].tolist(), 'kept_accuracy': kept[r].tolist()} for r, key in enumerate(keys)}
     if cleaned is not None:
         tables(cleaned, "_lcc")
         out['components'] = {(f'model_{i}' if i < len(models) else 'ensemble'): m.detailed_summary() for i, m in enumerate(comp)}

@@ -33,7 +33,7 @@ from torch import Tensor, nn
 
 from .. import ModelMode
 from .. import scheduler
-from ..metrics import AgreementMeter, AverageValueMeter, DiceMeter, HausdorffMeter, keep_largest_component
+from ..metrics import AgreementMeter, AverageValueMeter, CalibrationMeter, DiceMeter, HausdorffMeter, keep_largest_component
 from ..models import Segmentator
 from ..utils import iterator_, map_, dict_merge, tqdm_
 from ..utils.AEGenerator import FSGMGenerator
@@ -166,8 +166,12 @@ class CoTrainer(Trainer):
                  val_hausdorff: bool = False,
                  val_spacing=(1., 1., 1.),
                  val_kappa: bool = False,
-                 val_largest_component: bool = False) -> None:
+                 val_largest_component: bool = False,
+                 val_calibration: bool = False) -> None:
         self.max_epoch = max_epoch
+        # opt-in: _eval_loop also measures how well the confidences of every view and of their mean are calibrated (3-D rows, 15 bins, the
+        # pixels whose gt lies in `axises`) from the logits it already has, and uploads ECE, NLL and Brier score as 'val_calibration'
+        self.val_calibration = bool(val_calibration)
         # opt-in: _eval_loop also scores every model's prediction with only the largest connected component of each class of `axises`
         # kept (per batch as a volume, the rest to class 0) and uploads the 3-D Dice as 'val_lcc' (and, with val_hausdorff, the
         # Hausdorff distance as 'val_hd_lcc'): the number an ACDC-style post-processing would report
@@ -1160,8 +1164,10 @@ class CoTrainer(Trainer):
                     for _ in range(S)] if self.val_hausdorff else []
         kappaMeter = AgreementMeter(method='3d', C=self.C, n_models=S, with_gt=True,
                                     considered_classes=list(self.axises)) if self.val_kappa else None
+        calibMeter = CalibrationMeter(method='3d', C=self.C, n_models=S, with_ensemble=True, considered_classes=list(self.axises),
+                                      from_logits=True) if self.val_calibration else None
         lcc = self.val_largest_component
-        lccDiceMeters = [DiceMeter(report_axises=self.axises, method='3d', C=self.C) for _ in range(S)] if lcc else []
+        lccDiceMeters =[DiceMeter(report_axises=self.axises, method='3d', C=self.C) for _ in range(S)] if lcc else []
         lccHdMeters = [HausdorffMeter(report_axises=self.axises, method='3d', C=self.C, spacing=self.val_spacing)
                        for _ in range(S)] if lcc and self.val_hausdorff else []
         val_iter = tqdm_(val_dataloader) if self.use_tqdm else val_dataloader
@@ -1171,6 +1177,8 @@ class CoTrainer(Trainer):
             loss = map_(lambda pred: self.criterions.get('sup')(pred, gt.squeeze(1)), preds)
             if kappaMeter is not None:
                 kappaMeter.add(list(preds), gt)
+            if calibMeter is not None:
+                calibMeter.add(list(preds), gt)
             for i in range(S):
                 coefdiceMeters[i].add(preds[i], gt)
                 batchdiceMeters[i].add(preds[i], gt)
@@ -1196,6 +1204,9 @@ class CoTrainer(Trainer):
             self.upload_dicts('val_hd_lcc', {f"S{i}": {f"HD{n}": float(vals[i][1][0][n]) for n in self.axises} for i in range(S)}, epoch)
         if kappaMeter is not None:
             self.upload_dicts('val_kappa', {pair: {'kappa': k} for pair, k in kappaMeter.detailed_summary().items()}, epoch)
+        if calibMeter is not None:
+            self.upload_dicts('val_calibration', {name: {k: d[k] for k in ('ECE', 'NLL', 'Brier')}
+                                                  for name, d in calibMeter.detailed_summary().items()}, epoch)
         nice_dict = self._report_dict(batchdiceMeters)
         if self._is_main():
             print(f"{desc} " + ', '.join([f'{k}_{k_}: {v[k_]:.2f}' for k, v in nice_dict.items() for k_ in v.keys()]))

@@ -675,6 +675,36 @@ int dct_largest_component(const float* logits /*[B][H][W][C]*/, int B, int H, in
 int dct_confusion_counts(const float* const* logits, int S, const int64_t* gt /*[B][pixels], nullable*/,
                          int B, int64_t pixels_per_image, int C, int32_t* counts /*[B][P][C][C]*/, dct_stream stream);
 
+/* ---- Calibration on device: reliability tables, and the sums behind the Brier score and the negative log-likelihood ----------
+ * Inputs: S tensors probs[s] = [B][pixels][C] in fp32, 1 <= S <= 8, 1 <= C <= 8; gt as int64.  With from_logits each view first
+ *   becomes p = softmax(x) in fp32: m = max_c x_c, e_c = expf(x_c - m), p_c = e_c / sum_c e_c (the sum in class order).  Everything
+ *   below is a function of the fp32 p only; without from_logits the inputs are taken to be probabilities (in [0, 1]) as they are.
+ * Raters: the S views in order.  With with_ensemble one more rater follows: p_ens = (p_0 + p_1 + ...) / S, summed in view order in
+ *   fp32, one fp32 division (exact when S is a power of two).  R = S + with_ensemble.
+ * Which pixels count: those with 0 <= gt < C and bit gt of class_mask set (bits at C and above mean nothing) -- the "second rater
+ *   lies in this class set" convention of kappa above; 255, negative and >= C never count.
+ * Per counted pixel and rater: conf = max_c p_c; pred = the first maximum, exactly as dct_argmax / dct_confusion_counts;
+ *   correct = (pred == gt); bin = min(n_bins - 1, (int)(conf * (float)n_bins)), one fp32 multiply, 1 <= n_bins <= 32 (a negative
+ *   or NaN conf goes to bin 0); brier = sum_c (p_c - [c == gt])^2; nll = -logf(p_gt + 1e-10f).
+ * What is stored, all integers, so that the sums are order-independent and bit-identical from run to run:
+ *   bins[b][r][k][3] (int64) += {pixels, correct pixels, sum of (uint32)(conf * 2^24)} of bin k;
+ *   scores[b][r][2] (int64) += {sum of (int64)(brier * 2^24), sum of (int64)(nll * 2^24)}.
+ *   The truncation loses less than 2^-24 per pixel; for conf >= 0.5 the scaling is exact.  For probabilities every word fits 32 bits
+ *   (brier <= 2, nll <= -log(1e-10) = 23.03) and is converted as such: an input outside [0, 1] saturates there, a NaN gives 0.
+ * Derived, on the host, in float64, for a row (an image, a batch, everything pooled) with N counted pixels and per bin n_k pixels:
+ *   acc_k = correct_k / n_k, conf_k = confsum_k / (2^24 n_k); ECE = sum_k (n_k / N) |acc_k - conf_k|; MCE = the maximum of
+ *   |acc_k - conf_k| over the non-empty bins; Brier and NLL = the means over the counted pixels; N = 0 gives NaN everywhere.
+ *   Coverage and accuracy at a bin's lower edge k / n_bins: the share of the counted pixels in bins >= k, and their accuracy.
+ * One launch reads every pixel of every view once ((4 C S + 8) bytes per pixel).  probs: S host-side entries, each a device tensor
+ * aligned to its pixel (16 bytes at C = 4, 8 at C = 2, else 4); gt, bins and scores 8-byte aligned; bins and scores are zeroed by
+ * the caller (or hold earlier sums: the call adds).  No workspace; nothing waits for the device.
+ * DCT_ERR_BAD_ARG: a null probs / entry / gt / bins / scores, a misaligned pointer, S < 1, B < 1, pixels < 1, with_ensemble or
+ * from_logits not 0 or 1; DCT_ERR_UNSUPPORTED: S > 8, C < 1 or C > 8, n_bins < 1 or n_bins > 32, B > 65535, pixels_per_image >= 2^31.
+ * Both are decided before anything is launched. */
+int dct_calibration_counts(const float* const* probs, int S, const int64_t* gt /*[B][pixels]*/, int B, int64_t pixels_per_image,
+                           int C, int n_bins, uint32_t class_mask, int with_ensemble, int from_logits,
+                           int64_t* bins /*[B][R][n_bins][3]*/, int64_t* scores /*[B][R][2]*/, dct_stream stream);
+
 /* ---- per-kernel-class timing (bench.py roofline leg) --------------------------------------
  * When enabled every launch made through this library is bracketed by hipEvents on its stream;
  * dct_prof_read synchronises and returns accumulated milliseconds and launch counts per class. */
