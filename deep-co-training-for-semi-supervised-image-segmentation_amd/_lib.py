@@ -123,6 +123,11 @@ SIGNATURES = {
     "dct_ce_weighted_step": (_i, [_P, _P, _i64, _i, _i, _P, _i, _P, _P, _f, _P, _i, _P, _sz, _P]),
     "dct_ce_map_fwd": (_i, [_P, _P, _i64, _i, _i, _P, _P, _P]),
     "dct_ce_map_bwd": (_i, [_P, _P, _i64, _i, _i, _P, _P, _f, _P, _i, _P]),
+    "dct_focal_fwd": (_i, [_P, _P, _i64, _i, _i, _P, _f, _i, _P, _P, _sz, _P]),
+    "dct_focal_bwd": (_i, [_P, _P, _i64, _i, _i, _P, _f, _i, _P, _P, _f, _P, _i, _P]),
+    "dct_focal_step": (_i, [_P, _P, _i64, _i, _i, _P, _f, _i, _P, _P, _f, _P, _i, _P, _sz, _P]),
+    "dct_focal_map_fwd": (_i, [_P, _P, _i64, _i, _i, _P, _f, _P, _P]),
+    "dct_focal_map_bwd": (_i, [_P, _P, _i64, _i, _i, _P, _f, _P, _f, _P, _i, _P]),
     "dct_ce_dice_workspace_bytes": (_sz, [_i, _i, _i]),
     "dct_ce_dice_fwd": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _i, _f, _f, _P, _P, _P, _P, _sz, _P]),
     "dct_ce_dice_bwd": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _i, _f, _f, _P, _P, _P, _f, _P, _i, _P]),

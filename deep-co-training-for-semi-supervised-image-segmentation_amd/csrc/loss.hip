@@ -258,6 +258,135 @@ __global__ __launch_bounds__(256) void ce_map_bwd_kernel(const float* logits, co
   ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, gmul, dmap, dl, acc);
 }
 
+// ---- focal loss (the rule: include/dct.h, dct_focal_*) ----------------------------------------------------------------------------------
+// One pixel: p = softmax(x); q = the mass off the target, summed from the exponentials (never 1 - p_t: at a confident pixel that is a
+// rounding error); l = -log p_t = -log1p(-q) while q < 1/2 (relative error ~ that of q) and (max - x_t) + log(sum) above it (two terms
+// >= 0, l >= log 2: nothing cancels); m = q^gamma = exp2(gamma log2 q); k = m (1 + gamma p_t l / q), the sum of two terms >= 0.
+// gamma == 0 (the same in every lane) is m = k = 1 whatever q is; q == 0 under gamma > 0 is m = k = 0 (then l = -log1p(-0) = 0 too).
+// The selects keep every operand finite: log2 and the division see 1 in place of a zero q, and p_t == 0 (the only case in which l may
+// have overflowed) drops its term.  A target outside [0, C) selects nothing and leaves finite numbers that the callers discard.
+template <int C>
+__device__ __forceinline__ void focal_px(const float x[C], long long t, float gamma, float p[C], float& q, float& l, float& m, float& k) {
+  float mx = x[0];
+#pragma unroll
+  for (int c = 1; c < C; ++c) mx = fmaxf(mx, x[c]);
+  float s = 0.f, off = 0.f, xt = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    p[c] = expf(x[c] - mx);
+    s += p[c];
+    off += (t == c) ? 0.f : p[c];
+    xt = (t == c) ? x[c] : xt;
+  }
+  const float inv = 1.f / s;
+  float pt = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) { p[c] *= inv; pt = (t == c) ? p[c] : pt; }
+  q = off * inv;
+  l = q < 0.5f ? -log1pf(-q) : (mx - xt) + logf(s);
+  if (gamma == 0.f) { m = 1.f; k = 1.f; return; }
+  const bool some = q > 0.f;
+  const float qs = some ? q : 1.f;
+  const float pw = exp2f(gamma * log2f(qs));
+  const float tl = pt > 0.f ? pt * (l / qs) : 0.f;
+  m = some ? pw : 0.f;
+  k = some ? pw * (1.f + gamma * tl) : 0.f;
+}
+// dl (=|+=) (g * w_t * k) * (p - onehot) over the grid's pixels, the target's own entry as -q; g_px (nullable): the map's dmap
+template <int C>
+__device__ __forceinline__ void focal_grad_pixels(const float* logits, const long long* tgt, long long P, int ignore, const float wr[C],
+                                                  float gamma, float g, const float* g_px, float* dl, int acc) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[pix];
+    const bool on = counted<C>(t, ignore);
+    float x[C], p[C], d[C], q, l, m, k;
+    load_px<C>(logits, pix, x);
+    focal_px<C>(x, t, gamma, p, q, l, m, k);
+    const float gw = (g_px ? g * g_px[pix] : g) * weight_of<C>(t, wr) * k;
+#pragma unroll
+    for (int c = 0; c < C; ++c) d[c] = on ? gw * (t == c ? -q : p[c]) : 0.f;
+    store_px<C>(dl, pix, d, acc);
+  }
+}
+// w_t m l of one counted pixel and its w_t
+template <int C>
+__device__ __forceinline__ float focal_value(const float* logits, long long pix, long long t, const float wr[C], float gamma, float& w) {
+  float x[C], p[C], q, l, m, k;
+  load_px<C>(logits, pix, x);
+  focal_px<C>(x, t, gamma, p, q, l, m, k);
+  w = weight_of<C>(t, wr);
+  return w * (m * l);
+}
+// partial[2b] = the block's sum of w m l, partial[2b + 1] = its sum of w (ce_w_fwd_kernel's walk)
+template <int C>
+__global__ __launch_bounds__(256) void focal_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                         float gamma, float* partial) {
+  float wr[C];
+  load_weights<C>(weight, wr);
+  float sum = 0.f, den = 0.f;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[pix];
+    if (!counted<C>(t, ignore)) continue;
+    float w;
+    sum += focal_value<C>(logits, pix, t, wr, gamma, w);
+    den += w;
+  }
+  block_partial2(sum, den, partial);
+}
+template <int C>
+__global__ __launch_bounds__(256) void focal_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                         float gamma, const float* denom, const float* gscale, float gmul, float* dl, int acc) {
+  float wr[C];
+  load_weights<C>(weight, wr);
+  float g = (gscale ? gscale[0] : 1.f) * gmul;
+  if (denom) g = g / denom[0];          // (the sum reduction passes none: its denominator is 1)
+  focal_grad_pixels<C>(logits, tgt, P, ignore, wr, gamma, g, nullptr, dl, acc);
+}
+// ce_w_bwd_fin_kernel's fold (finalize_kernel's order, in every block) in front of the focal gradient
+template <int C>
+__global__ __launch_bounds__(256) void focal_bwd_fin_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                             float gamma, int mean, const float* partial, int blocks, float* out2,
+                                                             const float* gscale, float gmul, float* dl, int acc) {
+  __shared__ float sa[256], sb[256];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
+  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  const float den = sb[0];
+  if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = mean ? sa[0] / den : sa[0]; out2[1] = den; }
+  float wr[C];
+  load_weights<C>(weight, wr);
+  float g = (gscale ? gscale[0] : 1.f) * gmul;
+  if (mean) g = g / den;
+  focal_grad_pixels<C>(logits, tgt, P, ignore, wr, gamma, g, nullptr, dl, acc);
+}
+template <int C>
+__global__ __launch_bounds__(256) void focal_map_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                             float gamma, float* map) {
+  float wr[C];
+  load_weights<C>(weight, wr);
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[pix];
+    float v = 0.f;
+    if (counted<C>(t, ignore)) {
+      float w;
+      v = focal_value<C>(logits, pix, t, wr, gamma, w);
+    }
+    map[pix] = v;
+  }
+}
+template <int C>
+__global__ __launch_bounds__(256) void focal_map_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                             float gamma, const float* dmap, float gmul, float* dl, int acc) {
+  float wr[C];
+  load_weights<C>(weight, wr);
+  focal_grad_pixels<C>(logits, tgt, P, ignore, wr, gamma, gmul, dmap, dl, acc);
+}
+
 // ---- boundary loss: the softmax weighted by the signed distance map (the rule: include/dct.h, dct_boundary_*) --------------------------
 // phi has the layout of the logits: both are read with the same loads (16 bytes at C = 4, two of them at C = 8).
 template <int C> __device__ __forceinline__ void load_px16(const float* p, long long pix, float v[C]) {
@@ -1236,6 +1365,61 @@ extern "C" int dct_ce_map_bwd(const float* logits, const int64_t* targets, int64
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_map_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, dmap, gmul,
                             dlogits, accumulate));
+  return dct_check_launch();
+}
+// gamma of the focal loss: finite and >= 0 (a NaN fails the comparison)
+static inline bool gamma_ok(float gamma) { return gamma >= 0.f && gamma <= 3.402823466e38f; }
+
+extern "C" int dct_focal_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                             float gamma, int reduction, float* out2, void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !out2 || pixels < 1 || (reduction != 0 && reduction != 1) || !gamma_ok(gamma)) return DCT_ERR_BAD_ARG;
+  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, gamma,
+                            (float*)workspace));
+  DCT_LAUNCH(DCT_PROF_LOSS, finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, reduction == 0 ? 1 : 0, 1.f, 1);
+  return dct_check_launch();
+}
+extern "C" int dct_focal_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                             float gamma, int reduction, const float* denom, const float* gscale, float gmul, float* dlogits, int accumulate,
+                             dct_stream stream) {
+  if (!logits || !targets || !dlogits || pixels < 1 || (reduction != 0 && reduction != 1) || (reduction == 0 && !denom) || !gamma_ok(gamma))
+    return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
+                            gamma, reduction == 0 ? denom : (const float*)nullptr, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+extern "C" int dct_focal_step(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                              float gamma, int reduction, float* out2, const float* gscale, float gmul, float* dlogits, int accumulate,
+                              void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !out2 || !dlogits || pixels < 1 || (reduction != 0 && reduction != 1) || !gamma_ok(gamma)) return DCT_ERR_BAD_ARG;
+  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);       // dct_focal_fwd's grid: the same block partials
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, gamma,
+                            (float*)workspace));
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_bwd_fin_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
+                            gamma, reduction == 0 ? 1 : 0, (const float*)workspace, (int)grid, out2, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+extern "C" int dct_focal_map_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                                 float gamma, float* map, dct_stream stream) {
+  if (!logits || !targets || !map || pixels < 1 || !gamma_ok(gamma)) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_map_fwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
+                            gamma, map));
+  return dct_check_launch();
+}
+extern "C" int dct_focal_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                                 float gamma, const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream) {
+  if (!logits || !targets || !dmap || !dlogits || pixels < 1 || !gamma_ok(gamma)) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_map_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
+                            gamma, dmap, gmul, dlogits, accumulate));
   return dct_check_launch();
 }
 // K of a boundary mask (the number of its bits below C), or a status

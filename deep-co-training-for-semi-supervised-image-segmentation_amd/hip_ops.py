@@ -527,6 +527,48 @@ def ce_map_bwd(logits_pc, targets, C_, dmap, dlogits, weight=None, gmul=1.0, ign
     return dlogits
 
 
+def focal_fwd(logits_pc, targets, C_, weight=None, gamma=2.0, reduction=CE_MEAN, ignore_index=255):
+    """Focal loss (dct_focal_fwd): ``weight``: fp32 [C] on the device, or None (all ones); ``gamma``: a host float, finite and >= 0.
+    Returns the device tensor [2] = (sum f / sum w | sum f, sum w) with f = w_t (1 - p_t)^gamma (-log p_t)."""
+    out = torch.empty(2, dtype=torch.float32, device=logits_pc.device)
+    ws = _loss_ws(logits_pc.device)
+    call("dct_focal_fwd", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), float(gamma),
+         int(reduction), ptr(out), ptr(ws), ws.numel(), stream())
+    return out
+
+
+def focal_bwd(logits_pc, targets, C_, denom, dlogits, weight=None, gamma=2.0, reduction=CE_MEAN, gscale=None, gmul=1.0, ignore_index=255,
+              accumulate=False):
+    """``denom``: ``out[1:2]`` of focal_fwd (not read under CE_SUM, where it may be None)."""
+    call("dct_focal_bwd", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), float(gamma),
+         int(reduction), ptr(denom), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), stream())
+    return dlogits
+
+
+def focal_step(logits_pc, targets, C_, dlogits, weight=None, gamma=2.0, reduction=CE_MEAN, gscale=None, gmul=1.0, ignore_index=255,
+               accumulate=False):
+    """focal_fwd + focal_bwd of the same logits in two launches (dct_focal_step; bit for bit the two calls).  Returns the device tensor
+    [2]; ``dlogits`` is written (added to)."""
+    out = torch.empty(2, dtype=torch.float32, device=logits_pc.device)
+    ws = _loss_ws(logits_pc.device)
+    call("dct_focal_step", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), float(gamma),
+         int(reduction), ptr(out), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), ptr(ws), ws.numel(), stream())
+    return out
+
+
+def focal_map_fwd(logits_pc, targets, C_, weight=None, gamma=2.0, ignore_index=255):
+    """-> fp32 [P]: w_t (1 - p_t)^gamma (-log p_t) per pixel, 0 where the target is ignored."""
+    m = torch.empty(logits_pc.numel() // C_, dtype=torch.float32, device=logits_pc.device)
+    call("dct_focal_map_fwd", ptr(logits_pc), ptr(targets), m.numel(), C_, int(ignore_index), ptr(weight), float(gamma), ptr(m), stream())
+    return m
+
+
+def focal_map_bwd(logits_pc, targets, C_, dmap, dlogits, weight=None, gamma=2.0, gmul=1.0, ignore_index=255, accumulate=False):
+    call("dct_focal_map_bwd", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), float(gamma),
+         ptr(dmap), float(gmul), ptr(dlogits), int(accumulate), stream())
+    return dlogits
+
+
 def _i64_dense(t):
     """int64, contiguous and on the 16-byte grid (a dense view that starts inside its storage gets a copy of its own)."""
     if t.dtype != torch.int64 or not t.is_contiguous():

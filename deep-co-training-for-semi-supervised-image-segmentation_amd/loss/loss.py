@@ -171,6 +171,83 @@ class CrossEntropyLoss2d(_ClassWeighted):
         return _CEWeightedFn.apply(outputs, targets, w, K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM, self.ignore_index)
 
 
+class _FocalFn(torch.autograd.Function):
+    """Focal mean (``reduction`` 0) or sum (1) on dct_focal_*; ``weight``: the fp32 device buffer or None (all ones)."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, gamma, reduction, ignore_index):
+        lp = _pc(logits)
+        t = _targets(targets)
+        out = K.focal_fwd(lp, t, lp.shape[3], weight, gamma, reduction, ignore_index)
+        ctx.save_for_backward(lp, t, out)
+        ctx.weight, ctx.gamma, ctx.reduction, ctx.ignore_index = weight, gamma, reduction, ignore_index
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lp, t, out = ctx.saved_tensors
+        dl = torch.empty_like(lp)
+        g = g.to(torch.float32).contiguous()
+        K.focal_bwd(lp, t, lp.shape[3], out[1:2], dl, weight=ctx.weight, gamma=ctx.gamma, reduction=ctx.reduction, gscale=g,
+                    ignore_index=ctx.ignore_index)
+        return _nchw(dl), None, None, None, None, None
+
+
+class _FocalMapFn(torch.autograd.Function):
+    """The [B, H, W] map w_t (1 - p_t)^gamma (-log p_t) of ``reduce=False`` on dct_focal_map_*."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, gamma, ignore_index):
+        lp = _pc(logits)
+        t = _targets(targets)
+        ctx.save_for_backward(lp, t)
+        ctx.weight, ctx.gamma, ctx.ignore_index = weight, gamma, ignore_index
+        return K.focal_map_fwd(lp, t, lp.shape[3], weight, gamma, ignore_index).view(lp.shape[:3])
+
+    @staticmethod
+    def backward(ctx, g):
+        lp, t = ctx.saved_tensors
+        dl = torch.empty_like(lp)
+        K.focal_map_bwd(lp, t, lp.shape[3], g.to(torch.float32).contiguous().view(-1), dl, weight=ctx.weight, gamma=ctx.gamma,
+                        ignore_index=ctx.ignore_index)
+        return _nchw(dl), None, None, None, None
+
+
+class FocalLoss2d(_ClassWeighted):
+    """Focal loss of Lin et al. (ICCV 2017) in its softmax form: ``w_t (1 - p_t)^gamma (-log p_t)`` per pixel (the rule: include/dct.h,
+    dct_focal_*), which turns the easy pixels down instead of whole classes.  ``gamma``: finite and >= 0; 0 is the class-weighted cross
+    entropy (computed by the focal kernels all the same).  ``weight`` (the per-class alpha), ``reduce``, ``size_average`` and
+    ``ignore_index`` as on ``CrossEntropyLoss2d``: the mean is ``sum f / sum w_t`` over the counted pixels -- with ``weight=None`` the
+    mean over the counted pixels of most published focal-loss code --, the sum ``sum f``, the map ``f``; the weights are read from
+    ``device_weight``'s buffer on the device."""
+
+    def __init__(self, gamma=2.0, weight=None, reduce=True, size_average=True, ignore_index=255):
+        super().__init__()
+        try:
+            self.gamma = float(gamma)
+        except (TypeError, ValueError):
+            raise ValueError(f"dct_amd {type(self).__name__}: gamma must be a number, got {gamma!r}")
+        if not (0.0 <= self.gamma < float('inf')):
+            raise ValueError(f"dct_amd {type(self).__name__}: gamma must be finite and >= 0, got {gamma!r}")
+        self._set_weight(weight)
+        self.reduce, self.size_average = reduce, size_average
+        self.reduction = 'none' if not reduce else ('mean' if size_average else 'sum')
+        self.ignore_index = ignore_index
+
+    def launch_args(self, C):
+        """The keyword arguments of hip_ops.focal_* beyond the weights (the same for every ``C``)."""
+        return dict(gamma=self.gamma)
+
+    def forward(self, outputs, targets):
+        assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
+        if not outputs.is_cuda:
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        w = self.device_weight(outputs.device, outputs.shape[1])
+        if self.reduction == 'none':
+            return _FocalMapFn.apply(outputs, targets, w, self.gamma, self.ignore_index)
+        return _FocalFn.apply(outputs, targets, w, self.gamma, K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM, self.ignore_index)
+
+
 class _CEDiceFn(torch.autograd.Function):
     """``ce_coef`` ce + ``dice_coef`` dice on dct_ce_dice_*; ``rule``: the launch arguments of ``CrossEntropyDiceLoss2d.launch_args``.
     Returns the total and, without a gradient, the [G, C] table of D_gc."""

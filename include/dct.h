@@ -293,6 +293,46 @@ int dct_ce_map_fwd(const float* logits, const int64_t* targets, int64_t pixels, 
                    const float* weight /*nullable*/, float* map, dct_stream stream);
 int dct_ce_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
                    const float* weight, const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream);
+/* Focal loss (Lin et al., "Focal loss for dense object detection", ICCV 2017) in its softmax form: the cross entropy of a pixel scaled by
+ * (1 - p_t)^gamma, so that the easy pixels stop carrying the sum.  logits fp32 [pixels][C], 2 <= C <= 8; targets int64; weight: C fp32
+ * values in device memory, nullable = all ones, picked by an unrolled select, never by weight[t]; gamma: a host float, finite and >= 0.
+ * A pixel is counted exactly as in dct_ce_weighted_*: t != ignore_index && 0 <= t < C.  Per counted pixel, with p = softmax(x), y the
+ * one-hot of t and w = weight[t]:
+ *   q = sum_{c != t} p_c, the probability mass off the target -- summed, never formed as 1 - p_t, so that its relative error stays a few
+ *       units of roundoff at a confident pixel;
+ *   l = -log p_t;
+ *   m = q^gamma, with m = 1 when gamma == 0 whatever q is, and m = 0 when q == 0 && gamma > 0;
+ *   f = w m l;
+ *   k = m + gamma p_t l q^(gamma - 1): 1 when gamma == 0, 0 when q == 0 && gamma > 0;
+ *   d f / d x_c = w k (p_c - y_c).
+ *   No inf * 0 and no 0 / 0 arises for any finite logits.
+ * reduction 0 (mean): out2[0] = sum f / sum w over the counted pixels, out2[1] = sum w (NaN when sum w == 0, as in dct_ce_weighted_fwd).
+ *   With gamma == 0 this is F.cross_entropy(weight=, ignore_index=, reduction='mean'); with weight == NULL it is the mean over the counted
+ *   pixels that most published focal-loss code uses.      reduction 1 (sum): out2[0] = sum f, out2[1] = sum w.
+ * Gradient: dlogits[i][c] (=|+=) (g w k) (p_c - y_c) with g = gscale[0] * gmul (gscale nullable = 1), divided by sum w under the mean
+ *   (denom = out2 + 1 of the forward call; not read under the sum).  Uncounted pixels get exactly 0 in the map and in the gradient
+ *   (exactly the old value under accumulate).
+ * dct_focal_step: fwd + bwd in two launches like dct_ce_weighted_step (the backward kernel folds the forward kernel's block partials in
+ *   every block); out2 and dlogits are bit for bit those of dct_focal_fwd followed by dct_focal_bwd.
+ * map: map[i] = f_i;  backward: dlogits[i][c] (=|+=) (gmul * dmap[i] * w k) (p_c - y_c).
+ * All sums are folded in one fixed order without float atomics: bit-identical from run to run.  Workspace: dct_loss_workspace_bytes.
+ * DCT_ERR_BAD_ARG: as for dct_ce_weighted_*, and a gamma that is negative, NaN or infinite; DCT_ERR_UNSUPPORTED: C outside 2..8;
+ * DCT_ERR_WORKSPACE: less than dct_loss_workspace_bytes of workspace.
+ * Out of scope: the sigmoid (binary) form, a per-pixel alpha map, focal + Dice in one launch, gamma in device memory, probabilities as
+ * input. */
+int dct_focal_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                  const float* weight /*nullable*/, float gamma, int reduction, float* out2, void* workspace, size_t workspace_bytes,
+                  dct_stream stream);
+int dct_focal_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                  const float* weight, float gamma, int reduction, const float* denom /*out2 + 1*/, const float* gscale, float gmul,
+                  float* dlogits, int accumulate, dct_stream stream);
+int dct_focal_step(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                   const float* weight, float gamma, int reduction, float* out2, const float* gscale, float gmul, float* dlogits,
+                   int accumulate, void* workspace, size_t workspace_bytes, dct_stream stream);
+int dct_focal_map_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                      const float* weight /*nullable*/, float gamma, float* map, dct_stream stream);
+int dct_focal_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                      const float* weight, float gamma, const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream);
 /* Soft Dice and CE + Dice as one supervised criterion (the reference's loss/dice.py, SURVEY 2 row 3, on logits).  logits: fp32 NHWC
  * [B][pixels_per_image][C]; targets: int64 [B * pixels_per_image]; weight: the C fp32 class weights of the CE term on the device, nullable
  * = all ones, exactly as in dct_ce_weighted_*; class_mask: bit c set = class c takes part in the Dice mean, K = the number of set bits
