@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from helpers import FakeLoader, batches  # noqa: E402
 from test_step_gpu import _seeded_state  # noqa: E402
-from test_weighted_step_gpu import DEV, WEIGHT, _one_step  # noqa: E402
+from test_weighted_step_gpu import DEV, WEIGHT, _moments_agree, _one_step  # noqa: E402
 
 CE_DICE = dict(weight=WEIGHT, ce_coef=1.0, dice_coef=1.0, classes=[1, 2, 3], smooth=1e-5)
 DICE = dict(classes=[1, 2, 3], per_image=True)
@@ -74,6 +74,7 @@ def test_dice_fused_and_generic_paths_agree(golden, tmp_path, fused_steps, name,
     np.testing.assert_allclose(a["adv"].item(), b["adv"].item(), rtol=1e-4)
     for x, y in zip(wa, wb):
         np.testing.assert_allclose(x[1:], y[1:], rtol=1e-5)
+    _moments_agree(wa, wb)
 
 
 def test_dice_reaches_the_fused_step(golden, tmp_path, fused_steps):

@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from helpers import FakeLoader, batches  # noqa: E402
 from test_step_gpu import _seeded_state  # noqa: E402
-from test_weighted_step_gpu import DEV, WEIGHT, _one_step  # noqa: E402
+from test_weighted_step_gpu import DEV, WEIGHT, _moments_agree, _one_step  # noqa: E402
 
 GAMMA = 2.0
 
@@ -68,6 +68,7 @@ def test_focal_fused_and_generic_paths_agree(golden, tmp_path, focal_fused_step)
     np.testing.assert_allclose(a["adv"].item(), b["adv"].item(), rtol=1e-4)
     for x, y in zip(wa, wb):
         np.testing.assert_allclose(x[1:], y[1:], rtol=1e-5)
+    _moments_agree(wa, wb)
 
 
 def test_focal_reaches_the_fused_step(golden, tmp_path, focal_fused_step):

@@ -388,6 +388,29 @@ def test_jsd_at_scale(ops, P, S, C, accumulate):
 KL_CASES = [(1, 3), (255, 2), (257, 5), (262144, 6), (262145, 7), (263144, 8), (524291, 4), (2097152, 3), (2097153, 2), (1638400, 2)]
 
 
+def _kl_ref(xp, xy, C, gg):
+    """float64: per-pixel KL(y || p) of the softmaxes of fp32 logits (oracle.kl_divergence_2d), its bound, the gradient ``gg`` * d sum_pix KL /
+    d p-logits and its bound, and the two softmaxes."""
+    P = xp.shape[0]
+    same = (xp == xy).all(1)
+    p, sp = _sm64(xp)
+    y, sy = _sm64(xy)
+    kmap = oracle.kl_divergence_2d(p.t().reshape(1, C, P, 1), y.t().reshape(1, C, P, 1), eps=EPS_KL).reshape(P)
+    lqp, lqy = torch.log(p + EPS_KL), torch.log(y + EPS_KL)
+    # per pixel (differing inputs): y and p carry (C + 6 + |x - m|) U relative error, each logf 6U|log q| + U, the products and the
+    # two C-term sums U each, the subtraction U on the magnitudes; identical inputs give exactly 0 on both sides
+    b = torch.where(same, torch.zeros(()), U * ((C + 12 + sy + sp) * y * (2 + lqy.abs() + lqp.abs())).sum(1))
+    # gradient of the mean w.r.t. the p logits: d = -y / (p + eps); o = g p (d - sum d p)
+    d = -y / (p + EPS_KL)
+    dot = (d * p).sum(1, keepdim=True)
+    gref = gg * p * (d - dot)
+    # d: y's and p's errors and the division, (2C + 14 + |xy - m| + |xp - m|) U relative; the dot C U sum|d p| more
+    rel = (2 * C + 14 + sy + sp) * U
+    gb = abs(gg) * p * (rel * d.abs() + (rel * (d * p).abs()).sum(1, keepdim=True) + C * U * (d * p).abs().sum(1, keepdim=True)) \
+        + (C + 6 + sp) * U * gref.abs() + 4 * U * gref.abs() + 1e-30
+    return kmap, b, gref, gb, p, y
+
+
 @pytest.mark.parametrize("P,C", KL_CASES)
 def test_kl_at_scale(ops, P, C):
     """KL(y || p): the background has p and y from identical logits (per-pixel KL exactly 0 in both arithmetics), every 97th pixel
@@ -405,27 +428,12 @@ def test_kl_at_scale(ops, P, C):
     xy[sen, 1] = MARGIN_SAT
     same = (xp == xy).all(1)
 
-    p, sp = _sm64(xp)
-    y, sy = _sm64(xy)
-    kmap = oracle.kl_divergence_2d(p.t().reshape(1, C, P, 1), y.t().reshape(1, C, P, 1), eps=EPS_KL).reshape(P)
-    ref = kmap.mean().item()
-    lqp, lqy = torch.log(p + EPS_KL), torch.log(y + EPS_KL)
-    # per pixel (differing inputs): y and p carry (C + 6 + |x - m|) U relative error, each logf 6U|log q| + U, the products and the
-    # two C-term sums U each, the subtraction U on the magnitudes; identical inputs give exactly 0 on both sides
-    b = torch.where(same, torch.zeros(()), U * ((C + 12 + sy + sp) * y * (2 + lqy.abs() + lqp.abs())).sum(1))
-    tol = (b.sum().item() + SUM_DEPTH * U * kmap.abs().sum().item()) / P + 2 * U * abs(ref)
-    assert kmap[sen].min().item() / P > 4 * tol and (kmap[same] == 0).all()
-
-    # gradient of the mean w.r.t. the p logits: d = -y / (p + eps); o = g p (d - sum d p)
     gscale, gmul = 0.5, 2.0
     gg = float(np.float32(gscale)) * gmul / P
-    d = -y / (p + EPS_KL)
-    dot = (d * p).sum(1, keepdim=True)
-    gref = gg * p * (d - dot)
-    # d: y's and p's errors and the division, (2C + 14 + |xy - m| + |xp - m|) U relative; the dot C U sum|d p| more
-    rel = (2 * C + 14 + sy + sp) * U
-    gb = abs(gg) * p * (rel * d.abs() + (rel * (d * p).abs()).sum(1, keepdim=True) + C * U * (d * p).abs().sum(1, keepdim=True)) \
-        + (C + 6 + sp) * U * gref.abs() + 4 * U * gref.abs() + 1e-30
+    kmap, b, gref, gb, p, y = _kl_ref(xp, xy, C, gg)
+    ref = kmap.mean().item()
+    tol = (b.sum().item() + SUM_DEPTH * U * kmap.abs().sum().item()) / P + 2 * U * abs(ref)
+    assert kmap[sen].min().item() / P > 4 * tol and (kmap[same] == 0).all()
 
     xpg, xyg = xp.to(DEV), xy.to(DEV)
     gs = torch.tensor([gscale], device=DEV)

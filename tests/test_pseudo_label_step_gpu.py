@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from helpers import FakeLoader, batches  # noqa: E402
 from test_step_gpu import _trainer as _step_trainer  # noqa: E402
-from test_weighted_step_gpu import DEV, _one_step  # noqa: E402
+from test_weighted_step_gpu import DEV, _moments_agree, _one_step  # noqa: E402
 
 # Golden set-up, criterion, threshold of the fused-vs-generic comparison.  g5_step_enet_adv (B = 2, 64 x 64, C = 4: P = 8,192 unlabeled
 # pixels, two views): its untrained networks spread their confidences over 0.27 .. 0.86, so that a threshold can mask a part of the
@@ -96,6 +96,7 @@ def test_pl_fused_and_generic_paths_agree(golden, tmp_path, fused_steps, tag, na
     np.testing.assert_allclose(a["adv"].item(), b["adv"].item(), rtol=1e-4)
     for x, y in zip(wa, wb):
         np.testing.assert_allclose(x[1:], y[1:], rtol=1e-5)
+    _moments_agree(wa, wb)
 
 
 def test_pseudo_labels_reach_the_fused_step(fused_steps):

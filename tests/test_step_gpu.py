@@ -137,13 +137,19 @@ def test_fused_and_generic_paths_agree(golden, tmp_path):
         lb = [lab[i][0][0] for i in range(2)]
         out = tr._run_step([(lb[0][0], lb[0][1]), (lb[1][0], lb[1][1])], (unl[0][0][0], unl[0][0][1]), True, True, (0, 1))
         w = [digest(torch.cat([p.detach().flatten() for p in s.torchnet.parameters()])) for s in tr.segmentators]
-        outs.append((out, w))
-    (a, wa), (b, wb) = outs
+        # Adam's first update moves every weight by lr * sign(g): the weights cannot show a wrong gradient scale, the first moments
+        # (0.1 x the step's total gradient) do -- per parameter tensor, their l2 norm
+        m = [np.array([digest(s.optimizer.state[p]["exp_avg"])[2] for p in s.torchnet.parameters()]) for s in tr.segmentators]
+        outs.append((out, w, m))
+    (a, wa, ma), (b, wb, mb) = outs
     np.testing.assert_allclose([s.item() for s in a["sup"]], [s.item() for s in b["sup"]], rtol=1e-6)
     np.testing.assert_allclose(a["jsd"].item(), b["jsd"].item(), rtol=1e-5)
     np.testing.assert_allclose(a["adv"].item(), b["adv"].item(), rtol=1e-4)
     for x, y in zip(wa, wb):
         np.testing.assert_allclose(x[1:], y[1:], rtol=1e-5)
+    for x, y in zip(ma, mb):        # the UNet band of test_train_loop_fp32_matches_reference_golden
+        assert x.shape == y.shape and len(x) > 10 and np.all(np.isfinite(x)) and x.max() > 1e-6
+        np.testing.assert_allclose(x, y, rtol=2e-2, atol=1e-9)
 
 
 def test_bf16_step_tracks_oracle(tmp_path, golden):

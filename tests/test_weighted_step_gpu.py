@@ -40,12 +40,34 @@ def _trainer(tmp_path, g, n_steps, fused=True, **ce):
     return tr, lab, unl
 
 
+class _Digests(list):
+    """The weight digests of ``_one_step`` with, as ``moments``, the l2 norm of Adam's first moment per model and parameter tensor."""
+    moments = None
+
+
+def _first_moments(tr):
+    """Per model: the l2 norm of ``exp_avg`` of every parameter tensor.  After the first step that is 0.1 x the step's total gradient:
+    unlike the weights (which Adam's first update moves by lr * sign(g)) it shows a wrong scale of any gradient term."""
+    return [np.array([digest(s.optimizer.state[p]["exp_avg"])[2] for p in s.torchnet.parameters()]) for s in tr.segmentators]
+
+
+def _moments_agree(wa, wb):
+    """tests/test_step_gpu.py::test_train_loop_fp32_matches_reference_golden's UNet band for the first moments, per parameter tensor."""
+    assert len(wa.moments) == len(wb.moments) == 2
+    for x, y in zip(wa.moments, wb.moments):
+        assert x.shape == y.shape and len(x) > 10 and np.all(np.isfinite(x)) and x.max() > 1e-6
+        print(f"first moments of {len(x)} parameter tensors: norms {x.min():.3e} .. {x.max():.3e}, largest deviation "
+              f"{np.max(np.abs(x - y) / (2e-2 * np.abs(y) + 1e-9)):.3f} of the band")
+        np.testing.assert_allclose(x, y, rtol=2e-2, atol=1e-9)
+
+
 def _one_step(tr, lab, unl):
     for s in tr.segmentators:
         s.train()
     lb = [lab[i][0][0] for i in range(2)]
     out = tr._run_step([(lb[0][0], lb[0][1]), (lb[1][0], lb[1][1])], (unl[0][0][0], unl[0][0][1]), True, True, (0, 1))
-    w = [digest(torch.cat([p.detach().flatten() for p in s.torchnet.parameters()])) for s in tr.segmentators]
+    w = _Digests(digest(torch.cat([p.detach().flatten() for p in s.torchnet.parameters()])) for s in tr.segmentators)
+    w.moments = _first_moments(tr)
     return out, w
 
 
@@ -71,6 +93,7 @@ def test_weighted_fused_and_generic_paths_agree(golden, tmp_path, weighted_fused
     np.testing.assert_allclose(a["adv"].item(), b["adv"].item(), rtol=1e-4)
     for x, y in zip(wa, wb):
         np.testing.assert_allclose(x[1:], y[1:], rtol=1e-5)
+    _moments_agree(wa, wb)
 
 
 def test_weights_reach_the_fused_step(golden, tmp_path, weighted_fused_step):
