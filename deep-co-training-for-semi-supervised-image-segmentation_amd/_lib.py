@@ -156,6 +156,9 @@ SIGNATURES = {
     "dct_fgsm_step": (_i, [_P, _P, _f, _P, _P, _i64, _P]),
     "dct_adam_flat": (_i, [_P, _P, _P, _P, _i64, _f, _f, C.c_double, C.c_double, _f, _f, _f, _P, _P]),
     "dct_adam_flat_dev": (_i, [_P, _P, _P, _P, _i64, _P, _P, C.c_double, C.c_double, _f, _f, _f, _P, _P]),
+    "dct_grad_sumsq_workspace_bytes": (_sz, [_i64]),
+    "dct_grad_sumsq": (_i, [_P, _i64, _P, _sz, _P]),
+    "dct_adam_flat_dev_guarded": (_i, [_P, _P, _P, _P, _i64, _P, _P, C.c_double, C.c_double, _f, _f, _f, _P, _P, _sz, _P, _i, _i, _P]),
     "dct_enet_conv": (_i, [_VP, _P, _P, _TP, _VP, _DP, _i, _i, _i, _i, _VP, _VP, _i, _i, _P]),
     "dct_enet_reduce_workspace_bytes": (_sz, [_i]),
     "dct_enet_bn_fwd_stats": (_i, [_VP, _P, _P, _f, _f, _P, _P, _i, _P, _P, _P, _P, _P, _i, _i, _P, _sz, _P]),

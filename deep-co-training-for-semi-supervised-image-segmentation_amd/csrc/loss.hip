@@ -1219,9 +1219,9 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, flo
 // host value: table[2*(t-base-1)] = {1 - beta1^t, sqrt(1 - beta2^t)} as the HOST computed them (doubles; the step size
 // lr / bc1 is then the same correctly rounded division the host does: bit-identical to the scalar-argument path, and a
 // learning-rate change touches only state[1]); outside the table they are formed here in double.
-__global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, long long n, float step_size,
-                                                    float bc2s, float omb1, float b2, float omb2, float eps, float wd, float gs, bf16_t* shadow,
-                                                    const double* state, const double* table, double beta1, double beta2) {
+__device__ __forceinline__ void adam_body(float* p, const float* g, float* m, float* v, long long n, float step_size,
+                                          float bc2s, float omb1, float b2, float omb2, float eps, float wd, float gs, bf16_t* shadow,
+                                          const double* state, const double* table, double beta1, double beta2) {
   if (state) {
     const double t = state[0], lr = state[1];
     const long long idx = (long long)t - (long long)state[2] - 1;
@@ -1259,8 +1259,90 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     if (shadow) shadow[i] = (bf16_t)pp;
   }
 }
+__global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, long long n, float step_size,
+                                                    float bc2s, float omb1, float b2, float omb2, float eps, float wd, float gs, bf16_t* shadow,
+                                                    const double* state, const double* table, double beta1, double beta2) {
+  adam_body(p, g, m, v, n, step_size, bc2s, omb1, b2, omb2, eps, wd, gs, shadow, state, table, beta1, beta2);
+}
 
 __global__ void adam_advance_kernel(double* state) { state[0] += 1.0; }
+
+// ---- the guard in front of the update (dct_adam_guard, include/dct.h) ------------------------------------------------------------
+// Sum of squares of g[0..n), one double partial per block.  A finite fp32 squared is exact in double and cannot overflow there, so a
+// partial is non-finite iff its block read an inf or a NaN (squares are >= 0 or NaN: +inf and -inf cannot cancel).  One read of the
+// buffer at full occupancy (8 blocks of 256 per CU at the largest grid), two 16-byte loads in flight per thread; each thread adds its
+// elements in ascending order, the block folds lanes (xor 32 .. 1), then its four waves in order: the same buffer gives the same bits.
+constexpr int kSumsqMaxBlocks = 2048;
+static inline unsigned sumsq_grid(long long n) {
+  long long b = (n / 4 + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b > kSumsqMaxBlocks ? kSumsqMaxBlocks : b));
+}
+__device__ __forceinline__ void sumsq4(double& acc, const f32x4 gv) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { const double d = (double)gv[k]; acc = fma(d, d, acc); }
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, long long n, double* partials) {
+  __shared__ double sw[4];
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+  const long long n4 = n / 4, stride = (long long)gridDim.x * 256;
+  double acc = 0.0;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + stride < n4; i += 2 * stride) {
+    const f32x4 a = g4[i], b = g4[i + stride];
+    sumsq4(acc, a);
+    sumsq4(acc, b);
+  }
+  if (i < n4) sumsq4(acc, g4[i]);
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const double d = (double)g[n4 * 4 + threadIdx.x]; acc = fma(d, d, acc); }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((sw[0] + sw[1]) + sw[2]) + sw[3];
+}
+
+// One block of 256: thread t adds partials t, t + 256, ... in ascending order, a halving tree (128 .. 1) folds the 256 sums; thread 0
+// takes the decision, writes the record and advances the step count unless the step is skipped (takes adam_advance_kernel's place).
+__global__ __launch_bounds__(256) void adam_guard_kernel(const double* partials, int nparts, double* state, dct_adam_guard* guard,
+                                                         float gs, int skip_nonfinite, int clip) {
+  __shared__ double sm[256];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int k = t; k < nparts; k += 256) s += partials[k];
+  sm[t] = s;
+  __syncthreads();
+#pragma unroll
+  for (int off = 128; off > 0; off >>= 1) {
+    if (t < off) sm[t] += sm[t + off];
+    __syncthreads();
+  }
+  if (t != 0) return;
+  const double sum = sm[0];
+  const double norm = fabs((double)gs) * sqrt(sum);
+  const bool skip = skip_nonfinite && !isfinite(sum);
+  float coef = 1.f;
+  if (clip && !skip) {
+    const double c = guard->max_norm / (norm + 1e-6);   // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
+    coef = (float)(c > 1.0 ? 1.0 : c);                  // a NaN stays a NaN, as under torch's clamp
+    if (!(c >= 1.0)) guard->clipped += 1;
+  }
+  guard->norm = norm;
+  guard->coef = coef;
+  guard->skip = skip ? 1u : 0u;
+  if (skip) guard->skipped += 1;
+  else state[0] += 1.0;
+}
+
+// adam_kernel behind a guard record that the previous launch on the stream wrote: a skipped step returns before its first load, any
+// other multiplies the gradient scale by the clip coefficient (one fp32 multiply) and is adam_kernel's table path from there on.
+__global__ __launch_bounds__(256) void adam_guarded_kernel(float* p, const float* g, float* m, float* v, long long n,
+                                                           float omb1, float b2, float omb2, float eps, float wd, float gs, bf16_t* shadow,
+                                                           const double* state, const double* table, double beta1, double beta2,
+                                                           const dct_adam_guard* guard) {
+  if (guard->skip) return;
+  gs *= guard->coef;
+  adam_body(p, g, m, v, n, 0.f, 1.f, omb1, b2, omb2, eps, wd, gs, shadow, state, table, beta1, beta2);
+}
 
 static inline unsigned grid_for(long long P) {
   long long b = (P + 255) / 256;
@@ -1796,5 +1878,33 @@ extern "C" int dct_adam_flat_dev(float* p, const float* g, float* m, float* v, i
   DCT_LAUNCH(DCT_PROF_ADAM, adam_kernel, dim3(wide_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n,
              0.f, 1.f, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, weight_decay, grad_scale, (bf16_t*)bf16_shadow,
              (const double*)state, table, beta1, beta2);
+  return dct_check_launch();
+}
+
+extern "C" size_t dct_grad_sumsq_workspace_bytes(int64_t n) { return n < 1 ? 0 : (size_t)sumsq_grid(n) * sizeof(double); }
+
+extern "C" int dct_grad_sumsq(const float* g, int64_t n, void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!g || !workspace || n < 1) return DCT_ERR_BAD_ARG;
+  if (((uintptr_t)g & 15) || ((uintptr_t)workspace & 7)) return DCT_ERR_UNSUPPORTED;
+  if (workspace_bytes < dct_grad_sumsq_workspace_bytes(n)) return DCT_ERR_WORKSPACE;
+  DCT_LAUNCH(DCT_PROF_ADAM, grad_sumsq_kernel, dim3(sumsq_grid(n)), dim3(256), 0, (hipStream_t)stream, g, (long long)n, (double*)workspace);
+  return dct_check_launch();
+}
+
+extern "C" int dct_adam_flat_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n, double* state,
+                                         const double* table, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                                         void* bf16_shadow, void* workspace, size_t workspace_bytes, dct_adam_guard* guard,
+                                         int skip_nonfinite, int clip, dct_stream stream) {
+  if (!p || !g || !m || !v || !state || !workspace || !guard || n < 1) return DCT_ERR_BAD_ARG;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DCT_ERR_UNSUPPORTED;
+  if (bf16_shadow && ((uintptr_t)bf16_shadow & 7)) return DCT_ERR_UNSUPPORTED;
+  if (((uintptr_t)state | (uintptr_t)workspace | (uintptr_t)guard) & 7) return DCT_ERR_UNSUPPORTED;
+  if (workspace_bytes < dct_grad_sumsq_workspace_bytes(n)) return DCT_ERR_WORKSPACE;
+  DCT_LAUNCH(DCT_PROF_ADAM, grad_sumsq_kernel, dim3(sumsq_grid(n)), dim3(256), 0, (hipStream_t)stream, g, (long long)n, (double*)workspace);
+  DCT_LAUNCH(DCT_PROF_ADAM, adam_guard_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, (int)sumsq_grid(n),
+             state, guard, grad_scale, skip_nonfinite, clip);
+  DCT_LAUNCH(DCT_PROF_ADAM, adam_guarded_kernel, dim3(wide_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n,
+             (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, weight_decay, grad_scale, (bf16_t*)bf16_shadow,
+             (const double*)state, table, beta1, beta2, (const dct_adam_guard*)guard);
   return dct_check_launch();
 }

@@ -21,6 +21,10 @@ gradients summed onto device 0.  The MI355X-native equivalent here:
     use that form, so this is caution, but it is free: fused-Adam models get the factor folded into the optimizer's
     ``grad_scale`` (no launch, ``defer_average``); everything else is scaled in its buffer by ``dct_flat_scale``.
     The algorithm choice stays RCCL's (``prefer_ring()`` is there for the cautious);
+  * a guarded fused Adam (``max_grad_norm`` / ``skip_nonfinite``, optim.py) takes its gradient norm AFTER ``finish(i)``, on the exchanged
+    buffer, with the 1/world of ``grad_scale`` inside the norm: it is the norm of the averaged gradient, every rank reads the same bits and
+    therefore clips by the same coefficient and skips the same steps -- the ranks' weights stay identical without a collective for the
+    decision (tested on one rank through the ``grad_scale`` composition; no multi-rank run of it yet);
   * BatchNorm buffers stay per-rank (what DataParallel replicas do); FGSM's input-gradient pass
     produces no parameter gradients and therefore never touches the exchange.
 

@@ -812,6 +812,46 @@ def adam_flat_dev(p, g, m, v, state, table, beta1, beta2, eps, weight_decay, bf1
     return p
 
 
+GUARD_WORDS = 5     # dct_adam_guard (include/dct.h) as five 64-bit words: norm, max_norm, {coef, skip}, skipped, clipped
+
+
+def grad_sumsq_workspace(n, device):
+    """Workspace of grad_sumsq / adam_flat_dev_guarded for an n-element buffer: one float64 partial per block."""
+    return torch.empty(_lib.load().dct_grad_sumsq_workspace_bytes(int(n)) // 8, dtype=torch.float64, device=device)
+
+
+def adam_guard_record(device, max_norm=0.0):
+    """A zeroed dct_adam_guard on ``device`` (an int64[5] tensor; read it through guard_fields) with ``max_norm`` set."""
+    rec = torch.zeros(GUARD_WORDS, dtype=torch.int64, device=device)
+    rec[1:2].view(torch.float64).fill_(float(max_norm))
+    return rec
+
+
+def guard_fields(rec):
+    """Views of a dct_adam_guard record: norm, max_norm (float64[1]), coef (float32[1]), skip (int32[1]), skipped, clipped (int64[1])."""
+    return dict(norm=rec[0:1].view(torch.float64), max_norm=rec[1:2].view(torch.float64), coef=rec[2:3].view(torch.float32)[0:1],
+                skip=rec[2:3].view(torch.int32)[1:2], skipped=rec[3:4], clipped=rec[4:5])
+
+
+def grad_sumsq(g, workspace=None):
+    """The float64 per-block partial sums of g^2 (dct_grad_sumsq): their sum is ||g||^2, non-finite iff g holds an inf or a NaN."""
+    if workspace is None:
+        workspace = grad_sumsq_workspace(g.numel(), g.device)
+    call("dct_grad_sumsq", ptr(g), g.numel(), ptr(workspace), workspace.numel() * workspace.element_size(), stream())
+    return workspace
+
+
+def adam_flat_dev_guarded(p, g, m, v, state, table, beta1, beta2, eps, weight_decay, workspace, guard, bf16_shadow=None, grad_scale=1.0,
+                          skip_nonfinite=False, clip=False):
+    """adam_flat_dev behind the guard (dct_adam_flat_dev_guarded): the gradient norm is taken on the device, ``guard`` (adam_guard_record)
+    receives it with the decision, and the update is clipped to the record's max_norm (``clip``) or left out altogether when the
+    gradient holds an inf or a NaN (``skip_nonfinite``) -- the step count in state[0] then stays too."""
+    call("dct_adam_flat_dev_guarded", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(state), ptr(table), float(beta1), float(beta2),
+         float(eps), float(weight_decay), float(grad_scale), ptr(bf16_shadow), ptr(workspace),
+         workspace.numel() * workspace.element_size(), ptr(guard), int(bool(skip_nonfinite)), int(bool(clip)), stream())
+    return p
+
+
 def dice_counts(logits_bpc, gt_bp, B, C_):
     """logits [B, pix, C] fp32 dense, gt [B, pix] int64 -> (inter, psum, gsum) int32 [B, C]."""
     dev = logits_bpc.device

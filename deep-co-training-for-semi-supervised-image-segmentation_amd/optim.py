@@ -4,6 +4,11 @@ reference constructs it (models/segmentators.py:37-43; config/ACDC_config_cotrai
 Same hyper-parameters, same update rule (L2 weight decay folded into the gradient, bias
 correction as torch 2.x), same ``state_dict`` layout (per-parameter ``step`` / ``exp_avg`` /
 ``exp_avg_sq``) -- but ONE kernel launch per network instead of hundreds of tiny ones.
+
+Optional guard in front of the update (off by default; dct_adam_flat_dev_guarded): ``max_grad_norm`` clips the network's gradient to that
+norm as ``torch.nn.utils.clip_grad_norm_`` does before ``step()``, ``skip_nonfinite`` leaves out the whole step -- weights, moments and
+step count -- when the gradient holds an inf or a NaN, as ``torch.cuda.amp.GradScaler`` does.  Norm and decision are taken and consumed
+on the device, so a guarded step is replayed from a captured graph like a plain one.
 """
 from __future__ import annotations
 
@@ -18,9 +23,16 @@ from .arch.flat import FlatParams
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, flat: FlatParams = None,
-                 on_step=None):
+                 on_step=None, max_grad_norm=None, skip_nonfinite=False):
         if flat is None:
             raise ValueError("FusedAdam needs the network's FlatParams (use net.flat_params)")
+        self.max_grad_norm = self._checked_max_norm(max_grad_norm)
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f"dct_amd FusedAdam: skip_nonfinite must be True or False, got {skip_nonfinite!r}")
+        self.skip_nonfinite = skip_nonfinite
+        # the guard's device record (dct_adam_guard) and the norm's workspace: allocated once per device, captured graphs hold the addresses
+        self._guard = None
+        self._guard_ws = None
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         plist = [p for g in self.param_groups for p in g["params"]]
@@ -42,6 +54,52 @@ class FusedAdam(torch.optim.Optimizer):
         self._dev_lr = None
         self._table_base = 0
 
+    @staticmethod
+    def _checked_max_norm(x):
+        if x is None:
+            return None
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x <= 0:
+            raise ValueError(f"dct_amd FusedAdam: max_grad_norm must be None or a positive finite number, got {x!r}")
+        return float(x)
+
+    @property
+    def guarded(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _ensure_guard(self, dev):
+        if self._guard is None or self._guard.device != dev:
+            self._guard = hip_ops.adam_guard_record(dev, self.max_grad_norm or 0.0)
+            self._guard_ws = hip_ops.grad_sumsq_workspace(self.flat.total, dev)
+        return self._guard_ws, self._guard
+
+    def set_max_grad_norm(self, x):
+        """Another clipping threshold: one async fill of the device value, no new capture (call between graph replays, as refresh_lr).
+        Clipping itself is switched on or off with None <-> a number, and that IS another capture."""
+        self.max_grad_norm = self._checked_max_norm(x)
+        if self._guard is not None and self.max_grad_norm is not None:
+            hip_ops.guard_fields(self._guard)["max_norm"].fill_(self.max_grad_norm)
+
+    @property
+    def last_grad_norm(self):
+        """The gradient norm the last guarded step saw (of the unscaled, averaged gradient), as a float64 device scalar: reading the
+        attribute does not synchronise.  None before the first guarded step."""
+        return None if self._guard is None else hip_ops.guard_fields(self._guard)["norm"][0]
+
+    def guard_counts(self) -> dict:
+        """{'skipped': steps left out for a non-finite gradient, 'clipped': steps whose gradient was scaled down}.  Synchronises:
+        meant for once an epoch."""
+        if self._guard is None:
+            return {"skipped": 0, "clipped": 0}
+        skipped, clipped = self._guard[3:5].tolist()
+        return {"skipped": int(skipped), "clipped": int(clipped)}
+
+    def _reconcile_steps(self):
+        """With a guard the device's step count is the truth: a skipped step does not advance it, while step() and every replay bump the
+        host's ``_steps``.  Between two calls of this the host count may be too high, which is harmless -- the kernel enters the
+        bias-correction table with the device's t, and a host count that is too high only asks for the rebuild early.  Synchronises."""
+        if self.guarded and self._dev_state is not None:
+            self._steps = int(self._dev_state[0].item())
+
     def _state_views(self):
         f = self.flat
         for p, off in zip(f.params, f.offsets):
@@ -60,6 +118,8 @@ class FusedAdam(torch.optim.Optimizer):
         (a per-step schedule costs nothing more).  Never inside a captured graph."""
         lr = float(lr)
         fresh = self._dev_state is None or self._dev_state.device != dev
+        if not fresh and self._steps + 1 > self._table_base + self.TABLE_STEPS:
+            self._reconcile_steps()         # after skipped steps the table may not be exhausted yet; if it is, its new base is the device's count
         if not fresh and self._steps + 1 <= self._table_base + self.TABLE_STEPS:
             if lr != self._dev_lr:
                 self._dev_state[1:2].fill_(lr)
@@ -106,6 +166,7 @@ class FusedAdam(torch.optim.Optimizer):
         # (e.g. after load_state_dict of a reference checkpoint or after .to(device))
         m = torch.zeros(f.total, dtype=torch.float32, device=dev)
         v = torch.zeros(f.total, dtype=torch.float32, device=dev)
+        self._reconcile_steps()         # the device state is dropped below
         steps = self._steps
         if self._import_steps:          # load_state_dict: the loaded moments come with THEIR step count (torch.optim.Adam
             steps = 0                   # takes the loaded one too); one flat kernel = one count, the largest loaded
@@ -134,8 +195,14 @@ class FusedAdam(torch.optim.Optimizer):
         state = self._ensure_dev_state(f.flat.device, g["lr"])
         self._steps += 1                    # the kernel increments the device copy in stream order
         shadow = f.ensure_shadow() if f.want_shadow else None
-        hip_ops.adam_flat_dev(f.flat, f.gflat, self._m, self._v, state, self._dev_table, b1, b2, g["eps"],
-                              g["weight_decay"], bf16_shadow=shadow, grad_scale=self.grad_scale)
+        if self.guarded:
+            ws, guard = self._ensure_guard(f.flat.device)
+            hip_ops.adam_flat_dev_guarded(f.flat, f.gflat, self._m, self._v, state, self._dev_table, b1, b2, g["eps"],
+                                          g["weight_decay"], ws, guard, bf16_shadow=shadow, grad_scale=self.grad_scale,
+                                          skip_nonfinite=self.skip_nonfinite, clip=self.max_grad_norm is not None)
+        else:
+            hip_ops.adam_flat_dev(f.flat, f.gflat, self._m, self._v, state, self._dev_table, b1, b2, g["eps"],
+                                  g["weight_decay"], bf16_shadow=shadow, grad_scale=self.grad_scale)
         self._shadow_written = shadow is not None
         self._notify_step()
         return loss
@@ -157,11 +224,12 @@ class FusedAdam(torch.optim.Optimizer):
         super().load_state_dict(state_dict)
         self._m = None  # force re-import of the loaded per-parameter moments
         self._import_steps = True
-        self._dev_state = None
+        self._dev_state = None          # (a guard's device count goes with it: the loaded count is the truth from here on)
         steps = [int(float(st.get("step", 0))) for st in self.state.values() if isinstance(st, dict)]
         self._steps = max(steps) if steps else 0
 
     def state_dict(self):
         if self._m is not None:
+            self._reconcile_steps()     # after k skipped steps a checkpoint says steps - k, as torch's would
             self._state_views()         # refreshes the per-parameter "step" entries from the host count
         return super().state_dict()

@@ -1141,6 +1141,10 @@ class CoTrainer(Trainer):
         unlab_dsc_dict = self._dsc_dict(unlabdiceMeters)
         self.upload_dicts('labeled dataset', lab_dsc_dict, epoch)
         self.upload_dicts('unlabeled dataset', unlab_dsc_dict, epoch)
+        # guarded optimizers (FusedAdam max_grad_norm / skip_nonfinite): steps skipped and clipped so far, read once an epoch (one sync each)
+        guard_dict = {f"S{i}": s.optimizer.guard_counts() for i, s in enumerate(self.segmentators) if getattr(s.optimizer, "guarded", False)}
+        if guard_dict:
+            self.upload_dicts('optimizer guard', guard_dict, epoch)
         nice_dict = self._report_dict(diceMeters)
         if self._is_main():
             print(f"{desc} " + ', '.join([f'{k}_{k_}:{v[k_]:.2f}' for k, v in nice_dict.items() for k_ in v.keys()]))

@@ -87,7 +87,11 @@ class StepGraphCache(object):
                         fp.gflat.data_ptr() if fp.gflat is not None else 0,
                         opt._m.data_ptr() if getattr(opt, "_m", None) is not None else 0,
                         getattr(net, "external_dropout_masks", None) is None,
-                        bool(getattr(net, "record_dropout_masks", False))))
+                        bool(getattr(net, "record_dropout_masks", False)),
+                        # the optimizer's guard: its record's address (0 when off) and the two switches are launch arguments, so
+                        # switching it is another capture; max_grad_norm is read on the device, so changing it is not
+                        opt._guard.data_ptr() if getattr(opt, "_guard", None) is not None and opt.guarded else 0,
+                        getattr(opt, "max_grad_norm", None) is not None, bool(getattr(opt, "skip_nonfinite", False))))
         # the supervised criterion's launch arguments: another criterion (ignore_index, weight buffer; for CE + Dice its module type, the
         # two coefficients, mask, smooth and per_image) is another capture; the weights themselves are read on the device, so changing
         # them in place is not

@@ -503,6 +503,43 @@ int dct_adam_flat_dev(float* p, const float* g, float* m, float* v, int64_t n, d
                       const double* table, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
                       void* bf16_shadow, dct_stream stream);
 
+/* The guard in front of the update: gradient-norm clipping (torch.nn.utils.clip_grad_norm_) and the skipped step of a non-finite
+ * gradient (torch.cuda.amp.GradScaler), decided and consumed on the device so that the step stays one replayable graph.
+ *
+ * dct_grad_sumsq: workspace[b] = the sum of g[i]^2 over block b's elements, squared and added in DOUBLE (a finite fp32 squared is exact
+ * and cannot overflow there: the sum is non-finite iff some g[i] is inf or NaN; 1e30 is a large gradient, not an overflow).  The number
+ * of blocks, dct_grad_sumsq_workspace_bytes(n) / 8 = clamp(ceil(floor(n / 4) / 256), 1, 2048), depends on n alone and every fold has a
+ * fixed order (no float atomics): the same buffer gives the same bits on every run, eager or replayed.  g and workspace as below.
+ *
+ * dct_adam_flat_dev_guarded: three stream-ordered launches.  (1) dct_grad_sumsq into `workspace`.  (2) One block folds the partials in
+ * double (thread t of 256 adds partials t, t + 256, ... in ascending order, a halving tree folds the 256 sums) and writes `guard`:
+ *     norm = |grad_scale| * sqrt(sum)     the norm of the gradient the update sees (of the averaged one when grad_scale carries 1 / world)
+ *     skip = skip_nonfinite && !isfinite(sum);   skipped += skip
+ *     coef = 1 when clip == 0 or skip, else (float)min(1, max_norm / (norm + 1e-6)) formed in double, with max_norm READ FROM THE RECORD
+ *            (a schedule of it is one async fill, never a recapture); a NaN quotient stays NaN and an infinite norm gives 0, as in torch;
+ *            clipped += the quotient is not >= 1
+ *     state[0] += 1 unless skip           (torch does not count a skipped step)
+ * (3) The update of dct_adam_flat_dev with grad_scale * coef (one fp32 multiply) in grad_scale's place -- weight decay is added after
+ * the clip, as in torch -- or, when skip, nothing: p, m, v and the shadow keep every bit.  With clip == 0 and skip_nonfinite == 0, or
+ * with a max_norm that is never reached, p, m, v, the shadow and state[0] are bit-identical to dct_adam_flat_dev's.
+ * The caller zeroes the record once, sets max_norm and leaves the rest to the device.
+ * DCT_ERR_BAD_ARG: a null pointer (bf16_shadow and table may be null), n < 1; DCT_ERR_UNSUPPORTED: p, g, m, v not 16-byte aligned,
+ * state, workspace or guard not 8-byte aligned; DCT_ERR_WORKSPACE: less than dct_grad_sumsq_workspace_bytes(n). */
+typedef struct dct_adam_guard {
+  double   norm;      /* out: gradient norm of the last step */
+  double   max_norm;  /* in:  clipping threshold (read when clip != 0) */
+  float    coef;      /* out: the factor the last step put on its gradients */
+  uint32_t skip;      /* out: 1 when the last step was skipped */
+  uint64_t skipped;   /* running totals since the caller zeroed the record */
+  uint64_t clipped;
+} dct_adam_guard;     /* 40 bytes */
+size_t dct_grad_sumsq_workspace_bytes(int64_t n);
+int dct_grad_sumsq(const float* g, int64_t n, void* workspace, size_t workspace_bytes, dct_stream stream);
+int dct_adam_flat_dev_guarded(float* p, const float* g, float* m, float* v, int64_t n, double* state,
+                              const double* table, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                              void* bf16_shadow, void* workspace, size_t workspace_bytes, dct_adam_guard* guard,
+                              int skip_nonfinite, int clip, dct_stream stream);
+
 /* ---- K2/K3/K4/K6/K7/K8: Enet layers (arch/enet.py:8-243) -------------------------------------
  * Enet's widths are 1..128 channels (internal 3/16/32): HBM- and launch-bound, so these are direct
  * fused kernels, not GEMMs.  Every consumer reads its input through the producer's BatchNorm +
