@@ -192,6 +192,8 @@ SIGNATURES = {
     "dct_hausdorff": (_i, [_P, _P, _i, _i, _i, _i, _i, _f, _f, _f, _P, _P, _sz, _P]),
     "dct_confusion_counts": (_i, [_P, _i, _P, _i, _i64, _i, _P, _P]),
     "dct_calibration_counts": (_i, [_P, _i, _P, _i, _i64, _i, _i, C.c_uint32, _i, _i, _P, _P, _P]),
+    "dct_temperature_sums": (_i, [_P, _i, _P, _i, _i64, _i, C.c_uint32, _i, _P, _i, _P, _P, _P]),
+    "dct_temperature_apply": (_i, [_P, _i, _i, _i64, _i, _P, _i, _P, _P]),
     "dct_components_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "dct_largest_component": (_i, [_P, _i, _i, _i, _i, _i, _i, C.c_uint32, _i, _P, _P, _P, _P, _sz, _P]),
     "dct_tune_set": (_i, [_i, _i]),

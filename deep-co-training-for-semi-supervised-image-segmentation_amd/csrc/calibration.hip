@@ -12,40 +12,12 @@
 // The Brier and NLL words have one cell per rater: every lane keeps them in registers across its pixels, and the wave reduces them
 // once, after the pixel loop.  Everything that leaves the block is an integer: the sums do not depend on their order, the result is
 // bit-identical from run to run.
-#include "dct_common.h"
+#include "calibration_common.h"      // CbPack, cb_load, cb_softmax, CB_DISPATCH_C: shared with temperature.hip
 
 namespace {
 
-constexpr int CB_MAXS = 8;                                  // views; + their mean = 9 raters
-constexpr int CB_MAXR = CB_MAXS + 1;
 constexpr int CB_MAXBINS = 32;
 constexpr float CB_Q = 16777216.0f;                         // 2^24: the fixed-point unit of the confidence, Brier and NLL words
-struct CbPack { const float* in[CB_MAXS]; };                // the S device pointers travel by value (CfPack of confusion.hip)
-
-template <int C> __device__ __forceinline__ void cb_load(const float* p, float v[C]) {
-  if constexpr (C == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else if constexpr (C == 2) {
-    const f32x2 t = *reinterpret_cast<const f32x2*>(p);
-    v[0] = t[0]; v[1] = t[1];
-  } else {
-#pragma unroll
-    for (int c = 0; c < C; ++c) v[c] = p[c];
-  }
-}
-
-// p = softmax(x) in fp32, max-subtracted, the sum in class order, a true division (include/dct.h)
-template <int C> __device__ __forceinline__ void cb_softmax(float v[C]) {
-  float m = v[0];
-#pragma unroll
-  for (int c = 1; c < C; ++c) m = fmaxf(m, v[c]);
-  float sum = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) { v[c] = expf(v[c] - m); sum += v[c]; }
-#pragma unroll
-  for (int c = 0; c < C; ++c) v[c] = v[c] / sum;
-}
 
 // Sum of v over the 64 lanes of a wave that is wholly active, the same value in every lane.  DPP adds in the vector ALU: a scan
 // inside each row of 16 (row_shr 1, 2, 4, 8, zero fill), then lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15) and lane 31 into
@@ -198,18 +170,6 @@ __global__ __launch_bounds__(256) void calibration_kernel(CbPack pk, int S, int 
 }
 
 }  // namespace
-
-#define CB_DISPATCH_C(Cv, ...)                                       \
-  switch (Cv) {                                                      \
-    case 1: { constexpr int C = 1; __VA_ARGS__; } break;             \
-    case 2: { constexpr int C = 2; __VA_ARGS__; } break;             \
-    case 3: { constexpr int C = 3; __VA_ARGS__; } break;             \
-    case 4: { constexpr int C = 4; __VA_ARGS__; } break;             \
-    case 5: { constexpr int C = 5; __VA_ARGS__; } break;             \
-    case 6: { constexpr int C = 6; __VA_ARGS__; } break;             \
-    case 7: { constexpr int C = 7; __VA_ARGS__; } break;             \
-    default: { constexpr int C = 8; __VA_ARGS__; } break;            \
-  }
 
 extern "C" int dct_calibration_counts(const float* const* probs, int S, const int64_t* gt, int B, int64_t pixels_per_image, int C_,
                                       int n_bins, uint32_t class_mask, int with_ensemble, int from_logits, int64_t* bins,

@@ -991,6 +991,78 @@ def calibration_counts(probs: List[torch.Tensor], gt: torch.Tensor, n_bins: int 
     return bins, scores
 
 
+def _temperature_views(what, logits):
+    """The shape, dtype and alignment handling of ``calibration_counts`` -> (dense fp32 tensors, shape, B, pixels per image, C)."""
+    if not isinstance(logits, (list, tuple)) or len(logits) < 1:
+        raise ValueError(f"{what} needs a list of at least one tensor")
+    shape = logits[0].shape
+    if len(shape) not in (3, 4) or any(t.shape != shape for t in logits):
+        raise ValueError(f"{what} needs tensors of one shape [B, pix, C] or [B, H, W, C], got {[tuple(t.shape) for t in logits]}")
+    ppi = 1
+    for d in shape[1:-1]:
+        ppi *= d
+    return shape, shape[0], ppi, shape[-1]
+
+
+def _dense(t, dtype):
+    ptr(t)                                  # (refuses a CPU tensor before anything is copied)
+    if t.dtype != dtype or not t.is_contiguous():
+        t = t.to(dtype).contiguous()
+    # the kernels read a pixel at a time, 16 bytes at C = 4: a dense view that starts inside its storage gets a copy of its own
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def temperature_sums(logits: List[torch.Tensor], gt: torch.Tensor, betas: torch.Tensor, classes=None, with_ensemble: bool = False,
+                     out=None):
+    """logits: S fp32 tensors [B, pix, C] (or [B, H, W, C]), the logits of S views on one batch; gt [B, pix] (or [B, H, W]) int64;
+    betas [R, K]: K candidate inverse temperatures per rater, R = S + with_ensemble, the last rater being the mean of the views'
+    probabilities, scaled as log(p + 1e-10) -> (sums int64 [R, K, 2], counted int64 [1]): per rater and candidate {sum of nll * 2^20,
+    sum of d nll / d beta * 2^20} over the pixels whose gt lies in ``classes`` (None: every class), and the number of those pixels
+    (``dct_temperature_sums``, include/dct.h).  ``out``: a ``(sums, counted)`` pair of an earlier call, which this one adds to."""
+    shape, B, ppi, C_ = _temperature_views("temperature_sums", logits)
+    if gt is None or gt.numel() != B * ppi:
+        raise ValueError(f"temperature_sums: gt {None if gt is None else tuple(gt.shape)} does not match the logits {tuple(shape)}")
+    classes = list(range(min(C_, 32))) if classes is None else [int(c) for c in classes]
+    if any(not 0 <= c < C_ for c in classes):
+        raise ValueError(f"temperature_sums: classes {classes} must lie in [0, {C_})")
+    mask = sum(1 << c for c in set(classes))
+    R = len(logits) + int(bool(with_ensemble))
+    if betas is None or betas.dim() != 2 or betas.shape[0] != R or not 1 <= betas.shape[1] <= 16:
+        raise ValueError(f"temperature_sums: betas {None if betas is None else tuple(betas.shape)} must be [{R}, K], K in [1, 16]")
+    zs = [_dense(t.detach(), torch.float32) for t in logits]
+    g = _dense(gt, torch.int64)
+    bt = _dense(betas.detach(), torch.float32)
+    K_ = bt.shape[1]
+    if out is None:
+        # one allocation, one zeroing launch: the sums in front, the pixel count behind (both int64)
+        buf = torch.zeros(R * K_ * 2 + 1, dtype=torch.int64, device=zs[0].device)
+        sums, counted = buf[:R * K_ * 2].view(R, K_, 2), buf[R * K_ * 2:]
+    else:
+        sums, counted = out
+        if (sums.dtype != torch.int64 or counted.dtype != torch.int64 or tuple(sums.shape) != (R, K_, 2) or counted.numel() != 1
+                or not sums.is_contiguous()):
+            raise ValueError(f"temperature_sums: out must be (int64 [{R}, {K_}, 2] contiguous, int64 [1])")
+    call("dct_temperature_sums", _ptr_array(zs), len(zs), ptr(g), B, ppi, C_, mask, int(bool(with_ensemble)), ptr(bt), K_, ptr(sums),
+         ptr(counted), stream())
+    return sums, counted
+
+
+def temperature_apply(logits: List[torch.Tensor], betas, with_ensemble: bool = False):
+    """logits: S fp32 tensors [B, pix, C] (or [B, H, W, C]); betas: R = S + with_ensemble inverse temperatures (host numbers) -> a
+    list of R fp32 tensors of the logits' shape: softmax(beta_r * z_r) for the views and, last, softmax(beta_R * log(p_ens + 1e-10))
+    for the mean p_ens of the views' softmax at temperature 1 (``dct_temperature_apply``, include/dct.h)."""
+    shape, B, ppi, C_ = _temperature_views("temperature_apply", logits)
+    R = len(logits) + int(bool(with_ensemble))
+    bs = [float(b) for b in (betas.tolist() if hasattr(betas, "tolist") else betas)]
+    if len(bs) != R:
+        raise ValueError(f"temperature_apply: {len(bs)} inverse temperatures for {R} raters")
+    zs = [_dense(t.detach(), torch.float32) for t in logits]
+    outs = [torch.empty(tuple(shape), dtype=torch.float32, device=zs[0].device) for _ in range(R)]
+    call("dct_temperature_apply", _ptr_array(zs), len(zs), B, ppi, C_, (C.c_float * R)(*bs), int(bool(with_ensemble)), _ptr_array(outs),
+         stream())
+    return outs
+
+
 # ------------------------------------------------------------------------------ Enet family
 class Tf(object):
     """Producer transform act(scale*x + shift) applied by consumers on load (include/dct.h dct_enet_tf)."""

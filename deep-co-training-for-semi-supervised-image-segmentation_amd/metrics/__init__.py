@@ -7,7 +7,8 @@ reference's ``IoU`` / ``ConfusionMatrix`` meters, from the pairwise confusion ma
 ``keep_largest_component`` is the cleaning ACDC-style pipelines apply in front of all of them (``dct_largest_component``), and
 ``ComponentMeter`` reports what it removed.  ``CalibrationMeter`` is the first that uses the values of the probabilities and not only
 their argmax: ECE, MCE, Brier score, NLL, the reliability diagram and the coverage-accuracy curve of every view and of their mean,
-from the integer tables of ``dct_calibration_counts``."""
+from the integer tables of ``dct_calibration_counts``.  ``TemperatureScaler`` is the remedy: one temperature per view and one for their
+mean, fitted by ``solve_temperature`` on the integer sums of ``dct_temperature_sums``, applied by ``dct_temperature_apply``."""
 from __future__ import annotations
 
 import math
@@ -18,7 +19,7 @@ import torch
 from .. import hip_ops as K
 
 __all__ = ["DiceMeter", "HausdorffMeter", "AgreementMeter", "ComponentMeter", "AverageValueMeter", "keep_largest_component", "pair_index",
-           "kappa_of", "iou_of", "CalibrationMeter", "ece_of", "mce_of"]
+           "kappa_of", "iou_of", "CalibrationMeter", "ece_of", "mce_of", "TemperatureScaler", "solve_temperature"]
 
 
 class DiceMeter(object):
@@ -497,6 +498,157 @@ class CalibrationMeter(object):
         """Mean (and std) over the rows of a row's mean ECE over its raters."""
         (mean, std), _ = self.value()
         return {'mECE': mean, 'mVars': std}
+
+
+TEMP_UNIT = float(1 << 20)     # the fixed-point unit of the NLL and gradient sums of dct_temperature_sums
+
+
+def solve_temperature(sum_fn, R, n_candidates=16, rounds=4, log2_range=(-4., 4.)):
+    """The inverse temperature beta = 1 / T of each of R raters that minimises the negative log-likelihood, from pooled sums alone:
+    host float64, no torch device.  ``sum_fn(betas [R, K] float64)`` -> ``(sums [R, K, 2], N)``: per rater and candidate the integer
+    sums {nll * 2^20, d nll / d beta * 2^20} of ``dct_temperature_sums`` (include/dct.h) pooled over the data, and the number of
+    counted pixels.  The gradient sum g is non-decreasing in beta (the NLL is convex in it), so the fit is a root search, and it
+    is fixed so that the result is deterministic: each round places ``n_candidates`` candidates evenly in log2 beta across each rater's
+    bracket, endpoints included (first: ``log2_range``), and keeps the adjacent pair with g_k <= 0 < g_k+1; after ``rounds`` rounds g
+    is interpolated linearly inside the bracket (with exact sums the bracket is then 8 / 15^4 = 1.6e-4 wide in log2 beta at the
+    defaults).  g > 0 at the low end of the first bracket: ``at_bound`` 'low', beta = that end (T = 16); g <= 0 at its high end:
+    'high', beta = that end (T = 1 / 16).  A last call with the candidates {1, beta} gives the mean NLL before and after.  N = 0: NaN
+    everywhere, after one call.  ``sum_fn`` is called ``rounds + 1`` times.
+    -> dict: beta, temperature, nll_before, nll_after [R] float64; at_bound: list of None / 'low' / 'high'; N; curve_temperature,
+    curve_nll [R, K]: the first round's grid, the NLL(T) curve over the whole range."""
+    K_ = int(n_candidates)
+    assert R >= 1 and 2 <= K_ <= 16 and rounds >= 1 and log2_range[0] < log2_range[1], (R, n_candidates, rounds, log2_range)
+    lo, hi = np.full(R, float(log2_range[0])), np.full(R, float(log2_range[1]))
+    bound = [None] * R
+    steps = np.arange(K_, dtype=np.float64) / (K_ - 1)
+    nan = np.full(R, np.nan)
+    fit = None
+    for rnd in range(rounds):
+        grid = lo[:, None] + (hi - lo)[:, None] * steps[None]
+        grid[:, 0], grid[:, -1] = lo, hi                        # the ends are the bracket's own numbers: their sums repeat exactly
+        sums, N = sum_fn(np.exp2(grid))
+        sums, N = np.asarray(sums), int(N)
+        assert sums.shape == (R, K_, 2), sums.shape
+        if rnd == 0:
+            with np.errstate(divide='ignore', invalid='ignore'):
+                curve = (np.exp2(-grid), sums[..., 0].astype(np.float64) / (TEMP_UNIT * N) if N > 0 else np.full((R, K_), np.nan))
+            if N == 0:
+                return dict(beta=nan, temperature=nan.copy(), nll_before=nan.copy(), nll_after=nan.copy(), at_bound=bound, N=0,
+                            curve_temperature=curve[0], curve_nll=curve[1])
+        g = sums[..., 1].astype(np.float64)
+        fit = np.empty(R)
+        for r in range(R):
+            if rnd == 0 and g[r, 0] > 0:
+                bound[r] = 'low'
+            elif rnd == 0 and g[r, -1] <= 0:
+                bound[r] = 'high'
+            if bound[r] is not None:
+                fit[r] = lo[r] if bound[r] == 'low' else hi[r]
+                continue
+            k = next(k for k in range(K_ - 1) if g[r, k] <= 0 < g[r, k + 1])
+            fit[r] = grid[r, k] + (grid[r, k + 1] - grid[r, k]) * (-g[r, k]) / (g[r, k + 1] - g[r, k])
+            lo[r], hi[r] = grid[r, k], grid[r, k + 1]
+    beta = np.exp2(fit)
+    sums, N = sum_fn(np.stack([np.ones(R), beta], 1))
+    nll = np.asarray(sums)[..., 0].astype(np.float64) / (TEMP_UNIT * int(N))
+    return dict(beta=beta, temperature=1.0 / beta, nll_before=nll[:, 0], nll_after=nll[:, 1], at_bound=bound, N=int(N),
+                curve_temperature=curve[0], curve_nll=curve[1])
+
+
+class TemperatureScaler(object):
+    """Temperature scaling of ``n_models`` views and, ``with_ensemble``, of the mean of their probabilities (scaled as
+    log(p_ens + 1e-10): the ensemble is formed first, as ``CalibrationMeter``'s ensemble rater): one temperature per rater, fitted by
+    ``solve_temperature`` on the integer sums of ``dct_temperature_sums`` over the pixels whose gt lies in ``considered_classes``
+    (None: all).  Scaling never changes a hard prediction.  ``fit`` walks its batches ``rounds + 1`` times, one launch per batch and
+    one device->host copy per walk; ``apply`` is one launch (``dct_temperature_apply``)."""
+
+    def __init__(self, C=4, n_models=2, with_ensemble=True, considered_classes=None, rater_names=None, n_candidates=16, rounds=4) -> None:
+        assert 1 <= n_models <= 8, n_models
+        assert 1 <= C <= 8, C
+        assert 2 <= int(n_candidates) <= 16 and int(rounds) >= 1, (n_candidates, rounds)
+        assert considered_classes is None or all(0 <= int(c) < C for c in considered_classes), considered_classes
+        self.C = C
+        self.n_models = n_models
+        self.with_ensemble = bool(with_ensemble)
+        self.considered_classes = None if considered_classes is None else [int(c) for c in considered_classes]
+        self.n_candidates, self.rounds = int(n_candidates), int(rounds)
+        names = list(rater_names) if rater_names is not None else [f"S{i}" for i in range(n_models)]
+        assert len(names) == n_models, names
+        self.raters = names + (["ensemble"] if self.with_ensemble else [])
+        self._fit = None
+
+    def _check(self, logits):
+        if not isinstance(logits, (list, tuple)) or len(logits) != self.n_models:
+            raise RuntimeError(f"dct_amd TemperatureScaler was built for a list of {self.n_models} predictions")
+        if any(not z.is_cuda for z in logits):
+            raise RuntimeError("dct_amd TemperatureScaler counts on the HIP device only (no CPU fallback)")
+
+    def _device_sums(self, batches, betas):
+        R, K_ = betas.shape
+        out, bt = None, None
+        for logits, gt in batches:
+            self._check(logits)
+            if gt is None:
+                raise RuntimeError("dct_amd TemperatureScaler: gt is required")
+            if not gt.is_cuda:
+                raise RuntimeError("dct_amd TemperatureScaler counts on the HIP device only (no CPU fallback)")
+            if bt is None:
+                bt = torch.from_numpy(betas.astype(np.float32)).to(logits[0].device)
+            B = logits[0].shape[0]
+            out = K.temperature_sums([z.detach().permute(0, 2, 3, 1) for z in logits], gt.reshape(B, -1), bt,
+                                     classes=self.considered_classes, with_ensemble=self.with_ensemble, out=out)
+        if out is None:
+            return np.zeros((R, K_, 2), dtype=np.int64), 0
+        row = torch.cat((out[0].flatten(), out[1].flatten())).cpu().numpy()      # ONE device->host copy per walk
+        return row[:-1].reshape(R, K_, 2), int(row[-1])
+
+    def fit(self, batches):
+        """batches: a re-iterable of ``(list of n_models logits [B,C,H,W], gt [B,1,H,W])``, iterated ``rounds + 1`` times."""
+        return self.fit_sums(lambda betas: self._device_sums(batches, betas))
+
+    def fit_sums(self, sum_fn):
+        """The fit from any ``sum_fn`` of ``solve_temperature`` (``fit`` hands it the device sums)."""
+        self._fit = solve_temperature(sum_fn, len(self.raters), n_candidates=self.n_candidates, rounds=self.rounds)
+        return self
+
+    def set_temperature(self, temperatures):
+        """Given temperatures, one per rater, instead of a fit (no NLL, no curve)."""
+        t = np.asarray([float(x) for x in temperatures], dtype=np.float64)
+        R = len(self.raters)
+        if t.shape != (R,) or not (t > 0).all():
+            raise ValueError(f"dct_amd TemperatureScaler: {R} positive temperatures expected, got {temperatures}")
+        nan = np.full(R, np.nan)
+        self._fit = dict(beta=1.0 / t, temperature=t, nll_before=nan, nll_after=nan.copy(), at_bound=[None] * R, N=0,
+                         curve_temperature=np.zeros((R, 0)), curve_nll=np.zeros((R, 0)))
+        return self
+
+    def _get(self, key):
+        if self._fit is None:
+            raise RuntimeError("dct_amd TemperatureScaler: fit() or set_temperature() first")
+        return self._fit[key]
+
+    temperature = property(lambda self: torch.from_numpy(self._get('temperature').copy()))
+    beta = property(lambda self: torch.from_numpy(self._get('beta').copy()))
+    nll_before = property(lambda self: torch.from_numpy(self._get('nll_before').copy()))
+    nll_after = property(lambda self: torch.from_numpy(self._get('nll_after').copy()))
+    at_bound = property(lambda self: list(self._get('at_bound')))
+
+    def curve(self):
+        """(temperature [R, K], mean NLL [R, K]): the first round's grid, from T = 16 down to T = 1 / 16."""
+        return torch.from_numpy(self._get('curve_temperature').copy()), torch.from_numpy(self._get('curve_nll').copy())
+
+    def apply(self, logits):
+        """logits: ``n_models`` tensors [B,C,H,W] -> one [B,C,H,W] probability tensor per rater (logical views of NHWC buffers)."""
+        self._check(logits)
+        outs = K.temperature_apply([z.detach().permute(0, 2, 3, 1) for z in logits], self._get('beta'), with_ensemble=self.with_ensemble)
+        return [o.permute(0, 3, 1, 2) for o in outs]
+
+    def detailed_summary(self) -> dict:
+        t, before, after, bound = (self._get(k) for k in ('temperature', 'nll_before', 'nll_after', 'at_bound'))
+        return {name: {'T': float(t[r]), 'NLL_before': float(before[r]), 'NLL_after': float(after[r]), 'at_bound': bound[r]}
+                for r, name in enumerate(self.raters)}
+
+    summary = detailed_summary
 
 
 def keep_largest_component(pred: torch.Tensor, method='2d', classes=None, background=0, full_connectivity=False, return_stats=False):

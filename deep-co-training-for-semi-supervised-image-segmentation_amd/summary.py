@@ -11,8 +11,8 @@ matrices that ``dct_confusion_counts`` leaves.
 
 Predictions come from the HIP networks; voting, the Dice counting (``dct_dice_counts``), the distance transform behind the
 Hausdorff distance (``dct_hausdorff``), the confusion matrices behind kappa and IoU (``dct_confusion_counts``) and, on request,
-the largest-connected-component cleaning of every prediction in front of a second set of tables (``dct_largest_component``) run on
-the device."""
+the largest-connected-component cleaning of every prediction in front of a second set of tables (``dct_largest_component``) and
+the fit of a temperature per model and for their mean (``dct_temperature_sums``) run on the device."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional
@@ -20,7 +20,7 @@ from typing import Dict, List, Optional
 import torch
 from torch import Tensor
 
-from .metrics import AgreementMeter, CalibrationMeter, ComponentMeter, DiceMeter, HausdorffMeter, keep_largest_component
+from .metrics import AgreementMeter, CalibrationMeter, ComponentMeter, DiceMeter, HausdorffMeter, TemperatureScaler, keep_largest_component
 from .models import Segmentator
 
 
@@ -70,6 +70,7 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
               report_axises: Optional[List[int]] = None, hausdorff: bool = False, spacing=None,
               kappa: bool = False, iou: bool = False, kappa_classes: Optional[List[int]] = None,
               largest_component: Optional[str] = None, lcc_classes: Optional[List[int]] = None, lcc_full: bool = False,
+              temperature=None, temperature_loader=None,
               calibration: bool = False, calibration_bins: int = 15, calibration_classes: Optional[List[int]] = None) -> Dict[str, dict]:
     """Per-model and ensemble 2-D / 3-D Dice over a validation loader (batches ``[(img, gt), meta, names]``): tables ``'2d'`` and
     ``'3d'`` with keys ``DSC{j}``.  ``hausdorff=True`` adds the tables ``'hd_2d'`` and ``'hd_3d'`` with keys ``HD{j}``: mean (and
@@ -97,7 +98,18 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
     entry per bin, pooled over the loader: the reliability diagram, and at each bin's lower edge the share of the counted pixels at
     or above it and their accuracy (the curve a pseudo-label ``threshold=`` is read from).  The ensemble rater of these tables is
     always the MEAN of the models' probabilities, whatever ``ensemble_method`` is: a hard vote has no confidence.  They get no
-    ``_lcc`` twin: the cleaned maps are one-hot."""
+    ``_lcc`` twin: the cleaned maps are one-hot.
+
+    ``temperature='fit'`` fits one temperature per model and one for the mean of their probabilities (``metrics.TemperatureScaler``,
+    include/dct.h ``dct_temperature_sums``; over the pixels of ``calibration_classes``) on ``temperature_loader`` if one is given, else
+    on ``val_dataloader`` itself; a list of R = models + 1 numbers gives the temperatures instead.  A fit on the set that is reported
+    is optimistic: the reported NLL is then the minimum over T on that very set; fit on held-out data (``temperature_loader``) for
+    figures that carry over.  The fit re-runs the models' eval forward in each of its five walks and caches no logits.  It adds
+    ``'temperature'`` = ``{model_i | ensemble: {'T', 'NLL_before', 'NLL_after', 'at_bound'}, 'fitted_on': 'temperature_loader' |
+    'val_dataloader' | 'given', 'curve': {model_i | ensemble: {'T': [...], 'NLL': [...]}}}`` (NLL pooled over the fitting set's
+    counted pixels; the curve is the fit's first grid, T from 16 down to 1/16; empty for given temperatures), and with
+    ``calibration=True`` the twins ``'calibration_2d_ts'``, ``'calibration_3d_ts'`` and ``'reliability_ts'`` of the scaled
+    probabilities (one more eval forward per batch for the logits).  Every other table is what it is without the argument: scaling never changes a hard prediction."""
     assert largest_component in (None, '2d', '3d'), largest_component
     device = torch.device(device)
     C = models[0].arch_params['num_classes']
@@ -139,6 +151,29 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
     calib = [CalibrationMeter(method=method, C=C, n_models=len(models), with_ensemble=True, n_bins=calibration_bins,
                               considered_classes=calibration_classes, from_logits=False, rater_names=names[:-1])
              for method in ('2d', '3d')] if calibration else []
+    scaler, fitted_on = None, None
+    if temperature is not None:
+        assert len(models) <= 8, "temperature scaling: at most 8 models (dct_temperature_sums takes 8 views)"
+        scaler = TemperatureScaler(C=C, n_models=len(models), with_ensemble=True, considered_classes=calibration_classes,
+                                   rater_names=names[:-1])
+        if isinstance(temperature, str):
+            assert temperature == 'fit', temperature
+            fit_loader = temperature_loader if temperature_loader is not None else val_dataloader
+            fitted_on = 'temperature_loader' if temperature_loader is not None else 'val_dataloader'
+
+            class _Logits(object):          # re-iterable: every walk of the fit runs the eval forward again
+                def __iter__(self):
+                    for (img, gt), _, _ in fit_loader:
+                        img = img.to(device)
+                        yield [m.predict(img, logit=True) for m in models], gt.to(device)
+
+            scaler.fit(_Logits())
+        else:
+            scaler.set_temperature(temperature)
+            fitted_on = 'given'
+    calib_ts = [CalibrationMeter(method=method, C=C, n_models=len(names), with_ensemble=False, n_bins=calibration_bins,
+                                 considered_classes=calibration_classes, from_logits=False, rater_names=names)
+                for method in ('2d', '3d')] if calibration and scaler is not None else []
     cleaned = meter_set() if largest_component else None
     comp = [ComponentMeter(method=largest_component, C=C) for _ in names] if largest_component else []
     for (img, gt), _, _ in val_dataloader:
@@ -148,6 +183,10 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
         feed(raw, preds, v, gt)
         for c in calib:
             c.add(preds, gt)
+        if calib_ts:
+            scaled = scaler.apply([m.predict(img, logit=True) for m in models])
+            for c in calib_ts:
+                c.add(scaled, gt)
         if cleaned is not None:
             kept = []
             for meter, p in zip(comp, preds + [v]):
@@ -185,16 +224,24 @@ def summarize(models: List[Segmentator], val_dataloader, device, ensemble_method
 
     tables(raw, "")
     keys = [f'model_{i}' for i in range(len(models))] + ['ensemble']
-    for c in calib:
-        stats = {k: fn() for k, fn in (('ECE', c.ece), ('MCE', c.mce), ('Brier', c.brier), ('NLL', c.nll))}
-        res = {key: {k: float(stats[k][0][r]) for k in stats} for r, key in enumerate(keys)}
-        res['ensemble_std'] = {k: float(stats[k][1][-1]) for k in stats}
-        out[f'calibration_{c.method}'] = res
-    if calib:
-        count, acc, conf = calib[0].reliability()
-        cov, kept = calib[0].coverage_accuracy()
-        out['reliability'] = {key: {'count': count[r].tolist(), 'accuracy': acc[r].tolist(), 'confidence': conf[r].tolist(),
-                                    'coverage': cov[r].tolist(), 'kept_accuracy': kept[r].tolist()} for r, key in enumerate(keys)}
+    for meters, suffix in ((calib, ""), (calib_ts, "_ts")):
+        for c in meters:
+            stats = {k: fn() for k, fn in (('ECE', c.ece), ('MCE', c.mce), ('Brier', c.brier), ('NLL', c.nll))}
+            res = {key: {k: float(stats[k][0][r]) for k in stats} for r, key in enumerate(keys)}
+            res['ensemble_std'] = {k: float(stats[k][1][-1]) for k in stats}
+            out[f'calibration_{c.method}{suffix}'] = res
+        if meters:
+            count, acc, conf = meters[0].reliability()
+            cov, kept = meters[0].coverage_accuracy()
+            out['reliability' + suffix] = {key: {'count': count[r].tolist(), 'accuracy': acc[r].tolist(), 'confidence': conf[r].tolist(),
+                                                 'coverage': cov[r].tolist(), 'kept_accuracy': kept[r].tolist()}
+                                           for r, key in enumerate(keys)}
+    if scaler is not None:
+        res = dict(zip(keys, scaler.detailed_summary().values()))
+        res['fitted_on'] = fitted_on
+        ct, cn = scaler.curve()
+        res['curve'] = {key: {'T': ct[r].tolist(), 'NLL': cn[r].tolist()} for r, key in enumerate(keys)}
+        out['temperature'] = res
     if cleaned is not None:
         tables(cleaned, "_lcc")
         out['components'] = {(f'model_{i}' if i < len(models) else 'ensemble'): m.detailed_summary() for i, m in enumerate(comp)}

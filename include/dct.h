@@ -782,6 +782,38 @@ int dct_calibration_counts(const float* const* probs, int S, const int64_t* gt /
                            int C, int n_bins, uint32_t class_mask, int with_ensemble, int from_logits,
                            int64_t* bins /*[B][R][n_bins][3]*/, int64_t* scores /*[B][R][2]*/, dct_stream stream);
 
+/* ---- Temperature scaling on device: the sums behind the fit of one temperature per rater, and the scaled probabilities --------
+ * Raters: S tensors logits[s] = [B][pixels][C] in fp32, 1 <= S <= 8, 1 <= C <= 8, the views' logits z.  With with_ensemble one more
+ *   rater follows whose "logits" are u_c = logf(p_ens_c + 1e-10f), p_ens being exactly the mean of the calibration rule above: each
+ *   view's fp32 softmax at temperature 1, summed in view order, one fp32 division by S.  The ensemble is formed first and scaled
+ *   afterwards: it is the ensemble rater of dct_calibration_counts.  R = S + with_ensemble.
+ * Which pixels count: as above, 0 <= gt < C and bit gt of class_mask set.
+ * Candidates: betas[R][K], fp32 on the device, 1 <= K <= 16: inverse temperatures beta = 1 / T, a row per rater.
+ * Per counted pixel, rater r and candidate k, with z the rater's logits, y = gt, beta = betas[r][k], everything in fp32:
+ *   x_c = beta * z_c (a rounded product); m = max_c x_c; e_c = expf(x_c - m); s = sum_c e_c in class order;
+ *   nll = logf(s) - (x_y - m); g = (sum_c e_c * z_c) / s - z_y.
+ *   g is d nll / d beta, and its sum over the pixels is non-decreasing in beta (the NLL is convex in beta): the fit is a root
+ *   search on a monotone function.  (2 z, beta / 2) gives the same x, hence the same nll words, as (z, beta), and twice the g.
+ * What is stored, all integers, so that the sums are order-independent and bit-identical from run to run:
+ *   sums[r][k][0] (int64) += rint(min(nll, 4095) * 2^20); sums[r][k][1] += rint(clamp(g, -2047, 2047) * 2^20), signed;
+ *   counted[0] (int64) += the number of counted pixels.  rint rounds to nearest, ties to even; a NaN contributes 0.
+ * One launch per batch reads every logit once from HBM ((4 C S + 8) bytes per pixel) and evaluates all R K candidates.
+ * logits: S host-side entries, each a device tensor aligned to its pixel (16 bytes at C = 4, 8 at C = 2, else 4); gt, sums and counted
+ * 8-byte aligned, betas 4-byte; sums and counted are zeroed by the caller (or hold earlier sums: the call adds).  No workspace;
+ * nothing waits for the device.
+ * dct_temperature_apply writes R fp32 tensors out[r] = [B][pixels][C] (host-side entries, aligned as the logits): for a view the
+ *   softmax above (the calibration rule's: max-subtracted, the sum in class order, a true division) of beta_r * z, for the ensemble
+ *   the same softmax of beta_R * u.  beta: R floats on the HOST.  At beta = 1 a view's output is the p of dct_calibration_counts'
+ *   from_logits, bit for bit.
+ * DCT_ERR_BAD_ARG: a null logits / entry / gt / betas / sums / counted / beta / out, a misaligned pointer, S < 1, B < 1, pixels < 1,
+ * with_ensemble not 0 or 1; DCT_ERR_UNSUPPORTED: S > 8, C < 1 or C > 8, K < 1 or K > 16, B > 65535, pixels_per_image >= 2^31.
+ * Both are decided before anything is launched. */
+int dct_temperature_sums(const float* const* logits, int S, const int64_t* gt /*[B][pixels]*/, int B, int64_t pixels_per_image,
+                         int C, uint32_t class_mask, int with_ensemble, const float* betas /*[R][K], device*/, int K,
+                         int64_t* sums /*[R][K][2]*/, int64_t* counted /*[1]*/, dct_stream stream);
+int dct_temperature_apply(const float* const* logits, int S, int B, int64_t pixels_per_image, int C, const float* beta /*[R], host*/,
+                          int with_ensemble, float* const* out /*R entries*/, dct_stream stream);
+
 /* ---- per-kernel-class timing (bench.py roofline leg) --------------------------------------
  * When enabled every launch made through this library is bracketed by hipEvents on its stream;
  * dct_prof_read synchronises and returns accumulated milliseconds and launch counts per class. */
