@@ -68,87 +68,33 @@ __device__ __forceinline__ void block_partial2(float a, float b, float* partial)
     partial[blockIdx.x * 2 + 1] = sm[4] + sm[5] + sm[6] + sm[7];
   }
 }
+// The fold of the block partial pairs, by a whole block of 256 threads and in one fixed order: thread i takes pairs i, i + 256, ... in
+// order, then the LDS tree.  Every thread gets both sums.  The one copy: whichever kernel folds, the sums come out bit for bit.
+__device__ __forceinline__ void fold_partials(const float* partial, int blocks, float& sum_a, float& sum_b) {
+  __shared__ float sa[256], sb[256];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
+  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
+    __syncthreads();
+  }
+  sum_a = sa[0]; sum_b = sb[0];
+}
 // out[0] = sum_a / (use_count ? sum_b : denom); out[1] = sum_b
 __global__ __launch_bounds__(256) void finalize_kernel(const float* partial, int blocks, float* out, int use_count, float denom, int write_b) {
-  __shared__ float sa[256], sb[256];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-    __syncthreads();
-  }
+  float a, b;
+  fold_partials(partial, blocks, a, b);
   if (threadIdx.x == 0) {
-    out[0] = sa[0] / (use_count ? sb[0] : denom);
-    if (write_b) out[1] = sb[0];
+    out[0] = a / (use_count ? b : denom);
+    if (write_b) out[1] = b;
   }
 }
 
-// ---- cross entropy ---------------------------------------------------------------------------
-template <int C>
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, float* partial) {
-  float sum = 0.f, cnt = 0.f;
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    const long long t = tgt[pix];
-    if (t == ignore) continue;
-    float x[C], p[C];
-    load_px<C>(logits, pix, x);
-    const float lse = softmax_px<C>(x, p);
-    float xt = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) xt = (t == c) ? x[c] : xt;
-    sum += lse - xt; cnt += 1.f;
-  }
-  block_partial2(sum, cnt, partial);
-}
-template <int C>
-__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore,
-                                                      const float* count, const float* gscale, float gmul, float* dl, int acc) {
-  const float g = (gscale ? gscale[0] : 1.f) * gmul / count[0];
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    const long long t = tgt[pix];
-    float x[C], p[C], d[C];
-    load_px<C>(logits, pix, x);
-    softmax_px<C>(x, p);
-#pragma unroll
-    for (int c = 0; c < C; ++c) d[c] = (t == ignore) ? 0.f : g * (p[c] - (t == c ? 1.f : 0.f));
-    store_px<C>(dl, pix, d, acc);
-  }
-}
-
-// The step's cross-entropy pair in two launches instead of three (round 5: every small launch on a model's chain costs the step ~3 us): the backward
-// kernel folds the forward kernel's block partials itself -- every block, in finalize_kernel's order, so the count (and the loss block 0 writes)
-// come out bit for bit -- before it writes the logit gradients.
-template <int C>
-__global__ __launch_bounds__(256) void ce_bwd_fin_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* partial,
-                                                          int blocks, float* out2, const float* gscale, float gmul, float* dl, int acc) {
-  __shared__ float sa[256], sb[256];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  const float count = sb[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = sa[0] / count; out2[1] = count; }
-  const float g = (gscale ? gscale[0] : 1.f) * gmul / count;
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    const long long t = tgt[pix];
-    float x[C], p[C], d[C];
-    load_px<C>(logits, pix, x);
-    softmax_px<C>(x, p);
-#pragma unroll
-    for (int c = 0; c < C; ++c) d[c] = (t == ignore) ? 0.f : g * (p[c] - (t == c ? 1.f : 0.f));
-    store_px<C>(dl, pix, d, acc);
-  }
-}
-
-// ---- class-weighted cross entropy, sum reduction, per-pixel map (the rule: include/dct.h) ---------------------------------------------
+// ---- plain, class-weighted and focal cross entropy: one kernel family over the rule of one pixel (the rules: include/dct.h) ------------
 // The C class weights are read once per wave (a uniform address: they sit in scalar registers) and w_t is picked by the select that picks
-// x_t -- never weight[t].  A target outside [0, C) is ignored like ignore_index: w = 0, no logit read for the value, gradient exactly 0.
+// x_t -- never weight[t].
 template <int C> __device__ __forceinline__ void load_weights(const float* weight, float wr[C]) {
 #pragma unroll
   for (int c = 0; c < C; ++c) wr[c] = weight ? weight[c] : 1.f;
@@ -160,106 +106,17 @@ template <int C> __device__ __forceinline__ float weight_of(long long t, const f
   for (int c = 0; c < C; ++c) w = (t == c) ? wr[c] : w;
   return w;
 }
-// w_t and l = logsumexp(x) - x_t of one counted pixel
-template <int C> __device__ __forceinline__ float ce_px(const float* logits, long long pix, long long t, const float wr[C], float& w) {
+// l = logsumexp(x) - x_t of one pixel (x_t = 0 for a target outside [0, C))
+template <int C> __device__ __forceinline__ float ce_px(const float* logits, long long pix, long long t) {
   float x[C], p[C];
   load_px<C>(logits, pix, x);
   const float lse = softmax_px<C>(x, p);
   float xt = 0.f;
 #pragma unroll
   for (int c = 0; c < C; ++c) xt = (t == c) ? x[c] : xt;
-  w = weight_of<C>(t, wr);
   return lse - xt;
 }
-// dl (=|+=) (g * w_t) * (p - onehot) over the grid's pixels; g_px (nullable): a per-pixel factor times g (the map's dmap)
-template <int C>
-__device__ __forceinline__ void ce_w_grad_pixels(const float* logits, const long long* tgt, long long P, int ignore, const float wr[C], float g,
-                                                 const float* g_px, float* dl, int acc) {
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    const long long t = tgt[pix];
-    const bool on = counted<C>(t, ignore);
-    float x[C], p[C], d[C];
-    load_px<C>(logits, pix, x);
-    softmax_px<C>(x, p);
-    const float gw = (g_px ? g * g_px[pix] : g) * weight_of<C>(t, wr);
-#pragma unroll
-    for (int c = 0; c < C; ++c) d[c] = on ? gw * (p[c] - (t == c ? 1.f : 0.f)) : 0.f;
-    store_px<C>(dl, pix, d, acc);
-  }
-}
-// partial[2b] = the block's sum of w l, partial[2b + 1] = its sum of w (ce_fwd_kernel's walk; with all weights 1 its partials)
-template <int C>
-__global__ __launch_bounds__(256) void ce_w_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                        float* partial) {
-  float wr[C];
-  load_weights<C>(weight, wr);
-  float sum = 0.f, den = 0.f;
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    const long long t = tgt[pix];
-    if (!counted<C>(t, ignore)) continue;
-    float w;
-    const float l = ce_px<C>(logits, pix, t, wr, w);
-    sum += w * l; den += w;
-  }
-  block_partial2(sum, den, partial);
-}
-template <int C>
-__global__ __launch_bounds__(256) void ce_w_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                        const float* denom, const float* gscale, float gmul, float* dl, int acc) {
-  float wr[C];
-  load_weights<C>(weight, wr);
-  float g = (gscale ? gscale[0] : 1.f) * gmul;
-  if (denom) g = g / denom[0];          // (the sum reduction passes none: its denominator is 1)
-  ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, g, nullptr, dl, acc);
-}
-// ce_bwd_fin_kernel's fold (finalize_kernel's order, in every block) in front of the weighted gradient
-template <int C>
-__global__ __launch_bounds__(256) void ce_w_bwd_fin_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                            int mean, const float* partial, int blocks, float* out2, const float* gscale,
-                                                            float gmul, float* dl, int acc) {
-  __shared__ float sa[256], sb[256];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  const float den = sb[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = mean ? sa[0] / den : sa[0]; out2[1] = den; }
-  float wr[C];
-  load_weights<C>(weight, wr);
-  float g = (gscale ? gscale[0] : 1.f) * gmul;
-  if (mean) g = g / den;
-  ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, g, nullptr, dl, acc);
-}
-template <int C>
-__global__ __launch_bounds__(256) void ce_map_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                          float* map) {
-  float wr[C];
-  load_weights<C>(weight, wr);
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    const long long t = tgt[pix];
-    float v = 0.f;
-    if (counted<C>(t, ignore)) {
-      float w;
-      const float l = ce_px<C>(logits, pix, t, wr, w);
-      v = w * l;
-    }
-    map[pix] = v;
-  }
-}
-template <int C>
-__global__ __launch_bounds__(256) void ce_map_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                          const float* dmap, float gmul, float* dl, int acc) {
-  float wr[C];
-  load_weights<C>(weight, wr);
-  ce_w_grad_pixels<C>(logits, tgt, P, ignore, wr, gmul, dmap, dl, acc);
-}
-
-// ---- focal loss (the rule: include/dct.h, dct_focal_*) ----------------------------------------------------------------------------------
-// One pixel: p = softmax(x); q = the mass off the target, summed from the exponentials (never 1 - p_t: at a confident pixel that is a
+// One focal pixel: p = softmax(x); q = the mass off the target, summed from the exponentials (never 1 - p_t: at a confident pixel that is a
 // rounding error); l = -log p_t = -log1p(-q) while q < 1/2 (relative error ~ that of q) and (max - x_t) + log(sum) above it (two terms
 // >= 0, l >= log 2: nothing cancels); m = q^gamma = exp2(gamma log2 q); k = m (1 + gamma p_t l / q), the sum of two terms >= 0.
 // gamma == 0 (the same in every lane) is m = k = 1 whatever q is; q == 0 under gamma > 0 is m = k = 0 (then l = -log1p(-0) = 0 too).
@@ -292,99 +149,147 @@ __device__ __forceinline__ void focal_px(const float x[C], long long t, float ga
   m = some ? pw : 0.f;
   k = some ? pw * (1.f + gamma * tl) : 0.f;
 }
-// dl (=|+=) (g * w_t * k) * (p - onehot) over the grid's pixels, the target's own entry as -q; g_px (nullable): the map's dmap
-template <int C>
-__device__ __forceinline__ void focal_grad_pixels(const float* logits, const long long* tgt, long long P, int ignore, const float wr[C],
-                                                  float gamma, float g, const float* g_px, float* dl, int acc) {
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    const long long t = tgt[pix];
-    const bool on = counted<C>(t, ignore);
-    float x[C], p[C], d[C], q, l, m, k;
+
+// A rule is what the three criteria differ in.  It is built from (ignore, weight, gamma), once per thread, and offers
+//   counted(t)                      whether the pixel enters the sums (and the map);
+//   value(logits, pix, t, den)      the value of one counted pixel, with its term of the denominator in den;
+//   grad(logits, pix, t, g, d)      the gradient row of one pixel (counted or not) under the scalar factor g;
+//   kChecksC                        whether the host refuses an unsupported C ahead of the workspace (else: at dispatch).
+// Plain: every t != ignore counts, also one outside [0, C) (its x_t is 0, its gradient g p); value l, denominator 1.
+template <int C> struct PlainRule {
+  static constexpr bool kChecksC = false;
+  int ignore;
+  __device__ __forceinline__ PlainRule(int ignore_, const float*, float) : ignore(ignore_) {}
+  __device__ __forceinline__ bool counted(long long t) const { return t != ignore; }
+  __device__ __forceinline__ float value(const float* logits, long long pix, long long t, float& den) const {
+    den = 1.f;
+    return ce_px<C>(logits, pix, t);
+  }
+  __device__ __forceinline__ void grad(const float* logits, long long pix, long long t, float g, float d[C]) const {
+    float x[C], p[C];
+    load_px<C>(logits, pix, x);
+    softmax_px<C>(x, p);
+#pragma unroll
+    for (int c = 0; c < C; ++c) d[c] = (t == ignore) ? 0.f : g * (p[c] - (t == c ? 1.f : 0.f));
+  }
+};
+// Weighted: a target outside [0, C) is ignored like ignore_index (w = 0, no logit read for the value, gradient exactly 0); value w_t l,
+// denominator w_t, gradient (g w_t) (p - onehot).
+template <int C> struct WeightedRule {
+  static constexpr bool kChecksC = true;
+  int ignore;
+  float wr[C];
+  __device__ __forceinline__ WeightedRule(int ignore_, const float* weight, float) : ignore(ignore_) { load_weights<C>(weight, wr); }
+  __device__ __forceinline__ bool counted(long long t) const { return ::counted<C>(t, ignore); }
+  __device__ __forceinline__ float value(const float* logits, long long pix, long long t, float& den) const {
+    const float l = ce_px<C>(logits, pix, t);
+    den = weight_of<C>(t, wr);
+    return den * l;
+  }
+  __device__ __forceinline__ void grad(const float* logits, long long pix, long long t, float g, float d[C]) const {
+    const bool on = counted(t);
+    float x[C], p[C];
+    load_px<C>(logits, pix, x);
+    softmax_px<C>(x, p);
+    const float gw = g * weight_of<C>(t, wr);
+#pragma unroll
+    for (int c = 0; c < C; ++c) d[c] = on ? gw * (p[c] - (t == c ? 1.f : 0.f)) : 0.f;
+  }
+};
+// Focal: the weighted rule's pixels; value w_t m l, denominator w_t, gradient (g w_t k) (p - onehot) with the target's own entry as -q.
+template <int C> struct FocalRule {
+  static constexpr bool kChecksC = true;
+  int ignore;
+  float gamma, wr[C];
+  __device__ __forceinline__ FocalRule(int ignore_, const float* weight, float gamma_) : ignore(ignore_), gamma(gamma_) { load_weights<C>(weight, wr); }
+  __device__ __forceinline__ bool counted(long long t) const { return ::counted<C>(t, ignore); }
+  __device__ __forceinline__ float value(const float* logits, long long pix, long long t, float& den) const {
+    float x[C], p[C], q, l, m, k;
     load_px<C>(logits, pix, x);
     focal_px<C>(x, t, gamma, p, q, l, m, k);
-    const float gw = (g_px ? g * g_px[pix] : g) * weight_of<C>(t, wr) * k;
+    den = weight_of<C>(t, wr);
+    return den * (m * l);
+  }
+  __device__ __forceinline__ void grad(const float* logits, long long pix, long long t, float g, float d[C]) const {
+    const bool on = counted(t);
+    float x[C], p[C], q, l, m, k;
+    load_px<C>(logits, pix, x);
+    focal_px<C>(x, t, gamma, p, q, l, m, k);
+    const float gw = g * weight_of<C>(t, wr) * k;
 #pragma unroll
     for (int c = 0; c < C; ++c) d[c] = on ? gw * (t == c ? -q : p[c]) : 0.f;
+  }
+};
+
+// dl (=|+=) the rule's gradient rows over the grid's pixels; g_px (nullable): a per-pixel factor times g (the map's dmap)
+template <int C, template <int> class Rule>
+__device__ __forceinline__ void grad_pixels(const Rule<C>& rule, const float* logits, const long long* tgt, long long P, float g, const float* g_px,
+                                            float* dl, int acc) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float d[C];
+    rule.grad(logits, pix, tgt[pix], g_px ? g * g_px[pix] : g, d);
     store_px<C>(dl, pix, d, acc);
   }
 }
-// w_t m l of one counted pixel and its w_t
-template <int C>
-__device__ __forceinline__ float focal_value(const float* logits, long long pix, long long t, const float wr[C], float gamma, float& w) {
-  float x[C], p[C], q, l, m, k;
-  load_px<C>(logits, pix, x);
-  focal_px<C>(x, t, gamma, p, q, l, m, k);
-  w = weight_of<C>(t, wr);
-  return w * (m * l);
-}
-// partial[2b] = the block's sum of w m l, partial[2b + 1] = its sum of w (ce_w_fwd_kernel's walk)
-template <int C>
-__global__ __launch_bounds__(256) void focal_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                         float gamma, float* partial) {
-  float wr[C];
-  load_weights<C>(weight, wr);
+// partial[2b] = the block's sum of the values, partial[2b + 1] = its sum of the denominator terms
+template <int C, template <int> class Rule>
+__global__ __launch_bounds__(256) void loss_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                        float gamma, float* partial) {
+  const Rule<C> rule(ignore, weight, gamma);
   float sum = 0.f, den = 0.f;
   for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
     const long long t = tgt[pix];
-    if (!counted<C>(t, ignore)) continue;
+    if (!rule.counted(t)) continue;
     float w;
-    sum += focal_value<C>(logits, pix, t, wr, gamma, w);
+    sum += rule.value(logits, pix, t, w);
     den += w;
   }
   block_partial2(sum, den, partial);
 }
-template <int C>
-__global__ __launch_bounds__(256) void focal_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                         float gamma, const float* denom, const float* gscale, float gmul, float* dl, int acc) {
-  float wr[C];
-  load_weights<C>(weight, wr);
+// the logit gradient from a finished denominator (denom nullable: the sum reduction passes none, its denominator is 1)
+template <int C, template <int> class Rule>
+__global__ __launch_bounds__(256) void loss_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                        float gamma, const float* denom, const float* gscale, float gmul, float* dl, int acc) {
+  const Rule<C> rule(ignore, weight, gamma);
   float g = (gscale ? gscale[0] : 1.f) * gmul;
-  if (denom) g = g / denom[0];          // (the sum reduction passes none: its denominator is 1)
-  focal_grad_pixels<C>(logits, tgt, P, ignore, wr, gamma, g, nullptr, dl, acc);
+  if (denom) g = g / denom[0];
+  grad_pixels<C, Rule>(rule, logits, tgt, P, g, nullptr, dl, acc);
 }
-// ce_w_bwd_fin_kernel's fold (finalize_kernel's order, in every block) in front of the focal gradient
-template <int C>
-__global__ __launch_bounds__(256) void focal_bwd_fin_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                             float gamma, int mean, const float* partial, int blocks, float* out2,
-                                                             const float* gscale, float gmul, float* dl, int acc) {
-  __shared__ float sa[256], sb[256];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  const float den = sb[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = mean ? sa[0] / den : sa[0]; out2[1] = den; }
-  float wr[C];
-  load_weights<C>(weight, wr);
+// A step's forward and backward in two launches instead of three (every small launch on a model's chain costs the step ~3 us): this
+// kernel folds the forward kernel's block partials itself -- every block, through finalize_kernel's fold_partials, so the denominator
+// (and the loss block 0 writes) come out bit for bit -- before it writes the logit gradients.
+template <int C, template <int> class Rule>
+__global__ __launch_bounds__(256) void loss_bwd_fin_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                            float gamma, int mean, const float* partial, int blocks, float* out2,
+                                                            const float* gscale, float gmul, float* dl, int acc) {
+  float sum, den;
+  fold_partials(partial, blocks, sum, den);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = mean ? sum / den : sum; out2[1] = den; }
+  const Rule<C> rule(ignore, weight, gamma);
   float g = (gscale ? gscale[0] : 1.f) * gmul;
   if (mean) g = g / den;
-  focal_grad_pixels<C>(logits, tgt, P, ignore, wr, gamma, g, nullptr, dl, acc);
+  grad_pixels<C, Rule>(rule, logits, tgt, P, g, nullptr, dl, acc);
 }
-template <int C>
-__global__ __launch_bounds__(256) void focal_map_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                             float gamma, float* map) {
-  float wr[C];
-  load_weights<C>(weight, wr);
+// the per-pixel map: the value of a counted pixel, 0 elsewhere
+template <int C, template <int> class Rule>
+__global__ __launch_bounds__(256) void loss_map_fwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                            float gamma, float* map) {
+  const Rule<C> rule(ignore, weight, gamma);
   for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
     const long long t = tgt[pix];
     float v = 0.f;
-    if (counted<C>(t, ignore)) {
+    if (rule.counted(t)) {
       float w;
-      v = focal_value<C>(logits, pix, t, wr, gamma, w);
+      v = rule.value(logits, pix, t, w);
     }
     map[pix] = v;
   }
 }
-template <int C>
-__global__ __launch_bounds__(256) void focal_map_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
-                                                             float gamma, const float* dmap, float gmul, float* dl, int acc) {
-  float wr[C];
-  load_weights<C>(weight, wr);
-  focal_grad_pixels<C>(logits, tgt, P, ignore, wr, gamma, gmul, dmap, dl, acc);
+template <int C, template <int> class Rule>
+__global__ __launch_bounds__(256) void loss_map_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                            float gamma, const float* dmap, float gmul, float* dl, int acc) {
+  const Rule<C> rule(ignore, weight, gamma);
+  grad_pixels<C, Rule>(rule, logits, tgt, P, gmul, dmap, dl, acc);
 }
 
 // ---- boundary loss: the softmax weighted by the signed distance map (the rule: include/dct.h, dct_boundary_*) --------------------------
@@ -417,18 +322,11 @@ __global__ __launch_bounds__(256) void bd_fwd_kernel(const float* logits, const 
 }
 // finalize_kernel's fold; out[0] = sum / (N K), 0 when nothing is counted; out[1] = N
 __global__ __launch_bounds__(256) void bd_finalize_kernel(const float* partial, int blocks, float* out, float K) {
-  __shared__ float sa[256], sb[256];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-    __syncthreads();
-  }
+  float a, b;
+  fold_partials(partial, blocks, a, b);
   if (threadIdx.x == 0) {
-    out[0] = sb[0] > 0.f ? sa[0] / (sb[0] * K) : 0.f;
-    out[1] = sb[0];
+    out[0] = b > 0.f ? a / (b * K) : 0.f;
+    out[1] = b;
   }
 }
 // dl (=|+=) (g s_c) (q_c - sum_k s_k q_k), q_c = m_c phi_c / (N K); an uncounted pixel gets 0 (N = 0: every pixel is uncounted)
@@ -619,7 +517,7 @@ __device__ __forceinline__ void ce_dice_grad_pixels(const float* logits, const l
     store_px<C>(dl, base + pix, d, acc);
   }
 }
-// one softmax per counted pixel feeds both terms: ce_w_fwd_kernel's {w l, w} and {p_t, p_c, [t == c]} per class
+// one softmax per counted pixel feeds both terms: WeightedRule's {w l, w} and {p_t, p_c, [t == c]} per class
 template <int C>
 __global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
                                                            const float* weight, float* partial) {
@@ -664,7 +562,7 @@ __global__ __launch_bounds__(256) void ce_dice_bwd_kernel(const float* logits, c
   dice_coeffs<C>(sums + (r.per_image ? (long long)blockIdx.y * C * 3 : 0), r, qa, qb);
   ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, out4[2], r, qa, qb, dl, acc);
 }
-// ce_bwd_fin_kernel's pattern: every block folds the forward rows it needs (all of them for sum w; its own group's for the Dice sums)
+// loss_bwd_fin_kernel's pattern: every block folds the forward rows it needs (all of them for sum w; its own group's for the Dice sums)
 // in ce_dice_fin_kernel's order, block (0, 0) also writes what that kernel writes, then the gradient
 template <int C>
 __global__ __launch_bounds__(256) void ce_dice_bwd_fin_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
@@ -1081,16 +979,9 @@ __global__ __launch_bounds__(256) void pl_step_kernel(PtrPack pk, PtrPack probs,
 // finalize_kernel's fold with a denominator of its own for each sum: out[0] = mean map value, out[1] = kept teacher terms / all of them
 // (the kept counts are whole numbers held in floats: exact up to 2^24 terms)
 __global__ __launch_bounds__(256) void pl_finalize_kernel(const float* partial, int blocks, float* out, float denom_a, float denom_b) {
-  __shared__ float sa[256], sb[256];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < blocks; i += 256) { a += partial[2 * i]; b += partial[2 * i + 1]; }
-  sa[threadIdx.x] = a; sb[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { out[0] = sa[0] / denom_a; out[1] = sb[0] / denom_b; }
+  float a, b;
+  fold_partials(partial, blocks, a, b);
+  if (threadIdx.x == 0) { out[0] = a / denom_a; out[1] = b / denom_b; }
 }
 
 // ---- KL(y || p) -----------------------------------------------------------------------------------
@@ -1371,138 +1262,126 @@ extern "C" size_t dct_loss_workspace_bytes(int64_t) { return (size_t)kMaxBlocks 
 
 static inline bool ws_ok(void* ws, size_t bytes) { return ws && bytes >= (size_t)kMaxBlocks * 2 * sizeof(float); }
 
+// gamma of the focal loss: finite and >= 0 (a NaN fails the comparison)
+static inline bool gamma_ok(float gamma) { return gamma >= 0.f && gamma <= 3.402823466e38f; }
+
+// ---- plain, class-weighted and focal cross entropy: the 13 entry points on five launchers over the rule ---------------------------------
+// What every call takes.  The plain family passes no weight and gamma = 0, the weighted one gamma = 0; reduction: 0 mean, 1 sum.
+// The status of a bad call: BAD_ARG, then (rules with kChecksC) UNSUPPORTED, then WORKSPACE; any other C is UNSUPPORTED at dispatch.
+struct PxArgs { const float* logits; const long long* tgt; long long P; int C, ignore; const float* weight; float gamma; hipStream_t st; };
+static inline PxArgs px_args(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                             float gamma, dct_stream stream) {
+  return PxArgs{logits, (const long long*)targets, (long long)pixels, C_, ignore_index, weight, gamma, (hipStream_t)stream};
+}
+static inline bool px_ok(const PxArgs& a) { return a.logits && a.tgt && a.P >= 1 && gamma_ok(a.gamma); }
+static inline bool reduction_ok(int reduction) { return reduction == 0 || reduction == 1; }
+
+template <template <int> class Rule>
+static int loss_fwd(const PxArgs& a, int reduction, float* out2, void* workspace, size_t workspace_bytes) {
+  if (!px_ok(a) || !out2 || !reduction_ok(reduction)) return DCT_ERR_BAD_ARG;
+  if (Rule<2>::kChecksC && (a.C < 2 || a.C > 8)) return DCT_ERR_UNSUPPORTED;
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  const unsigned grid = grid_for(a.P);
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (loss_fwd_kernel<C, Rule>), dim3(grid), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight, a.gamma, (float*)workspace));
+  DCT_LAUNCH(DCT_PROF_LOSS, finalize_kernel, dim3(1), dim3(256), 0, a.st, (const float*)workspace, (int)grid, out2, reduction == 0 ? 1 : 0, 1.f, 1);
+  return dct_check_launch();
+}
+// denom: required under the mean, not read under the sum
+template <template <int> class Rule>
+static int loss_bwd(const PxArgs& a, int reduction, const float* denom, const float* gscale, float gmul, float* dlogits, int accumulate) {
+  if (!px_ok(a) || !dlogits || !reduction_ok(reduction) || (reduction == 0 && !denom)) return DCT_ERR_BAD_ARG;
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (loss_bwd_kernel<C, Rule>), dim3(wide_grid(a.P)), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight, a.gamma,
+                             reduction == 0 ? denom : (const float*)nullptr, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+template <template <int> class Rule>
+static int loss_step(const PxArgs& a, int reduction, float* out2, const float* gscale, float gmul, float* dlogits, int accumulate, void* workspace,
+                     size_t workspace_bytes) {
+  if (!px_ok(a) || !out2 || !dlogits || !reduction_ok(reduction)) return DCT_ERR_BAD_ARG;
+  if (Rule<2>::kChecksC && (a.C < 2 || a.C > 8)) return DCT_ERR_UNSUPPORTED;
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  const unsigned grid = grid_for(a.P);       // loss_fwd's grid: the same block partials
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (loss_fwd_kernel<C, Rule>), dim3(grid), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight, a.gamma, (float*)workspace));
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (loss_bwd_fin_kernel<C, Rule>), dim3(wide_grid(a.P)), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight, a.gamma,
+                             reduction == 0 ? 1 : 0, (const float*)workspace, (int)grid, out2, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+template <template <int> class Rule>
+static int loss_map_fwd(const PxArgs& a, float* map) {
+  if (!px_ok(a) || !map) return DCT_ERR_BAD_ARG;
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (loss_map_fwd_kernel<C, Rule>), dim3(wide_grid(a.P)), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight, a.gamma, map));
+  return dct_check_launch();
+}
+template <template <int> class Rule>
+static int loss_map_bwd(const PxArgs& a, const float* dmap, float gmul, float* dlogits, int accumulate) {
+  if (!px_ok(a) || !dmap || !dlogits) return DCT_ERR_BAD_ARG;
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (loss_map_bwd_kernel<C, Rule>), dim3(wide_grid(a.P)), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight, a.gamma, dmap, gmul,
+                             dlogits, accumulate));
+  return dct_check_launch();
+}
+
 extern "C" int dct_ce_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index,
                           float* out2, void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out2 || pixels < 1) return DCT_ERR_BAD_ARG;
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, (float*)workspace));
-  DCT_LAUNCH(DCT_PROF_LOSS, finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, 1, 1.f, 1);
-  return dct_check_launch();
+  return loss_fwd<PlainRule>(px_args(logits, targets, pixels, C_, ignore_index, nullptr, 0.f, stream), 0, out2, workspace, workspace_bytes);
 }
 extern "C" int dct_ce_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index,
                           const float* count, const float* gscale, float gmul, float* dlogits, int accumulate,
                           dct_stream stream) {
-  if (!logits || !targets || !count || !dlogits || pixels < 1) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, count, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  return loss_bwd<PlainRule>(px_args(logits, targets, pixels, C_, ignore_index, nullptr, 0.f, stream), 0, count, gscale, gmul, dlogits, accumulate);
 }
 extern "C" int dct_ce_step(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, float* out2,
                            const float* gscale, float gmul, float* dlogits, int accumulate, void* workspace, size_t workspace_bytes,
                            dct_stream stream) {
-  if (!logits || !targets || !out2 || !dlogits || pixels < 1) return DCT_ERR_BAD_ARG;
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);       // dct_ce_fwd's grid: the same block partials
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, (float*)workspace));
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_bwd_fin_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index,
-                            (const float*)workspace, (int)grid, out2, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  return loss_step<PlainRule>(px_args(logits, targets, pixels, C_, ignore_index, nullptr, 0.f, stream), 0, out2, gscale, gmul, dlogits, accumulate,
+                              workspace, workspace_bytes);
 }
 extern "C" int dct_ce_weighted_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                                    int reduction, float* out2, void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out2 || pixels < 1 || (reduction != 0 && reduction != 1)) return DCT_ERR_BAD_ARG;
-  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_w_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, (float*)workspace));
-  DCT_LAUNCH(DCT_PROF_LOSS, finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, reduction == 0 ? 1 : 0, 1.f, 1);
-  return dct_check_launch();
+  return loss_fwd<WeightedRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, 0.f, stream), reduction, out2, workspace, workspace_bytes);
 }
 extern "C" int dct_ce_weighted_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                                    int reduction, const float* denom, const float* gscale, float gmul, float* dlogits, int accumulate,
                                    dct_stream stream) {
-  if (!logits || !targets || !dlogits || pixels < 1 || (reduction != 0 && reduction != 1) || (reduction == 0 && !denom)) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_w_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
-                            reduction == 0 ? denom : (const float*)nullptr, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  return loss_bwd<WeightedRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, 0.f, stream), reduction, denom, gscale, gmul, dlogits,
+                                accumulate);
 }
 extern "C" int dct_ce_weighted_step(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                                     int reduction, float* out2, const float* gscale, float gmul, float* dlogits, int accumulate,
                                     void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out2 || !dlogits || pixels < 1 || (reduction != 0 && reduction != 1)) return DCT_ERR_BAD_ARG;
-  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);       // dct_ce_weighted_fwd's grid: the same block partials
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_w_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, (float*)workspace));
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_w_bwd_fin_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
-                            reduction == 0 ? 1 : 0, (const float*)workspace, (int)grid, out2, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  return loss_step<WeightedRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, 0.f, stream), reduction, out2, gscale, gmul, dlogits,
+                                 accumulate, workspace, workspace_bytes);
 }
 extern "C" int dct_ce_map_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                               float* map, dct_stream stream) {
-  if (!logits || !targets || !map || pixels < 1) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_map_fwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, map));
-  return dct_check_launch();
+  return loss_map_fwd<WeightedRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, 0.f, stream), map);
 }
 extern "C" int dct_ce_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                               const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream) {
-  if (!logits || !targets || !dmap || !dlogits || pixels < 1) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_map_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, dmap, gmul,
-                            dlogits, accumulate));
-  return dct_check_launch();
+  return loss_map_bwd<WeightedRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, 0.f, stream), dmap, gmul, dlogits, accumulate);
 }
-// gamma of the focal loss: finite and >= 0 (a NaN fails the comparison)
-static inline bool gamma_ok(float gamma) { return gamma >= 0.f && gamma <= 3.402823466e38f; }
-
 extern "C" int dct_focal_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                              float gamma, int reduction, float* out2, void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out2 || pixels < 1 || (reduction != 0 && reduction != 1) || !gamma_ok(gamma)) return DCT_ERR_BAD_ARG;
-  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, gamma,
-                            (float*)workspace));
-  DCT_LAUNCH(DCT_PROF_LOSS, finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, reduction == 0 ? 1 : 0, 1.f, 1);
-  return dct_check_launch();
+  return loss_fwd<FocalRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, gamma, stream), reduction, out2, workspace, workspace_bytes);
 }
 extern "C" int dct_focal_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                              float gamma, int reduction, const float* denom, const float* gscale, float gmul, float* dlogits, int accumulate,
                              dct_stream stream) {
-  if (!logits || !targets || !dlogits || pixels < 1 || (reduction != 0 && reduction != 1) || (reduction == 0 && !denom) || !gamma_ok(gamma))
-    return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
-                            gamma, reduction == 0 ? denom : (const float*)nullptr, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  return loss_bwd<FocalRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, gamma, stream), reduction, denom, gscale, gmul, dlogits,
+                             accumulate);
 }
 extern "C" int dct_focal_step(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                               float gamma, int reduction, float* out2, const float* gscale, float gmul, float* dlogits, int accumulate,
                               void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out2 || !dlogits || pixels < 1 || (reduction != 0 && reduction != 1) || !gamma_ok(gamma)) return DCT_ERR_BAD_ARG;
-  if (C_ < 2 || C_ > 8) return DCT_ERR_UNSUPPORTED;
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);       // dct_focal_fwd's grid: the same block partials
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_fwd_kernel<C>, dim3(grid), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight, gamma,
-                            (float*)workspace));
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_bwd_fin_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
-                            gamma, reduction == 0 ? 1 : 0, (const float*)workspace, (int)grid, out2, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  return loss_step<FocalRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, gamma, stream), reduction, out2, gscale, gmul, dlogits,
+                              accumulate, workspace, workspace_bytes);
 }
 extern "C" int dct_focal_map_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                                  float gamma, float* map, dct_stream stream) {
-  if (!logits || !targets || !map || pixels < 1 || !gamma_ok(gamma)) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_map_fwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
-                            gamma, map));
-  return dct_check_launch();
+  return loss_map_fwd<FocalRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, gamma, stream), map);
 }
 extern "C" int dct_focal_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                                  float gamma, const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream) {
-  if (!logits || !targets || !dmap || !dlogits || pixels < 1 || !gamma_ok(gamma)) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, focal_map_bwd_kernel<C>, dim3(wide_grid(pixels)), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels, ignore_index, weight,
-                            gamma, dmap, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  return loss_map_bwd<FocalRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, gamma, stream), dmap, gmul, dlogits, accumulate);
 }
 // K of a boundary mask (the number of its bits below C), or a status
 static inline int boundary_k(int64_t pixels, int C_, int class_mask, float& K) {

@@ -41,28 +41,6 @@ def _simplex(t: torch.Tensor, axis=1) -> bool:
     return torch.allclose(s, torch.ones_like(s))
 
 
-class _CEFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, targets, ignore_index):
-        lp = _pc(logits)
-        C = lp.shape[3]
-        t = targets.reshape(-1)
-        if t.dtype != torch.int64 or not t.is_contiguous():
-            t = t.to(torch.int64).contiguous()
-        out = K.ce_fwd(lp, t, C, ignore_index)
-        ctx.save_for_backward(lp, t, out)
-        ctx.ignore_index = ignore_index
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        lp, t, out = ctx.saved_tensors
-        dl = torch.empty_like(lp)
-        g = g.to(torch.float32).contiguous()
-        K.ce_bwd(lp, t, lp.shape[3], out[1:2], dl, gscale=g, ignore_index=ctx.ignore_index)
-        return _nchw(dl), None, None
-
-
 def _targets(targets):
     t = targets.reshape(-1)
     if t.dtype != torch.int64 or not t.is_contiguous():
@@ -70,16 +48,18 @@ def _targets(targets):
     return t
 
 
-class _CEWeightedFn(torch.autograd.Function):
-    """Class-weighted mean (``reduction`` 0) or sum (1) on dct_ce_weighted_*; ``weight``: the fp32 device buffer or None (all ones)."""
+class _ReducedFn(torch.autograd.Function):
+    """The mean or sum of one criterion on a hip_ops family: ``family`` is 'ce', 'ce_weighted' or 'focal' (its ``_fwd`` and ``_bwd``
+    wrappers are called), ``kw`` their keyword arguments (``ignore_index`` and, beyond the plain family, ``weight`` -- the fp32 device
+    buffer or None for all ones --, ``reduction`` and ``gamma``)."""
 
     @staticmethod
-    def forward(ctx, logits, targets, weight, reduction, ignore_index):
+    def forward(ctx, logits, targets, family, kw):
         lp = _pc(logits)
         t = _targets(targets)
-        out = K.ce_weighted_fwd(lp, t, lp.shape[3], weight, reduction, ignore_index)
+        out = getattr(K, family + "_fwd")(lp, t, lp.shape[3], **kw)
         ctx.save_for_backward(lp, t, out)
-        ctx.weight, ctx.reduction, ctx.ignore_index = weight, reduction, ignore_index
+        ctx.family, ctx.kw = family, kw
         return out[0]
 
     @staticmethod
@@ -87,28 +67,35 @@ class _CEWeightedFn(torch.autograd.Function):
         lp, t, out = ctx.saved_tensors
         dl = torch.empty_like(lp)
         g = g.to(torch.float32).contiguous()
-        K.ce_weighted_bwd(lp, t, lp.shape[3], out[1:2], dl, weight=ctx.weight, reduction=ctx.reduction, gscale=g,
-                          ignore_index=ctx.ignore_index)
-        return _nchw(dl), None, None, None, None
+        getattr(K, ctx.family + "_bwd")(lp, t, lp.shape[3], out[1:2], dl, gscale=g, **ctx.kw)
+        return _nchw(dl), None, None, None
 
 
-class _CEMapFn(torch.autograd.Function):
-    """The [B, H, W] map w_t * (logsumexp(x) - x_t) of ``reduce=False`` on dct_ce_map_*."""
+class _MapFn(torch.autograd.Function):
+    """The [B, H, W] map of ``reduce=False`` on a hip_ops family: 'ce_map' (w_t * (logsumexp(x) - x_t)) or 'focal_map'
+    (w_t (1 - p_t)^gamma (-log p_t)); ``kw``: ``weight``, ``ignore_index`` and focal's ``gamma``."""
 
     @staticmethod
-    def forward(ctx, logits, targets, weight, ignore_index):
+    def forward(ctx, logits, targets, family, kw):
         lp = _pc(logits)
         t = _targets(targets)
         ctx.save_for_backward(lp, t)
-        ctx.weight, ctx.ignore_index = weight, ignore_index
-        return K.ce_map_fwd(lp, t, lp.shape[3], weight, ignore_index).view(lp.shape[:3])
+        ctx.family, ctx.kw = family, kw
+        return getattr(K, family + "_fwd")(lp, t, lp.shape[3], **kw).view(lp.shape[:3])
 
     @staticmethod
     def backward(ctx, g):
         lp, t = ctx.saved_tensors
         dl = torch.empty_like(lp)
-        K.ce_map_bwd(lp, t, lp.shape[3], g.to(torch.float32).contiguous().view(-1), dl, weight=ctx.weight, ignore_index=ctx.ignore_index)
+        getattr(K, ctx.family + "_bwd")(lp, t, lp.shape[3], g.to(torch.float32).contiguous().view(-1), dl, **ctx.kw)
         return _nchw(dl), None, None, None
+
+
+def _ce_reduced(outputs, targets, w, reduction, ignore_index):
+    """The class-weighted cross entropy under ``reduction``; None (all-ones) weights under the mean run the plain family."""
+    if w is None and reduction == K.CE_MEAN:
+        return _ReducedFn.apply(outputs, targets, 'ce', dict(ignore_index=ignore_index))
+    return _ReducedFn.apply(outputs, targets, 'ce_weighted', dict(weight=w, reduction=reduction, ignore_index=ignore_index))
 
 
 class _ClassWeighted(nn.Module):
@@ -165,52 +152,8 @@ class CrossEntropyLoss2d(_ClassWeighted):
             raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
         w = self.device_weight(outputs.device, outputs.shape[1])
         if self.reduction == 'none':
-            return _CEMapFn.apply(outputs, targets, w, self.ignore_index)
-        if self.reduction == 'mean' and w is None:
-            return _CEFn.apply(outputs, targets, self.ignore_index)
-        return _CEWeightedFn.apply(outputs, targets, w, K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM, self.ignore_index)
-
-
-class _FocalFn(torch.autograd.Function):
-    """Focal mean (``reduction`` 0) or sum (1) on dct_focal_*; ``weight``: the fp32 device buffer or None (all ones)."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, weight, gamma, reduction, ignore_index):
-        lp = _pc(logits)
-        t = _targets(targets)
-        out = K.focal_fwd(lp, t, lp.shape[3], weight, gamma, reduction, ignore_index)
-        ctx.save_for_backward(lp, t, out)
-        ctx.weight, ctx.gamma, ctx.reduction, ctx.ignore_index = weight, gamma, reduction, ignore_index
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        lp, t, out = ctx.saved_tensors
-        dl = torch.empty_like(lp)
-        g = g.to(torch.float32).contiguous()
-        K.focal_bwd(lp, t, lp.shape[3], out[1:2], dl, weight=ctx.weight, gamma=ctx.gamma, reduction=ctx.reduction, gscale=g,
-                    ignore_index=ctx.ignore_index)
-        return _nchw(dl), None, None, None, None, None
-
-
-class _FocalMapFn(torch.autograd.Function):
-    """The [B, H, W] map w_t (1 - p_t)^gamma (-log p_t) of ``reduce=False`` on dct_focal_map_*."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, weight, gamma, ignore_index):
-        lp = _pc(logits)
-        t = _targets(targets)
-        ctx.save_for_backward(lp, t)
-        ctx.weight, ctx.gamma, ctx.ignore_index = weight, gamma, ignore_index
-        return K.focal_map_fwd(lp, t, lp.shape[3], weight, gamma, ignore_index).view(lp.shape[:3])
-
-    @staticmethod
-    def backward(ctx, g):
-        lp, t = ctx.saved_tensors
-        dl = torch.empty_like(lp)
-        K.focal_map_bwd(lp, t, lp.shape[3], g.to(torch.float32).contiguous().view(-1), dl, weight=ctx.weight, gamma=ctx.gamma,
-                        ignore_index=ctx.ignore_index)
-        return _nchw(dl), None, None, None, None
+            return _MapFn.apply(outputs, targets, 'ce_map', dict(weight=w, ignore_index=self.ignore_index))
+        return _ce_reduced(outputs, targets, w, K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM, self.ignore_index)
 
 
 class FocalLoss2d(_ClassWeighted):
@@ -243,9 +186,10 @@ class FocalLoss2d(_ClassWeighted):
         if not outputs.is_cuda:
             raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
         w = self.device_weight(outputs.device, outputs.shape[1])
+        kw = dict(weight=w, gamma=self.gamma, ignore_index=self.ignore_index)
         if self.reduction == 'none':
-            return _FocalMapFn.apply(outputs, targets, w, self.gamma, self.ignore_index)
-        return _FocalFn.apply(outputs, targets, w, self.gamma, K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM, self.ignore_index)
+            return _MapFn.apply(outputs, targets, 'focal_map', kw)
+        return _ReducedFn.apply(outputs, targets, 'focal', dict(kw, reduction=K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM))
 
 
 class _CEDiceFn(torch.autograd.Function):
@@ -448,8 +392,7 @@ class CrossEntropyBoundaryLoss2d(_ClassWeighted):
         w = self.device_weight(outputs.device, outputs.shape[1])
         ce = bd = None
         if self.ce_coef != 0.0:
-            ce = (_CEFn.apply(outputs, targets, self.ignore_index) if w is None
-                  else _CEWeightedFn.apply(outputs, targets, w, K.CE_MEAN, self.ignore_index))
+            ce = _ce_reduced(outputs, targets, w, K.CE_MEAN, self.ignore_index)
         if self.boundary_coef != 0.0:
             bd = self.boundary(outputs, targets, dist_map)
         self.last_terms = (None if ce is None else ce.detach(), None if bd is None else bd.detach())

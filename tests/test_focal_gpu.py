@@ -16,7 +16,7 @@ error of q^gamma), eps_k, eps_v, eps_g -- are derived line by line in the docstr
 tests/test_focal_cpu.py holds a float32 evaluation on the CPU to them on the inputs below.
 
 Pixel counts: 1, 255, 257 (partial blocks), 262,145 (one past ``grid_for``'s 1024 blocks: a thread takes a second trip) and, in two
-cases, 2,097,153 (one past ``wide_grid``'s 8192, the backward kernels' grid).  C: 2, 3, 4, 8; gamma: 0, 0.5, 1, 2, 5, spread over the
+cases, 2,097,153 (one past ``wide_grid``'s 8192, the backward kernels' grid); 262,401 at every C from 2 to 8.  C otherwise: 2, 3, 4, 8; gamma: 0, 0.5, 1, 2, 5, spread over the
 cases.  A quarter of the targets are 255, some cases carry stray targets (C, -1).  Every case plants confident pixels and checks them
 by name: the target logit 20 and 40 above the rest (q ~ 1e-9, ~ 1e-17), 120 above (q = 0 in fp32: value and gradient exactly 0 under
 gamma > 0, the cross entropy's under gamma = 0, everything finite), and 150 below (p_t = 0 in fp32, q = 1).
@@ -49,7 +49,16 @@ def _ratio(got, ref, bound):
     return ((got.detach().cpu().double() - ref).abs() / bound.clamp(min=1e-300)).max().item()
 
 
-@pytest.mark.parametrize("P,C,gamma,reduction,accumulate,stray,weighted", R.CASES)
+# every C from 2 to 8 at 1024 * 256 + 257 pixels (the forward grid's second trip ends in a ragged block): the kernels are one template per
+# role over the pixel rule, and "the step is fwd followed by bwd, bit for bit" below is held at every C it is instantiated for
+STEP_CASES = [
+    (262401, 2, 2.0, MEAN, True, False, True), (262401, 3, 0.5, SUM, False, False, True), (262401, 4, 0.0, MEAN, False, True, False),
+    (262401, 5, 2.0, SUM, True, False, True), (262401, 6, 0.5, MEAN, False, False, False), (262401, 7, 1.0, MEAN, True, True, True),
+    (262401, 8, 2.0, MEAN, False, False, True),
+]
+
+
+@pytest.mark.parametrize("P,C,gamma,reduction,accumulate,stray,weighted", R.CASES + STEP_CASES)
 def test_focal_at_scale(ops, P, C, gamma, reduction, accumulate, stray, weighted):
     w = R.weights(C, alt=reduction == SUM) if weighted else torch.ones(C)
     g, x, t, t_ref, sen, plants = R.inputs(P, C, w, stray, seed=P + 7 * C + reduction)

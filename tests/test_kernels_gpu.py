@@ -556,7 +556,9 @@ def test_ce_step_is_bit_identical_to_forward_then_backward(ops, C, accumulate, i
 # above the 1024-block cap of the forward grid (every thread of it walks several pixels) and the 8192-block cap of the backward's;
 # 524,291 pixels: cfg2's labelled batch (C = 4) and cfg4's (C = 2) plus a ragged tail
 @pytest.mark.parametrize("P,C,accumulate,ignored", [(524291, 4, False, False), (524291, 2, True, True), (262145, 8, False, True),
-                                                    (2097153, 3, True, False)])
+                                                    (2097153, 3, True, False)]
+                         # 1024 * 256 + 257 (the forward grid's second trip ends in a ragged block) at every C the templates are instantiated for
+                         + [(262401, C, C % 2 == 1, C % 3 != 0) for C in range(2, 9)])
 def test_ce_step_is_bit_identical_above_the_grid_caps(ops, P, C, accumulate, ignored):
     _ce_step_bit_identical(ops, P, C, accumulate, ignored)
 

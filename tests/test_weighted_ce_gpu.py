@@ -171,7 +171,8 @@ def test_weighted_ce_at_scale(ops, P, C, reduction, accumulate, stray):
             assert torch.equal(d.cpu()[gone], want)
 
 
-@pytest.mark.parametrize("P,C", [(1, 2), (255, 3), (257, 8), (262145, 4), (2097153, 2), (2097153, 3)])
+# (262401 = 1024 * 256 + 257: the forward grid's second trip ends in a ragged block; there every C the kernel templates are instantiated for)
+@pytest.mark.parametrize("P,C", [(1, 2), (255, 3), (257, 8), (262145, 4), (2097153, 2), (2097153, 3)] + [(262401, C) for C in range(2, 9)])
 def test_weighted_ce_identities(ops, P, C):
     """All-ones weights under the mean are dct_ce_step bit for bit (out2 and dlogits, both accumulate values, gscale set, gmul = 8);
     weight = NULL is all ones; dct_ce_weighted_step is fwd followed by bwd under both reductions; two runs are bit-identical."""
