@@ -128,6 +128,10 @@ SIGNATURES = {
     "dct_focal_step": (_i, [_P, _P, _i64, _i, _i, _P, _f, _i, _P, _P, _f, _P, _i, _P, _sz, _P]),
     "dct_focal_map_fwd": (_i, [_P, _P, _i64, _i, _i, _P, _f, _P, _P]),
     "dct_focal_map_bwd": (_i, [_P, _P, _i64, _i, _i, _P, _f, _P, _f, _P, _i, _P]),
+    "dct_topk_ce_workspace_bytes": (_sz, [_i64]),
+    "dct_topk_ce_fwd": (_i, [_P, _P, _i64, _i, _i, _P, C.c_double, _P, _P, _P, _P, _sz, _P]),
+    "dct_topk_ce_bwd": (_i, [_P, _P, _i64, _i, _i, _P, _P, _P, _P, _P, _f, _P, _i, _P]),
+    "dct_topk_ce_step": (_i, [_P, _P, _i64, _i, _i, _P, C.c_double, _P, _P, _P, _P, _f, _P, _i, _P, _sz, _P]),
     "dct_ce_dice_workspace_bytes": (_sz, [_i, _i, _i]),
     "dct_ce_dice_fwd": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _i, _f, _f, _P, _P, _P, _P, _sz, _P]),
     "dct_ce_dice_bwd": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _i, _f, _f, _P, _P, _P, _f, _P, _i, _P]),

@@ -292,6 +292,202 @@ __global__ __launch_bounds__(256) void loss_map_bwd_kernel(const float* logits, 
   grad_pixels<C, Rule>(rule, logits, tgt, P, gmul, dmap, dl, acc);
 }
 
+// ---- top-k cross entropy: the mean of the K largest entries of the weighted rule's map (the rule: include/dct.h, dct_topk_ce_*) ---------
+// tau, the K-th largest entry, is found by a radix select over the map's order-preserving 32-bit keys, most significant digit first:
+// three histograms (11 + 11 + 10 bits; LDS integer atomics per block, then one global integer add per non-empty bin), and every block
+// of the next launch picks the digit from the finished histogram for itself (the way the fused backward kernels fold the forward
+// partials in every block: no ticket, no last block).  Only integers are added atomically, so nothing depends on arrival order.
+// Workspace, in 32-bit words: the three histograms (zeroed by the entry point), the select's state, then kMaxBlocks partial pairs.
+constexpr int kTopkBins1 = 2048, kTopkBins2 = 2048, kTopkBins3 = 1024;
+constexpr int kTopkHistWords = kTopkBins1 + kTopkBins2 + kTopkBins3;
+constexpr int kTopkSelWords = 16;        // {N, K, digit 1, entries above it, digit 2, entries above digits 1:2}, written by block 0
+constexpr size_t kTopkWsBytes = (size_t)(kTopkHistWords + kTopkSelWords + kMaxBlocks * 2) * 4;
+
+// The key: unsigned order of the keys = float order of the values, -0 on +0's key, every NaN on the largest key (above +inf).
+__device__ __forceinline__ unsigned topk_key(float v) {
+  unsigned b = __float_as_uint(v);
+  if (b == 0x80000000u) b = 0u;
+  const unsigned k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return v != v ? 0xffffffffu : k;
+}
+__device__ __forceinline__ float topk_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+// K = min(N, max(1, floor(N k / 100))) in IEEE double, in this order
+__device__ __forceinline__ unsigned topk_k(unsigned N, double k_percent) {
+  long long k = (long long)floor((double)N * k_percent / 100.0);
+  k = k < 1 ? 1 : k;
+  return (unsigned)(k > (long long)N ? (long long)N : k);
+}
+__device__ __forceinline__ float topk_value(float sum, long long K, long long n_gt, float tau) {
+#pragma clang fp contract(off)    // one rounding per operation in both kernels that form it
+  const float rest = (float)(K - n_gt) * tau;
+  return (sum + rest) / (float)K;
+}
+// Thread i holds bins [i PER, (i + 1) PER) of a histogram of NB = 256 PER bins in h; above = the entries in the bins above its own
+// (a suffix sum: shuffles inside the wave, then the four wave totals), total = all entries.  Every thread of the block calls it.
+template <int NB>
+__device__ __forceinline__ void hist_suffix(const unsigned* hist, unsigned h[NB / 256], unsigned& above, unsigned& total) {
+  constexpr int PER = NB / 256;
+  __shared__ unsigned wsum[4];
+  unsigned mine = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) { h[j] = hist[threadIdx.x * PER + j]; mine += h[j]; }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  unsigned incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned o = __shfl_down(incl, off, 64);
+    incl += (lane + off < 64) ? o : 0u;
+  }
+  if (lane == 0) wsum[w] = incl;
+  __syncthreads();
+  above = incl - mine;
+#pragma unroll
+  for (int k = 1; k < 4; ++k) above += (k > w) ? wsum[k] : 0u;
+  total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// The bin that holds the rank-th largest entry (1 <= rank <= total), in every thread: bin, gt = the entries in the bins above it,
+// cnt = its own.  Exactly one thread's bins straddle the rank; a rank of 0 (nothing counted) leaves {0, 0, 0}.
+template <int NB>
+__device__ __forceinline__ void pick_bin(const unsigned h[NB / 256], unsigned above, unsigned rank, unsigned& bin, unsigned& gt, unsigned& cnt) {
+  constexpr int PER = NB / 256;
+  __shared__ unsigned res[3];
+  if (threadIdx.x == 0) { res[0] = 0u; res[1] = 0u; res[2] = 0u; }
+  __syncthreads();
+  unsigned a = above;
+#pragma unroll
+  for (int j = PER - 1; j >= 0; --j) {
+    if (a < rank && rank <= a + h[j]) { res[0] = threadIdx.x * PER + j; res[1] = a; res[2] = h[j]; }
+    a += h[j];
+  }
+  __syncthreads();
+  bin = res[0]; gt = res[1]; cnt = res[2];
+}
+__device__ __forceinline__ void lds_hist_clear(unsigned* lh, int bins) {
+  for (int i = threadIdx.x; i < bins; i += 256) lh[i] = 0u;
+  __syncthreads();
+}
+__device__ __forceinline__ void lds_hist_flush(const unsigned* lh, int bins, unsigned* hist) {
+  __syncthreads();
+  for (int i = threadIdx.x; i < bins; i += 256) {
+    const unsigned c = lh[i];
+    if (c) atomicAdd(hist + i, c);
+  }
+}
+// Launch 1: loss_map_fwd_kernel<C, WeightedRule> (the same expressions: the map comes out bit for bit) + the histogram of the top 11
+// key bits of the counted pixels.  Its total is N.
+template <int C>
+__global__ __launch_bounds__(256) void topk_map_hist_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                             float* map, unsigned* h1) {
+  __shared__ unsigned lh[kTopkBins1];
+  lds_hist_clear(lh, kTopkBins1);
+  const WeightedRule<C> rule(ignore, weight, 0.f);
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const long long t = tgt[pix];
+    float v = 0.f;
+    if (rule.counted(t)) {
+      float w;
+      v = rule.value(logits, pix, t, w);
+      atomicAdd(&lh[topk_key(v) >> 21], 1u);
+    }
+    map[pix] = v;
+  }
+  lds_hist_flush(lh, kTopkBins1, h1);
+}
+// Launch 2: N and K from the first histogram, the first digit, then the histogram of the next 11 bits of the counted pixels under it.
+// The stored map is read (here and from here on), never a recomputed value; the target only where the key matches.
+__global__ __launch_bounds__(256) void topk_hist2_kernel(const float* map, const long long* tgt, long long P, int ignore, int C, double k_percent,
+                                                          const unsigned* h1, unsigned* h2, unsigned* sel) {
+  __shared__ unsigned lh[kTopkBins2];
+  lds_hist_clear(lh, kTopkBins2);
+  unsigned h[kTopkBins1 / 256], above, N, b1, gt1, cnt;
+  hist_suffix<kTopkBins1>(h1, h, above, N);
+  const unsigned K = N ? topk_k(N, k_percent) : 0u;
+  pick_bin<kTopkBins1>(h, above, K, b1, gt1, cnt);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { sel[0] = N; sel[1] = K; sel[2] = b1; sel[3] = gt1; }
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const unsigned key = topk_key(map[pix]);
+    if ((key >> 21) != b1) continue;
+    const long long t = tgt[pix];
+    if (t != ignore && t >= 0 && t < C) atomicAdd(&lh[(key >> 10) & (kTopkBins2 - 1)], 1u);
+  }
+  lds_hist_flush(lh, kTopkBins2, h2);
+}
+// Launch 3: the second digit, then the histogram of the last 10 bits under the 22-bit prefix.
+__global__ __launch_bounds__(256) void topk_hist3_kernel(const float* map, const long long* tgt, long long P, int ignore, int C,
+                                                          const unsigned* h2, unsigned* h3, unsigned* sel) {
+  __shared__ unsigned lh[kTopkBins3];
+  lds_hist_clear(lh, kTopkBins3);
+  const unsigned K = sel[1], b1 = sel[2], gt1 = sel[3];
+  unsigned h[kTopkBins2 / 256], above, total, b2, gt2, cnt;
+  hist_suffix<kTopkBins2>(h2, h, above, total);
+  pick_bin<kTopkBins2>(h, above, K - gt1, b2, gt2, cnt);
+  const unsigned prefix = (b1 << 11) | b2;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const unsigned key = topk_key(map[pix]);
+    if ((key >> 10) != prefix) continue;
+    const long long t = tgt[pix];
+    if (t != ignore && t >= 0 && t < C) atomicAdd(&lh[key & (kTopkBins3 - 1)], 1u);
+  }
+  lds_hist_flush(lh, kTopkBins3, h3);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { sel[4] = b2; sel[5] = gt1 + gt2; }     // (sel[2:4] were read before pick_bin's barriers)
+}
+// Launch 4: the last digit = tau's key; n_gt and n_eq exactly from the histograms; the block partials of sum_{v > tau} v.  An uncounted
+// pixel's stored 0 may lie above a negative tau: it adds 0.  Keys are compared, so a counted NaN reaches the sum.
+__global__ __launch_bounds__(256) void topk_sum_kernel(const float* map, long long P, const unsigned* h3, const unsigned* sel, float* partial,
+                                                        float* out2, long long* counts4) {
+  const unsigned N = sel[0], K = sel[1], b1 = sel[2], b2 = sel[4], gt2 = sel[5];
+  unsigned h[kTopkBins3 / 256], above, total, b3, gt3, n_eq;
+  hist_suffix<kTopkBins3>(h3, h, above, total);
+  pick_bin<kTopkBins3>(h, above, K - gt2, b3, gt3, n_eq);
+  const unsigned tk = (b1 << 21) | (b2 << 10) | b3;
+  float sum = 0.f;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const float v = map[pix];
+    if (topk_key(v) > tk) sum += v;
+  }
+  block_partial2(sum, 0.f, partial);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    counts4[0] = K; counts4[1] = N; counts4[2] = gt2 + gt3; counts4[3] = n_eq;
+    out2[1] = N ? topk_unkey(tk) : 0.f;
+  }
+}
+__global__ __launch_bounds__(256) void topk_fin_kernel(const float* partial, int blocks, float* out2, const long long* counts4) {
+  float a, b;
+  fold_partials(partial, blocks, a, b);
+  if (threadIdx.x == 0) out2[0] = topk_value(a, counts4[0], counts4[2], out2[1]);
+}
+// dl (=|+=) (g a w)(p - y): a = 1 above tau, (K - n_gt) / n_eq on it, 0 below (those pixels get a plain 0 / keep their old value,
+// without a look at their logits).  partial non-null (the step): block 0 also folds the sum's partials and writes the value, in
+// topk_fin_kernel's order.
+template <int C>
+__global__ __launch_bounds__(256) void topk_bwd_kernel(const float* logits, const long long* tgt, long long P, int ignore, const float* weight,
+                                                        const float* map, const float* out2, const long long* counts4, const float* partial,
+                                                        int blocks, float* value_out, const float* gscale, float gmul, float* dl, int acc) {
+  const long long K = counts4[0], n_gt = counts4[2], n_eq = counts4[3];
+  const float tau = out2[1];
+  if (partial && blockIdx.x == 0) {
+    float a, b;
+    fold_partials(partial, blocks, a, b);
+    if (threadIdx.x == 0) value_out[0] = topk_value(a, K, n_gt, tau);
+  }
+  const WeightedRule<C> rule(ignore, weight, 0.f);
+  const float g = (gscale ? gscale[0] : 1.f) * gmul / (float)K;
+  const float share = (float)(K - n_gt) / (float)n_eq;
+  const unsigned tk = topk_key(tau);
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    const unsigned key = topk_key(map[pix]);
+    float d[C];
+    if (key < tk) {
+      if (acc) continue;
+#pragma unroll
+      for (int c = 0; c < C; ++c) d[c] = 0.f;
+    } else {
+      rule.grad(logits, pix, tgt[pix], key > tk ? g : g * share, d);
+    }
+    store_px<C>(dl, pix, d, acc);
+  }
+}
+
 // ---- boundary loss: the softmax weighted by the signed distance map (the rule: include/dct.h, dct_boundary_*) --------------------------
 // phi has the layout of the logits: both are read with the same loads (16 bytes at C = 4, two of them at C = 8).
 template <int C> __device__ __forceinline__ void load_px16(const float* p, long long pix, float v[C]) {
@@ -1382,6 +1578,71 @@ extern "C" int dct_focal_map_fwd(const float* logits, const int64_t* targets, in
 extern "C" int dct_focal_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
                                  float gamma, const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream) {
   return loss_map_bwd<FocalRule>(px_args(logits, targets, pixels, C_, ignore_index, weight, gamma, stream), dmap, gmul, dlogits, accumulate);
+}
+// ---- top-k cross entropy: the weighted rule's map, three histogram launches of the radix select, the sum above tau ----------------------
+extern "C" size_t dct_topk_ce_workspace_bytes(int64_t) { return kTopkWsBytes; }
+
+static inline bool k_percent_ok(double k) { return k > 0.0 && k <= 100.0; }      // (a NaN fails both comparisons)
+struct TopkWs { unsigned *h1, *h2, *h3, *sel; float* partial; };
+static inline TopkWs topk_ws(void* workspace) {
+  unsigned* w = (unsigned*)workspace;
+  return TopkWs{w, w + kTopkBins1, w + kTopkBins1 + kTopkBins2, w + kTopkHistWords, (float*)(w + kTopkHistWords + kTopkSelWords)};
+}
+// BAD_ARG, then UNSUPPORTED, then WORKSPACE
+static int topk_check(const PxArgs& a, double k_percent, const float* out2, const int64_t* counts4, const float* vmap, void* workspace,
+                      size_t workspace_bytes) {
+  if (!px_ok(a) || !out2 || !counts4 || !vmap || !k_percent_ok(k_percent)) return DCT_ERR_BAD_ARG;
+  if (a.C < 2 || a.C > 8 || a.P > 2147483647LL) return DCT_ERR_UNSUPPORTED;
+  if (!workspace || workspace_bytes < kTopkWsBytes) return DCT_ERR_WORKSPACE;
+  return DCT_OK;
+}
+// the memset of the histograms and launches 1 to 4: vmap, counts4, out2[1] and the partials of the sum above tau; -> the partials' count
+static int topk_select(const PxArgs& a, double k_percent, float* out2, int64_t* counts4, float* vmap, const TopkWs& ws, unsigned& grid) {
+  grid = grid_for(a.P);
+  if (hipMemsetAsync(ws.h1, 0, (size_t)kTopkHistWords * 4, a.st) != hipSuccess) return DCT_ERR_LAUNCH;
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (topk_map_hist_kernel<C>), dim3(grid), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight, vmap, ws.h1));
+  DCT_LAUNCH(DCT_PROF_LOSS, topk_hist2_kernel, dim3(grid), dim3(256), 0, a.st, (const float*)vmap, a.tgt, a.P, a.ignore, a.C, k_percent,
+             (const unsigned*)ws.h1, ws.h2, ws.sel);
+  DCT_LAUNCH(DCT_PROF_LOSS, topk_hist3_kernel, dim3(grid), dim3(256), 0, a.st, (const float*)vmap, a.tgt, a.P, a.ignore, a.C, (const unsigned*)ws.h2,
+             ws.h3, ws.sel);
+  DCT_LAUNCH(DCT_PROF_LOSS, topk_sum_kernel, dim3(grid), dim3(256), 0, a.st, (const float*)vmap, a.P, (const unsigned*)ws.h3, (const unsigned*)ws.sel,
+             ws.partial, out2, (long long*)counts4);
+  return DCT_OK;
+}
+extern "C" int dct_topk_ce_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                               double k_percent, float* out2, int64_t* counts4, float* vmap, void* workspace, size_t workspace_bytes,
+                               dct_stream stream) {
+  const PxArgs a = px_args(logits, targets, pixels, C_, ignore_index, weight, 0.f, stream);
+  if (const int rc = topk_check(a, k_percent, out2, counts4, vmap, workspace, workspace_bytes)) return rc;
+  const TopkWs ws = topk_ws(workspace);
+  unsigned grid;
+  if (const int rc = topk_select(a, k_percent, out2, counts4, vmap, ws, grid)) return rc;
+  DCT_LAUNCH(DCT_PROF_LOSS, topk_fin_kernel, dim3(1), dim3(256), 0, a.st, (const float*)ws.partial, (int)grid, out2, (const long long*)counts4);
+  return dct_check_launch();
+}
+extern "C" int dct_topk_ce_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                               const float* vmap, const float* out2, const int64_t* counts4, const float* gscale, float gmul, float* dlogits,
+                               int accumulate, dct_stream stream) {
+  const PxArgs a = px_args(logits, targets, pixels, C_, ignore_index, weight, 0.f, stream);
+  if (!px_ok(a) || !out2 || !counts4 || !vmap || !dlogits) return DCT_ERR_BAD_ARG;
+  if (a.C < 2 || a.C > 8 || a.P > 2147483647LL) return DCT_ERR_UNSUPPORTED;
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (topk_bwd_kernel<C>), dim3(wide_grid(a.P)), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight, vmap, out2,
+                             (const long long*)counts4, (const float*)nullptr, 0, (float*)nullptr, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+extern "C" int dct_topk_ce_step(const float* logits, const int64_t* targets, int64_t pixels, int C_, int ignore_index, const float* weight,
+                                double k_percent, float* out2, int64_t* counts4, float* vmap, const float* gscale, float gmul, float* dlogits,
+                                int accumulate, void* workspace, size_t workspace_bytes, dct_stream stream) {
+  const PxArgs a = px_args(logits, targets, pixels, C_, ignore_index, weight, 0.f, stream);
+  if (!dlogits) return DCT_ERR_BAD_ARG;
+  if (const int rc = topk_check(a, k_percent, out2, counts4, vmap, workspace, workspace_bytes)) return rc;
+  const TopkWs ws = topk_ws(workspace);
+  unsigned grid;
+  if (const int rc = topk_select(a, k_percent, out2, counts4, vmap, ws, grid)) return rc;
+  DISPATCH_C(a.C, DCT_LAUNCH(DCT_PROF_LOSS, (topk_bwd_kernel<C>), dim3(wide_grid(a.P)), dim3(256), 0, a.st, a.logits, a.tgt, a.P, a.ignore, a.weight,
+                             (const float*)vmap, (const float*)out2, (const long long*)counts4, (const float*)ws.partial, (int)grid, out2, gscale, gmul,
+                             dlogits, accumulate));
+  return dct_check_launch();
 }
 // K of a boundary mask (the number of its bits below C), or a status
 static inline int boundary_k(int64_t pixels, int C_, int class_mask, float& K) {

@@ -569,6 +569,41 @@ def focal_map_bwd(logits_pc, targets, C_, dmap, dlogits, weight=None, gamma=2.0,
     return dlogits
 
 
+def _topk_ce_bufs(P, device):
+    """(out2, counts4, vmap, workspace) of one dct_topk_ce_* call: fresh tensors, so that a captured graph owns them."""
+    return (torch.empty(2, dtype=torch.float32, device=device), torch.empty(4, dtype=torch.int64, device=device),
+            torch.empty(P, dtype=torch.float32, device=device),
+            torch.empty(_lib.load().dct_topk_ce_workspace_bytes(P), dtype=torch.uint8, device=device))
+
+
+def topk_ce_fwd(logits_pc, targets, C_, weight=None, k_percent=10.0, ignore_index=255):
+    """Top-k cross entropy (dct_topk_ce_fwd; the rule: include/dct.h): the mean of w_t l over the hardest ``k_percent`` % of the counted
+    pixels.  ``weight``: fp32 [C] on the device, or None (all ones); ``k_percent``: a host float, 0 < k <= 100.  Returns the device
+    tensors ``out2`` = (value, tau), ``counts4`` = int64 (K, N, n_gt, n_eq) and ``vmap`` [P], the stored map the selection compared."""
+    P = logits_pc.numel() // C_
+    out2, counts4, vmap, ws = _topk_ce_bufs(P, logits_pc.device)
+    call("dct_topk_ce_fwd", ptr(logits_pc), ptr(targets), P, C_, int(ignore_index), ptr(weight), float(k_percent), ptr(out2), ptr(counts4),
+         ptr(vmap), ptr(ws), ws.numel(), stream())
+    return out2, counts4, vmap
+
+
+def topk_ce_bwd(logits_pc, targets, C_, vmap, out2, counts4, dlogits, weight=None, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
+    """``vmap``, ``out2`` and ``counts4``: those of topk_ce_fwd under the same arguments."""
+    call("dct_topk_ce_bwd", ptr(logits_pc), ptr(targets), logits_pc.numel() // C_, C_, int(ignore_index), ptr(weight), ptr(vmap), ptr(out2),
+         ptr(counts4), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), stream())
+    return dlogits
+
+
+def topk_ce_step(logits_pc, targets, C_, dlogits, weight=None, k_percent=10.0, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
+    """topk_ce_fwd + topk_ce_bwd of the same logits (dct_topk_ce_step; bit for bit the two calls).  Returns (out2, counts4, vmap);
+    ``dlogits`` is written (added to)."""
+    P = logits_pc.numel() // C_
+    out2, counts4, vmap, ws = _topk_ce_bufs(P, logits_pc.device)
+    call("dct_topk_ce_step", ptr(logits_pc), ptr(targets), P, C_, int(ignore_index), ptr(weight), float(k_percent), ptr(out2), ptr(counts4),
+         ptr(vmap), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), ptr(ws), ws.numel(), stream())
+    return out2, counts4, vmap
+
+
 def _i64_dense(t):
     """int64, contiguous and on the 16-byte grid (a dense view that starts inside its storage gets a copy of its own)."""
     if t.dtype != torch.int64 or not t.is_contiguous():

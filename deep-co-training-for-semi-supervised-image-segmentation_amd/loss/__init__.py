@@ -3,12 +3,14 @@ from .loss import CrossEntropyLoss2d, CrossEntropyDiceLoss2d, DiceLoss, JSD_2D, 
 from .loss import BoundaryLoss, CrossEntropyBoundaryLoss2d, signed_distance_map  # noqa: F401
 from .loss import PseudoLabel_2D, CrossPseudoSupervision_2D, EnsemblePseudoLabel_2D  # noqa: F401
 from .loss import FocalLoss2d  # noqa: F401
+from .loss import TopKCrossEntropyLoss2d  # noqa: F401
 from . import loss as _loss_mod
 
 __all__ = ['get_loss_fn']
 
 LOSS = {'cross_entropy': CrossEntropyLoss2d,
         'focal': FocalLoss2d,
+        'topk_ce': TopKCrossEntropyLoss2d,
         'dice': DiceLoss,
         'ce_dice': CrossEntropyDiceLoss2d,
         'boundary': BoundaryLoss,

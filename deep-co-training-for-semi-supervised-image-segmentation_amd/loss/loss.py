@@ -192,6 +192,65 @@ class FocalLoss2d(_ClassWeighted):
         return _ReducedFn.apply(outputs, targets, 'focal', dict(kw, reduction=K.CE_MEAN if self.reduction == 'mean' else K.CE_SUM))
 
 
+class _TopKFn(torch.autograd.Function):
+    """The top-k cross entropy on dct_topk_ce_*.  Returns the value and, without a gradient, ``out2`` = (value, tau) and ``counts4`` =
+    (K, N, n_gt, n_eq); the backward launch compares the map the forward launch stored."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, k_percent, ignore_index):
+        lp = _pc(logits)
+        t = _targets(targets)
+        out2, counts4, vmap = K.topk_ce_fwd(lp, t, lp.shape[3], weight, k_percent, ignore_index)
+        ctx.save_for_backward(lp, t, vmap, out2, counts4)
+        ctx.weight, ctx.ignore_index = weight, ignore_index
+        info = out2.clone()
+        ctx.mark_non_differentiable(info, counts4)
+        return out2[0], info, counts4
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        lp, t, vmap, out2, counts4 = ctx.saved_tensors
+        dl = torch.empty_like(lp)
+        g = g.to(torch.float32).contiguous()
+        K.topk_ce_bwd(lp, t, lp.shape[3], vmap, out2, counts4, dl, weight=ctx.weight, gscale=g, ignore_index=ctx.ignore_index)
+        return _nchw(dl), None, None, None, None
+
+
+class TopKCrossEntropyLoss2d(_ClassWeighted):
+    """Top-k cross entropy (nnU-Net's ``TopKLoss``, online hard-example mining): the mean of the per-pixel class-weighted cross entropy
+    ``w_t l`` over the hardest ``k`` % of the counted pixels only (the rule: include/dct.h, dct_topk_ce_*), so that the mass of easy
+    background stops diluting the mean.  ``k``: a number, finite, 0 < k <= 100; 100 is ``sum w_t l / N`` (with ``weight=None`` the plain
+    mean cross entropy).  ``weight`` and ``ignore_index`` as on ``CrossEntropyLoss2d``.  Returns a scalar only.  After a call
+    ``last_topk`` = (``out2``, ``counts4``): the device tensors (value, tau) and int64 (K, N, n_gt, n_eq) for logging (nothing
+    synchronises)."""
+
+    def __init__(self, k=10.0, weight=None, ignore_index=255):
+        super().__init__()
+        try:
+            self.k = float(k)
+        except (TypeError, ValueError):
+            raise ValueError(f"dct_amd {type(self).__name__}: k must be a number, got {k!r}")
+        if not (0.0 < self.k <= 100.0):
+            raise ValueError(f"dct_amd {type(self).__name__}: k must be finite with 0 < k <= 100, got {k!r}")
+        self._set_weight(weight)
+        self.reduction = 'mean'
+        self.ignore_index = ignore_index
+        self.last_topk = None
+
+    def launch_args(self, C):
+        """The keyword arguments of hip_ops.topk_ce_* beyond the weights (the same for every ``C``)."""
+        return dict(k_percent=self.k)
+
+    def forward(self, outputs, targets):
+        assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
+        if not outputs.is_cuda:
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        w = self.device_weight(outputs.device, outputs.shape[1])
+        value, out2, counts4 = _TopKFn.apply(outputs, targets, w, self.k, self.ignore_index)
+        self.last_topk = (out2, counts4)
+        return value
+
+
 class _CEDiceFn(torch.autograd.Function):
     """``ce_coef`` ce + ``dice_coef`` dice on dct_ce_dice_*; ``rule``: the launch arguments of ``CrossEntropyDiceLoss2d.launch_args``.
     Returns the total and, without a gradient, the [G, C] table of D_gc."""

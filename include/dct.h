@@ -333,6 +333,45 @@ int dct_focal_map_fwd(const float* logits, const int64_t* targets, int64_t pixel
                       const float* weight /*nullable*/, float gamma, float* map, dct_stream stream);
 int dct_focal_map_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
                       const float* weight, float gamma, const float* dmap, float gmul, float* dlogits, int accumulate, dct_stream stream);
+/* Top-k cross entropy (nnU-Net's TopKLoss; online hard-example mining): the mean of the per-pixel class-weighted cross entropy over the
+ * hardest k_percent of the counted pixels only.  logits, targets, weight and ignore_index are those of dct_ce_weighted_*; k_percent: a
+ * host double, finite, 0 < k_percent <= 100.  A pixel is counted exactly as in dct_ce_weighted_*: t != ignore_index && 0 <= t < C.
+ *   v_i = w_i l_i for a counted pixel, 0 for an uncounted one: bit for bit the map of dct_ce_map_fwd.  The forward call stores it in vmap
+ *       (fp32 [pixels], provided by the caller), and every later comparison reads the stored value, never a recomputed one (a backward
+ *       kernel whose recomputed v_i differed in the last bit would put the pixel on the wrong side of the threshold).
+ *   N = the number of counted pixels;  K = min(N, max(1, (int64) floor((double) N * k_percent / 100.0))), formed on the device in IEEE
+ *       double in this order (Python's int(N * k / 100), clamped).
+ *   tau = the K-th largest v_i over the counted pixels, in the order of float comparison with -0 equal to +0.  Negative values are allowed
+ *       (weights need not be >= 0).  A NaN orders above +inf: if any counted v_i is NaN the value is NaN and the gradient is unspecified.
+ *   n_gt = #{counted i: v_i > tau}, n_eq = #{counted i: v_i == tau}, so n_gt < K <= n_gt + n_eq.
+ * Value: out2[0] = (sum_{v_i > tau} v_i + (float)(K - n_gt) * tau) / (float) K, out2[1] = tau: the mean of torch.topk(v, K) whatever the
+ *   ties are.  counts4 (int64 [4] on the device) = {K, N, n_gt, n_eq}.  N == 0: K = 0, the value is NaN, every gradient entry exactly 0
+ *   (the old value under accumulate).  k_percent == 100 with weight == NULL is the plain mean cross entropy; with weights it is
+ *   sum w l / N, not / sum w.
+ * Gradient: dlogits[i][c] (=|+=) (g a_i w_i)(p_c - y_c) with g = gscale[0] * gmul / (float) K (gscale nullable = 1); a_i = 1 where
+ *   v_i > tau, (float)(K - n_gt) / (float) n_eq where v_i == tau (the ties share what is left: a valid subgradient that depends on neither
+ *   pixel order nor launch geometry), 0 below tau.  Uncounted pixels and counted pixels below tau get exactly 0 for finite logits (exactly
+ *   the old value under accumulate).
+ * tau is found by a most-significant-digit radix select (11 + 11 + 10 bits) over the order-preserving 32-bit keys of the stored map; the
+ *   histograms use integer atomics only, the float sum is folded in one fixed order without float atomics: bit-identical from run to
+ *   run.  Nothing synchronises with the host.  The entry point zeroes the histograms itself (a memset on the stream): the caller never
+ *   clears the workspace.
+ * dct_topk_ce_bwd: vmap, out2 and counts4 are those of the forward call under the same arguments.
+ * dct_topk_ce_step: fwd + bwd of the same logits; out2, counts4, vmap and dlogits are bit for bit those of the two calls.
+ * DCT_ERR_BAD_ARG: as for dct_ce_weighted_*, a null vmap / counts4, or a k_percent that is NaN, <= 0 or > 100; DCT_ERR_UNSUPPORTED: C
+ * outside 2..8, or pixels > 2^31 - 1; DCT_ERR_WORKSPACE: less than dct_topk_ce_workspace_bytes(pixels) of workspace.
+ * Out of scope: per-image top-k, top-k + Dice in one launch, k_percent in device memory, top-k of the focal map, probabilities as
+ * input. */
+size_t dct_topk_ce_workspace_bytes(int64_t pixels);
+int dct_topk_ce_fwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                    const float* weight /*nullable*/, double k_percent, float* out2, int64_t* counts4, float* vmap, void* workspace,
+                    size_t workspace_bytes, dct_stream stream);
+int dct_topk_ce_bwd(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                    const float* weight, const float* vmap, const float* out2, const int64_t* counts4, const float* gscale, float gmul,
+                    float* dlogits, int accumulate, dct_stream stream);
+int dct_topk_ce_step(const float* logits, const int64_t* targets, int64_t pixels, int C, int ignore_index,
+                     const float* weight, double k_percent, float* out2, int64_t* counts4, float* vmap, const float* gscale, float gmul,
+                     float* dlogits, int accumulate, void* workspace, size_t workspace_bytes, dct_stream stream);
 /* Soft Dice and CE + Dice as one supervised criterion (the reference's loss/dice.py, SURVEY 2 row 3, on logits).  logits: fp32 NHWC
  * [B][pixels_per_image][C]; targets: int64 [B * pixels_per_image]; weight: the C fp32 class weights of the CE term on the device, nullable
  * = all ones, exactly as in dct_ce_weighted_*; class_mask: bit c set = class c takes part in the Dice mean, K = the number of set bits
