@@ -136,6 +136,10 @@ SIGNATURES = {
     "dct_ce_dice_fwd": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _i, _f, _f, _P, _P, _P, _P, _sz, _P]),
     "dct_ce_dice_bwd": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _i, _f, _f, _P, _P, _P, _f, _P, _i, _P]),
     "dct_ce_dice_step": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _i, _f, _f, _P, _P, _P, _P, _f, _P, _i, _P, _sz, _P]),
+    "dct_ce_tversky_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dct_ce_tversky_fwd": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _f, _f, _f, _i, _f, _f, _P, _P, _P, _P, _sz, _P]),
+    "dct_ce_tversky_bwd": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _f, _f, _f, _i, _f, _f, _P, _P, _P, _f, _P, _i, _P]),
+    "dct_ce_tversky_step": (_i, [_P, _P, _i, _i64, _i, _i, _P, _i, _f, _f, _f, _f, _i, _f, _f, _P, _P, _P, _P, _f, _P, _i, _P, _sz, _P]),
     "dct_signed_distance_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "dct_signed_distance": (_i, [_P, _i, _i, _i, _i, _i, _f, _f, _P, _P, _sz, _P]),
     "dct_boundary_fwd": (_i, [_P, _P, _P, _i64, _i, _i, _i, _P, _P, _sz, _P]),

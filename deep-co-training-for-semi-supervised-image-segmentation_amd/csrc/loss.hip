@@ -775,6 +775,119 @@ __global__ __launch_bounds__(256) void ce_dice_bwd_fin_kernel(const float* logit
   ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, ce2[1], r, qa, qb, dl, acc);
 }
 
+// ---- Tversky and focal Tversky, alone or beside CE (the rule: include/dct.h) -----------------------------------------------------------------
+// The sums are Dice's: ce_dice_fwd_kernel writes the partial rows, fold_rows / wave_fold_rows / ce_dice_fold fold them in Dice's order and
+// ce_dice_grad_pixels writes the gradient from qa, qb.  What differs is the rule from {I, S, Y} to the value and to qa, qb (tversky_terms),
+// evaluated per block (and by one thread per group for the outputs), never per pixel.
+// c0 = fl(1 - alpha - beta) and e = fl(1 / gamma), formed on the host in double; focal = gamma != 1 (gamma == 1 evaluates no power function)
+struct TverskyRule { int mask, per_image, focal; float smooth, ce_coef, tv_coef, inv_gk, alpha, beta, c0, e; };
+
+__device__ __forceinline__ DiceRule as_dice(TverskyRule r) { return DiceRule{r.mask, r.per_image, r.smooth, r.ce_coef, r.tv_coef, r.inv_gk}; }
+// T = (I + smooth) / Den, Den = c0 I + alpha S + beta Y + smooth in the order written; term = u^e with u = max(1 - T, 0) (u when !focal);
+// with f = m e u^(e - 1) (m when !focal): a = f (1 - c0 T) / Den, b = f alpha T / Den.  Den == 0: T = 1; Den == 0 or u == 0: term = a = b = 0.
+__device__ __forceinline__ void tversky_terms(float I, float S, float Y, TverskyRule r, float m, float& T, float& term, float& a, float& b) {
+#pragma clang fp contract(off)    // one rounding per operation wherever this is inlined: _step's numbers are _fwd's and _bwd's
+  const float den = ((r.c0 * I + r.alpha * S) + r.beta * Y) + r.smooth;
+  const float num = I + r.smooth;
+  const bool empty = den == 0.f;
+  const float ds = empty ? 1.f : den;
+  T = empty ? 1.f : num / ds;
+  const float u = fmaxf(1.f - T, 0.f);
+  const bool some = u > 0.f;                                               // (false under an empty denominator: T = 1)
+  const float us = some ? u : 1.f;
+  float pw = us, f = m;
+  if (r.focal) {                                                           // (the same in every lane)
+    const float lg = log2f(us);
+    pw = exp2f(r.e * lg);
+    f = (m * r.e) * exp2f((r.e - 1.f) * lg);
+  }
+  term = some ? pw : 0.f;
+  a = some ? (f * (1.f - r.c0 * T)) / ds : 0.f;
+  b = some ? ((f * r.alpha) * T) / ds : 0.f;
+}
+// q_c = qb[c] - [t == c] qa[c] from a group's folded sums d = {I, S, Y} per class
+template <int C> __device__ __forceinline__ void tversky_coeffs(const float* d, TverskyRule r, float qa[C], float qb[C]) {
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float T, term;
+    tversky_terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r, ((r.mask >> c) & 1) ? r.inv_gk : 0.f, T, term, qa[c], qb[c]);
+  }
+}
+// group g's rows of tversky_gc [G][C] and sums [G][C][3] from its folded sums (one thread); -> the sum of the terms over the classes of the mask
+template <int C> __device__ __forceinline__ float tversky_group_out(const float d[3 * C], int g, TverskyRule r, float* tversky_gc, float* sums) {
+  float tsum = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float T, term, a, b;
+    tversky_terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r, 0.f, T, term, a, b);
+    tversky_gc[g * C + c] = T;
+    sums[(g * C + c) * 3 + 0] = d[3 * c]; sums[(g * C + c) * 3 + 1] = d[3 * c + 1]; sums[(g * C + c) * 3 + 2] = d[3 * c + 2];
+    if ((r.mask >> c) & 1) tsum += term;
+  }
+  return tsum;
+}
+// ce_dice_finish's walk (the whole block calls it; under per_image wave w takes groups w, w + 4, ... and the four waves' sums are added
+// in order) with the Tversky terms: out4 = {total, ce, sum w, tversky}
+template <int C>
+__device__ __forceinline__ void ce_tversky_finish(const float* partial, int B, int fbx, TverskyRule r, float* out4, float* tversky_gc, float* sums, float* sm) {
+  constexpr int NS = 3 * C + 2;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  float ce2[2], d[3 * C], tsum = 0.f;
+  if (!r.per_image) {
+    ce_dice_fold<C>(partial, B, fbx, 0, 0, sm, ce2, d);
+    if (threadIdx.x == 0) tsum = tversky_group_out<C>(d, 0, r, tversky_gc, sums);
+  } else {
+    fold_rows<NS, 0, 2>(partial, 0, B * fbx, sm, ce2);
+    for (int g = w; g < B; g += 4) {
+      wave_fold_rows<NS, 2, 3 * C>(partial, g * fbx, fbx, d);
+      if (lane == 0) tsum += tversky_group_out<C>(d, g, r, tversky_gc, sums);
+    }
+    __syncthreads();                     // (fold_rows' readers are done with sm)
+    if (lane == 0) sm[w] = tsum;
+    __syncthreads();
+    tsum = sm[0] + sm[1] + sm[2] + sm[3];
+  }
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    const float ce = ce2[0] / ce2[1];
+    const float tv = tsum * r.inv_gk;
+    float total = 0.f;
+    if (r.ce_coef != 0.f) total = r.ce_coef * ce;            // a coefficient of exactly 0 removes its term (a NaN ce with it)
+    if (r.tv_coef != 0.f) total = total + r.tv_coef * tv;
+    out4[0] = total; out4[1] = ce; out4[2] = ce2[1]; out4[3] = tv;
+  }
+}
+template <int C>
+__global__ __launch_bounds__(256) void ce_tversky_fin_kernel(const float* partial, int B, int fbx, TverskyRule r, float* out4, float* tversky_gc, float* sums) {
+  __shared__ float sm[4 * (3 * C + 2)];
+  ce_tversky_finish<C>(partial, B, fbx, r, out4, tversky_gc, sums, sm);
+}
+template <int C>
+__global__ __launch_bounds__(256) void ce_tversky_bwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore, const float* weight,
+                                                              TverskyRule r, const float* out4, const float* sums, const float* gscale, float gmul,
+                                                              float* dl, int acc) {
+  float wr[C], qa[C], qb[C];
+  load_weights<C>(weight, wr);
+  tversky_coeffs<C>(sums + (r.per_image ? (long long)blockIdx.y * C * 3 : 0), r, qa, qb);
+  ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, out4[2], as_dice(r), qa, qb, dl, acc);
+}
+// ce_dice_bwd_fin_kernel's pattern: every block folds the forward rows it needs in ce_tversky_fin_kernel's order, block (0, 0) also writes
+// what that kernel writes, then the gradient
+template <int C>
+__global__ __launch_bounds__(256) void ce_tversky_bwd_fin_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
+                                                                  const float* weight, TverskyRule r, const float* partial, int fbx, float* out4,
+                                                                  float* tversky_gc, float* sums, const float* gscale, float gmul, float* dl, int acc) {
+  __shared__ float sm[4 * (3 * C + 2)];
+  const int B = gridDim.y;
+  float ce2[2], d[3 * C];
+  ce_dice_fold<C>(partial, B, fbx, r.per_image, blockIdx.y, sm, ce2, d);
+  if (blockIdx.x == 0 && blockIdx.y == 0) ce_tversky_finish<C>(partial, B, fbx, r, out4, tversky_gc, sums, sm);
+  float wr[C], qa[C], qb[C];
+  load_weights<C>(weight, wr);
+  tversky_coeffs<C>(d, r, qa, qb);
+  ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, ce2[1], as_dice(r), qa, qb, dl, acc);
+}
+
 // ---- softmax / entropy (module API) -------------------------------------------------------------
 template <int C>
 __global__ __launch_bounds__(256) void softmax_fwd_kernel(const float* logits, float* probs, long long P) {
@@ -1745,6 +1858,63 @@ extern "C" int dct_ce_dice_step(const float* logits, const int64_t* targets, int
                             ignore_index, weight, (float*)workspace));
   DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_bwd_fin_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
                             ignore_index, weight, r, (const float*)workspace, (int)fbx, out4, dice_gc, sums, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+// dice_rule's checks and the Tversky parameters' own; 1 - alpha - beta and 1 / gamma are formed in double and rounded once each
+static int tversky_rule(int B, int64_t ppi, int C_, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
+                        float ce_coef, float tv_coef, TverskyRule& r) {
+  DiceRule d;
+  if (const int e = dice_rule(B, ppi, C_, class_mask, smooth, per_image, ce_coef, tv_coef, d)) return e;
+  if (!(alpha >= 0.f) || !(beta >= 0.f) || __builtin_isinf(alpha) || __builtin_isinf(beta) || alpha + beta == 0.f) return DCT_ERR_BAD_ARG;
+  if (!(gamma > 0.f) || __builtin_isinf(gamma)) return DCT_ERR_BAD_ARG;
+  r = TverskyRule{d.mask, per_image, gamma != 1.f, smooth, ce_coef, tv_coef, d.inv_gk, alpha, beta,
+                  (float)(1.0 - (double)alpha - (double)beta), (float)(1.0 / (double)gamma)};
+  return DCT_OK;
+}
+extern "C" size_t dct_ce_tversky_workspace_bytes(int B, int C_, int per_image) { return dct_ce_dice_workspace_bytes(B, C_, per_image); }
+extern "C" int dct_ce_tversky_fwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
+                                  const float* weight, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
+                                  float ce_coef, float tversky_coef, float* out4, float* tversky_gc, float* sums, void* workspace,
+                                  size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !out4 || !tversky_gc || !sums) return DCT_ERR_BAD_ARG;
+  TverskyRule r;
+  if (const int e = tversky_rule(B, pixels_per_image, C_, class_mask, smooth, alpha, beta, gamma, per_image, ce_coef, tversky_coef, r)) return e;
+  if (!workspace || workspace_bytes < dice_ws_bytes(B, C_)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned fbx = dice_grid_x(pixels_per_image, B, kDiceFwdBlocks);
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fwd_kernel<C>, dim3(fbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
+                            ignore_index, weight, (float*)workspace));
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_tversky_fin_kernel<C>, dim3(1), dim3(256), 0, st, (const float*)workspace, B, (int)fbx, r, out4, tversky_gc, sums));
+  return dct_check_launch();
+}
+extern "C" int dct_ce_tversky_bwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
+                                  const float* weight, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
+                                  float ce_coef, float tversky_coef, const float* out4, const float* sums, const float* gscale, float gmul,
+                                  float* dlogits, int accumulate, dct_stream stream) {
+  if (!logits || !targets || !out4 || !sums || !dlogits) return DCT_ERR_BAD_ARG;
+  TverskyRule r;
+  if (const int e = tversky_rule(B, pixels_per_image, C_, class_mask, smooth, alpha, beta, gamma, per_image, ce_coef, tversky_coef, r)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned bbx = dice_grid_x(pixels_per_image, B, kDiceBwdBlocks);
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_tversky_bwd_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
+                            ignore_index, weight, r, out4, sums, gscale, gmul, dlogits, accumulate));
+  return dct_check_launch();
+}
+extern "C" int dct_ce_tversky_step(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
+                                   const float* weight, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
+                                   float ce_coef, float tversky_coef, float* out4, float* tversky_gc, float* sums, const float* gscale,
+                                   float gmul, float* dlogits, int accumulate, void* workspace, size_t workspace_bytes, dct_stream stream) {
+  if (!logits || !targets || !out4 || !tversky_gc || !sums || !dlogits) return DCT_ERR_BAD_ARG;
+  TverskyRule r;
+  if (const int e = tversky_rule(B, pixels_per_image, C_, class_mask, smooth, alpha, beta, gamma, per_image, ce_coef, tversky_coef, r)) return e;
+  if (!workspace || workspace_bytes < dice_ws_bytes(B, C_)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned fbx = dice_grid_x(pixels_per_image, B, kDiceFwdBlocks);       // dct_ce_tversky_fwd's grid: the same partial rows
+  const unsigned bbx = dice_grid_x(pixels_per_image, B, kDiceBwdBlocks);       // dct_ce_tversky_bwd's grid
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fwd_kernel<C>, dim3(fbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
+                            ignore_index, weight, (float*)workspace));
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_tversky_bwd_fin_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
+                            ignore_index, weight, r, (const float*)workspace, (int)fbx, out4, tversky_gc, sums, gscale, gmul, dlogits, accumulate));
   return dct_check_launch();
 }
 extern "C" int dct_softmax_fwd(const float* logits, float* probs, int64_t pixels, int C_, dct_stream stream) {

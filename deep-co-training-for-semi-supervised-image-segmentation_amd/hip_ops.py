@@ -695,6 +695,53 @@ def ce_dice_step(logits_bpc, targets, C_, dlogits, weight=None, class_mask=None,
     return out4, dice_gc, sums
 
 
+def _ce_tversky_ws(B, C_, per_image, device):
+    return torch.empty(_lib.load().dct_ce_tversky_workspace_bytes(B, C_, int(per_image)), dtype=torch.uint8, device=device)
+
+
+def ce_tversky_fwd(logits_bpc, targets, C_, weight=None, class_mask=None, smooth=1e-5, alpha=0.3, beta=0.7, gamma=1.0, per_image=False,
+                   ce_coef=1.0, tversky_coef=1.0, ignore_index=255):
+    """Tversky / focal Tversky / CE + Tversky (dct_ce_tversky_fwd; the rule: include/dct.h).  ``logits_bpc``: fp32 [B, ..., C] dense;
+    ``targets``: int64, one per pixel; ``class_mask``: bit c = class c is in the mean (None: all).  Returns device tensors ``out4`` =
+    (total, ce, sum w, tversky), ``tversky_gc`` [G, C] (the index T_gc) and ``sums`` [G, C, 3] (G = B under ``per_image``, else 1)."""
+    B, ppi, mask, G = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
+    dev = logits_bpc.device
+    out4 = torch.empty(4, dtype=torch.float32, device=dev)
+    tversky_gc = torch.empty(G, C_, dtype=torch.float32, device=dev)
+    sums = torch.empty(G, C_, 3, dtype=torch.float32, device=dev)
+    ws = _ce_tversky_ws(B, C_, per_image, dev)
+    call("dct_ce_tversky_fwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), float(alpha),
+         float(beta), float(gamma), int(per_image), float(ce_coef), float(tversky_coef), ptr(out4), ptr(tversky_gc), ptr(sums), ptr(ws),
+         ws.numel(), stream())
+    return out4, tversky_gc, sums
+
+
+def ce_tversky_bwd(logits_bpc, targets, C_, out4, sums, dlogits, weight=None, class_mask=None, smooth=1e-5, alpha=0.3, beta=0.7, gamma=1.0,
+                   per_image=False, ce_coef=1.0, tversky_coef=1.0, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
+    """``out4`` and ``sums``: those of ce_tversky_fwd under the same arguments."""
+    B, ppi, mask, _ = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
+    call("dct_ce_tversky_bwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), float(alpha),
+         float(beta), float(gamma), int(per_image), float(ce_coef), float(tversky_coef), ptr(out4), ptr(sums), ptr(gscale), float(gmul),
+         ptr(dlogits), int(accumulate), stream())
+    return dlogits
+
+
+def ce_tversky_step(logits_bpc, targets, C_, dlogits, weight=None, class_mask=None, smooth=1e-5, alpha=0.3, beta=0.7, gamma=1.0,
+                    per_image=False, ce_coef=1.0, tversky_coef=1.0, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
+    """ce_tversky_fwd + ce_tversky_bwd of the same logits in two launches (dct_ce_tversky_step; bit for bit the two calls).  Returns
+    (out4, tversky_gc, sums); ``dlogits`` is written (added to)."""
+    B, ppi, mask, G = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
+    dev = logits_bpc.device
+    out4 = torch.empty(4, dtype=torch.float32, device=dev)
+    tversky_gc = torch.empty(G, C_, dtype=torch.float32, device=dev)
+    sums = torch.empty(G, C_, 3, dtype=torch.float32, device=dev)
+    ws = _ce_tversky_ws(B, C_, per_image, dev)
+    call("dct_ce_tversky_step", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), float(alpha),
+         float(beta), float(gamma), int(per_image), float(ce_coef), float(tversky_coef), ptr(out4), ptr(tversky_gc), ptr(sums), ptr(gscale),
+         float(gmul), ptr(dlogits), int(accumulate), ptr(ws), ws.numel(), stream())
+    return out4, tversky_gc, sums
+
+
 def softmax_fwd(logits_pc, C_):
     probs = torch.empty_like(logits_pc)
     call("dct_softmax_fwd", ptr(logits_pc), ptr(probs), logits_pc.numel() // C_, C_, stream())

@@ -4,6 +4,7 @@ from .loss import BoundaryLoss, CrossEntropyBoundaryLoss2d, signed_distance_map 
 from .loss import PseudoLabel_2D, CrossPseudoSupervision_2D, EnsemblePseudoLabel_2D  # noqa: F401
 from .loss import FocalLoss2d  # noqa: F401
 from .loss import TopKCrossEntropyLoss2d  # noqa: F401
+from .loss import CrossEntropyTverskyLoss2d, FocalTverskyLoss, TverskyLoss  # noqa: F401
 from . import loss as _loss_mod
 
 __all__ = ['get_loss_fn']
@@ -13,6 +14,9 @@ LOSS = {'cross_entropy': CrossEntropyLoss2d,
         'topk_ce': TopKCrossEntropyLoss2d,
         'dice': DiceLoss,
         'ce_dice': CrossEntropyDiceLoss2d,
+        'tversky': TverskyLoss,
+        'focal_tversky': FocalTverskyLoss,
+        'ce_tversky': CrossEntropyTverskyLoss2d,
         'boundary': BoundaryLoss,
         'ce_boundary': CrossEntropyBoundaryLoss2d,
         'jsd': JSD_2D,

@@ -322,6 +322,100 @@ class DiceLoss(CrossEntropyDiceLoss2d):
         super().__init__(None, 0.0, 1.0, classes, smooth, per_image, ignore_index)
 
 
+class _CETverskyFn(torch.autograd.Function):
+    """``ce_coef`` ce + ``tversky_coef`` tversky on dct_ce_tversky_*; ``rule``: the launch arguments of
+    ``CrossEntropyTverskyLoss2d.launch_args``.  Returns the total and, without a gradient, the [G, C] table of T_gc."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, weight, rule, ignore_index):
+        lp = _pc(logits)
+        t = _targets(targets)
+        out4, tversky_gc, sums = K.ce_tversky_fwd(lp, t, lp.shape[3], weight, ignore_index=ignore_index, **rule)
+        ctx.save_for_backward(lp, t, out4, sums)
+        ctx.weight, ctx.rule, ctx.ignore_index = weight, rule, ignore_index
+        ctx.mark_non_differentiable(tversky_gc)
+        return out4[0], tversky_gc
+
+    @staticmethod
+    def backward(ctx, g, _):
+        lp, t, out4, sums = ctx.saved_tensors
+        dl = torch.empty_like(lp)
+        g = g.to(torch.float32).contiguous()
+        K.ce_tversky_bwd(lp, t, lp.shape[3], out4, sums, dl, weight=ctx.weight, gscale=g, ignore_index=ctx.ignore_index, **ctx.rule)
+        return _nchw(dl), None, None, None, None
+
+
+def _number(value, what, who):
+    try:
+        return float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"dct_amd {who}: {what} must be a number, got {value!r}")
+
+
+class CrossEntropyTverskyLoss2d(_ClassWeighted):
+    """``ce_coef`` * class-weighted mean cross entropy + ``tversky_coef`` * focal Tversky loss of the softmax (Salehi et al. 2017; Abraham &
+    Khan 2019; the rule: include/dct.h, dct_ce_tversky_*), in one forward and one backward launch pair.  Per group and class the index is
+    ``T = (I + smooth) / (I + alpha FP + beta FN + smooth)`` and the loss the mean of ``(1 - T)^(1 / gamma)``: ``alpha`` weighs the false
+    positives, ``beta`` the false negatives (both finite and >= 0, not both 0; 0.5 / 0.5 is Dice, 1 / 1 Jaccard), ``gamma`` (finite, > 0;
+    1: plain Tversky) is the focal parameter.  ``classes``, ``smooth``, ``per_image``, ``weight`` and ``ignore_index`` as on
+    ``CrossEntropyDiceLoss2d``.  After a call ``last_tversky`` is the [G, C] device tensor of T_gc of every class (nothing synchronises).
+    A coefficient of exactly 0 removes its term."""
+
+    def __init__(self, weight=None, ce_coef=1.0, tversky_coef=1.0, alpha=0.3, beta=0.7, gamma=1.0, classes=None, smooth=1e-5,
+                 per_image=False, ignore_index=255):
+        super().__init__()
+        who = type(self).__name__
+        self._set_weight(weight)
+        self.ce_coef, self.tversky_coef = _number(ce_coef, "ce_coef", who), _number(tversky_coef, "tversky_coef", who)
+        self.alpha, self.beta, self.gamma = _number(alpha, "alpha", who), _number(beta, "beta", who), _number(gamma, "gamma", who)
+        for name, v, given in (("alpha", self.alpha, alpha), ("beta", self.beta, beta)):
+            if not (0.0 <= v < float('inf')):
+                raise ValueError(f"dct_amd {who}: {name} must be finite and >= 0, got {given!r}")
+        # (the kernels take the three as fp32: what is 0 or infinite there is refused here)
+        a32, b32, g32 = (float(torch.tensor(v, dtype=torch.float32)) for v in (self.alpha, self.beta, self.gamma))
+        if a32 + b32 == 0.0 or a32 == float('inf') or b32 == float('inf'):
+            raise ValueError(f"dct_amd {who}: alpha + beta must be > 0 and finite in fp32, got {alpha!r}, {beta!r}")
+        if not (0.0 < self.gamma < float('inf')) or not (0.0 < g32 < float('inf')):
+            raise ValueError(f"dct_amd {who}: gamma must be finite and > 0, got {gamma!r}")
+        self.classes = _class_list(classes, who)
+        self.smooth = _number(smooth, "smooth", who)
+        if not (0.0 <= self.smooth < float('inf')):
+            raise ValueError(f"dct_amd {who}: smooth must be finite and >= 0, got {smooth!r}")
+        self.per_image = bool(per_image)
+        self.ignore_index = ignore_index
+        self.last_tversky = None
+
+    def launch_args(self, C):
+        """The keyword arguments of hip_ops.ce_tversky_* for logits of ``C`` classes (checks ``classes`` against C)."""
+        return dict(class_mask=_class_mask(self.classes, C, type(self).__name__), smooth=self.smooth, alpha=self.alpha, beta=self.beta,
+                    gamma=self.gamma, per_image=self.per_image, ce_coef=self.ce_coef, tversky_coef=self.tversky_coef)
+
+    def forward(self, outputs, targets):
+        assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
+        if not outputs.is_cuda:
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        rule = self.launch_args(outputs.shape[1])
+        w = self.device_weight(outputs.device, outputs.shape[1])
+        total, self.last_tversky = _CETverskyFn.apply(outputs, targets, w, rule, self.ignore_index)
+        return total
+
+
+class FocalTverskyLoss(CrossEntropyTverskyLoss2d):
+    """Focal Tversky loss alone: ``mean_{g, c in classes} (1 - T_gc)^(1 / gamma)`` (``CrossEntropyTverskyLoss2d`` with the cross-entropy
+    term removed; the defaults are the paper's)."""
+
+    def __init__(self, alpha=0.3, beta=0.7, gamma=4.0 / 3.0, classes=None, smooth=1e-5, per_image=False, ignore_index=255):
+        super().__init__(None, 0.0, 1.0, alpha, beta, gamma, classes, smooth, per_image, ignore_index)
+
+
+class TverskyLoss(CrossEntropyTverskyLoss2d):
+    """Tversky loss alone: ``1 - mean_{g, c in classes} T_gc`` (``CrossEntropyTverskyLoss2d`` with the cross-entropy term removed and
+    ``gamma`` = 1)."""
+
+    def __init__(self, alpha=0.3, beta=0.7, classes=None, smooth=1e-5, per_image=False, ignore_index=255):
+        super().__init__(None, 0.0, 1.0, alpha, beta, 1.0, classes, smooth, per_image, ignore_index)
+
+
 def _spacing2(spacing, who):
     try:
         sy, sx = (float(s) for s in spacing)

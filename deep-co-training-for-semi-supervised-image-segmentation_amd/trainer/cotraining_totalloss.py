@@ -115,9 +115,10 @@ class ExecutionPlan:
 class _StepContext(object):
     """What one issue of the step carries from its forward passes to its optimizers; dropped when the step returns (the join closure
     holds this step's streams, the pass buffers' owners its tapes)."""
-    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice", "pl", "focal", "topk")
+    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice", "pl", "focal", "topk", "tversky")
 
-    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None, pl=None, focal=None, topk=None):
+    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None, pl=None, focal=None, topk=None,
+                 tversky=None):
         self.sched, self.route = sched, route
         # the gradient exchange as far as it is issued from inside the step (between two graphs it is the replay's business)
         self.sync = grad_sync if any(e in ("model", "buckets") for e in route.exchange) else None
@@ -135,6 +136,7 @@ class _StepContext(object):
         self.pl = pl                        # a pseudo-label consistency criterion's launch arguments (PseudoLabel_2D.launch_args), or None: JSD
         self.focal = focal                  # a focal criterion's launch arguments (FocalLoss2d.launch_args), or None
         self.topk = topk                    # a top-k criterion's launch arguments (TopKCrossEntropyLoss2d.launch_args), or None
+        self.tversky = tversky              # a Tversky / focal Tversky / CE + Tversky criterion's launch arguments (CrossEntropyTverskyLoss2d.launch_args), or None
 
     def on(self, streams, i):
         """Model i's stream of ``streams`` as the current one (no-op without streams, or for the joint backward of the generic step)."""
@@ -301,11 +303,13 @@ class CoTrainer(Trainer):
         gpu = self.device.type == 'cuda'
         fused_criteria = False
         if gpu:
-            from ..loss.loss import (CrossEntropyDiceLoss2d, CrossEntropyLoss2d, CrossPseudoSupervision_2D, DiceLoss,
-                                     EnsemblePseudoLabel_2D, FocalLoss2d, JSD_2D, PseudoLabel_2D, TopKCrossEntropyLoss2d)
+            from ..loss.loss import (CrossEntropyDiceLoss2d, CrossEntropyLoss2d, CrossEntropyTverskyLoss2d, CrossPseudoSupervision_2D, DiceLoss,
+                                     EnsemblePseudoLabel_2D, FocalLoss2d, FocalTverskyLoss, JSD_2D, PseudoLabel_2D, TopKCrossEntropyLoss2d,
+                                     TverskyLoss)
             sup = self.criterions['sup']
-            # (class weights, focal, top-k, Dice and CE + Dice ride the fused kernels; the sum and the per-pixel map go through the module: the generic step)
-            fused_sup = (type(sup) in (CrossEntropyLoss2d, FocalLoss2d) and sup.reduction == 'mean') or type(sup) in (CrossEntropyDiceLoss2d, DiceLoss, TopKCrossEntropyLoss2d)
+            # (class weights, focal, top-k, Dice, CE + Dice and the Tversky family ride the fused kernels; the sum and the per-pixel map go through the module: the generic step)
+            fused_sup = (type(sup) in (CrossEntropyLoss2d, FocalLoss2d) and sup.reduction == 'mean') or type(sup) in (
+                CrossEntropyDiceLoss2d, DiceLoss, TopKCrossEntropyLoss2d, CrossEntropyTverskyLoss2d, TverskyLoss, FocalTverskyLoss)
             cons = self.criterions['jsd']
             # (the pseudo-label criteria ride dct_pl_logits_step; cross pseudo supervision of a single network goes through the module, which refuses it)
             fused_cons = type(cons) is JSD_2D or (type(cons) in (PseudoLabel_2D, CrossPseudoSupervision_2D, EnsemblePseudoLabel_2D)
@@ -457,6 +461,7 @@ class CoTrainer(Trainer):
 
     def _ce_step(self, ctx, lp, t, dl):
         """The supervised criterion's value + logit gradient: Dice / CE + Dice (dct_ce_dice_step over the images of ``lp``: [B, H, W, C]),
+        Tversky / focal Tversky / CE + Tversky (dct_ce_tversky_step likewise; the criterion's ``last_tversky`` is set to this launch's table),
         focal (dct_focal_step, whatever its gamma), top-k (dct_topk_ce_step; the criterion's ``last_topk`` is set), class-weighted when it carries weights (dct_ce_weighted_step), else dct_ce_step."""
         from .. import hip_ops as K
         if ctx.focal is not None:
@@ -465,6 +470,10 @@ class CoTrainer(Trainer):
             out2, counts4, _ = K.topk_ce_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore, **ctx.topk)
             self.criterions['sup'].last_topk = (out2, counts4)
             return out2
+        if ctx.tversky is not None:
+            out4, tversky_gc, _ = K.ce_tversky_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore, **ctx.tversky)
+            self.criterions['sup'].last_tversky = tversky_gc
+            return out4
         if ctx.ce_dice is not None:
             return K.ce_dice_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore, **ctx.ce_dice)[0]
         if ctx.ce_weight is not None:
@@ -635,15 +644,15 @@ class CoTrainer(Trainer):
         ``lam_dev`` (float32[2] device tensor holding lambda_cot, lambda_adv): the loss weights are then read on the
         device, as a captured graph needs."""
         nets = [s.torchnet for s in self.segmentators]
-        from ..loss.loss import FocalLoss2d, TopKCrossEntropyLoss2d
+        from ..loss.loss import CrossEntropyTverskyLoss2d, FocalLoss2d, TopKCrossEntropyLoss2d
         sup, cons = self.criterions['sup'], self.criterions['jsd']
         rule = sup.launch_args(self.C) if hasattr(sup, "launch_args") else None
-        focal, topk = type(sup) is FocalLoss2d, type(sup) is TopKCrossEntropyLoss2d
+        focal, topk, tversky = type(sup) is FocalLoss2d, type(sup) is TopKCrossEntropyLoss2d, isinstance(sup, CrossEntropyTverskyLoss2d)
         ctx = _StepContext(self._sched, route, self.grad_sync, (float(self.cot_scheduler.value), float(self.adv_scheduler.value)),
                            lam_dev, sup.ignore_index, sup.device_weight(self.device, self.C),
-                           None if focal or topk else rule,
+                           None if focal or topk or tversky else rule,
                            cons.launch_args() if hasattr(cons, "launch_args") else None,
-                           rule if focal else None, rule if topk else None)
+                           rule if focal else None, rule if topk else None, tversky=rule if tversky else None)
         streams = self._streams() if route.model_streams else None
         if route.kind in ("wide", "wide_grouped"):
             return self._run_step_wide(ctx, lab, unl, train_adv, adv_choice, nets)

@@ -93,8 +93,8 @@ class StepGraphCache(object):
                         opt._guard.data_ptr() if getattr(opt, "_guard", None) is not None and opt.guarded else 0,
                         getattr(opt, "max_grad_norm", None) is not None, bool(getattr(opt, "skip_nonfinite", False))))
         # the supervised criterion's launch arguments: another criterion (ignore_index, weight buffer; for CE + Dice its module type, the
-        # two coefficients, mask, smooth and per_image) is another capture; the weights themselves are read on the device, so changing
-        # them in place is not
+        # two coefficients, mask, smooth and per_image; for the Tversky family also alpha, beta and gamma) is another capture; the weights
+        # themselves are read on the device, so changing them in place is not
         sup = tr.criterions['sup']
         w = sup.device_weight(tr.device, tr.C)
         rule = sup.launch_args(tr.C) if hasattr(sup, "launch_args") else None

@@ -412,6 +412,49 @@ int dct_ce_dice_step(const float* logits, const int64_t* targets, int B, int64_t
                      const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, float* out4,
                      float* dice_gc, float* sums, const float* gscale, float gmul, float* dlogits, int accumulate, void* workspace,
                      size_t workspace_bytes, dct_stream stream);
+/* Tversky loss (Salehi et al. 2017) and focal Tversky loss (Abraham & Khan 2019), alone or beside the class-weighted cross entropy, as one
+ * supervised criterion on logits.  logits, targets, weight, class_mask, K, smooth, per_image, G, the counted pixels (t_i != ignore_index
+ * && 0 <= t_i < C), the sums I = sum p_c y_c, S = sum p_c, Y = sum y_c per group g and class c, ce and sum w_i are those of dct_ce_dice_*.
+ * alpha >= 0 weighs the false positives S - I, beta >= 0 the false negatives Y - I (alpha + beta > 0); gamma > 0 is the focal parameter,
+ * the exponent is 1 / gamma as in the paper; ce_coef, tversky_coef: host floats.
+ *   Den_gc = (1 - alpha - beta) I + alpha S + beta Y + smooth,   N_gc = I + smooth,   T_gc = N / Den
+ *            a denominator of 0: T_gc = 1, and the class contributes neither to the value nor to the gradient (Dice's empty denominator)
+ *   u_gc   = max(1 - T, 0)
+ *   term   = u when gamma == 1 (no power function is evaluated), else u^(1 / gamma); u == 0: term = 0 and no gradient
+ *   tversky = (1 / (G K)) sum_g sum_{c in mask} term_gc
+ *   total  = ce_coef ce + tversky_coef tversky; a coefficient that is exactly 0 removes its term from the total and from the gradient (a
+ *            NaN ce then does not reach total).
+ *   alpha = beta = 0.5 is the soft Dice loss with twice the smooth; alpha = beta = 1 is the Jaccard loss.
+ * Gradient, with g = gscale[0] * gmul (gscale nullable = 1) and m_c = 1 for the classes of the mask, else 0:
+ *   dlogits[i][c] (=|+=) g (ce_coef (w_i / sum w)(p_c - y_c) + tversky_coef p_c (q_c - sum_k p_k q_k)),   q_c = qb_gc - y_c qa_gc
+ *   f_gc  = (m_c / (G K)) (1 / gamma) u^(1 / gamma - 1)      (gamma == 1: m_c / (G K);  u == 0 or Den == 0: 0)
+ *   qa_gc = f (1 - (1 - alpha - beta) T) / Den,              qb_gc = f alpha T / Den
+ * Arithmetic: the host forms c0 = 1 - alpha - beta and e = 1 / gamma once, in double from the fp32 arguments, and rounds each to fp32
+ *   once; the kernels take e - 1 from the fp32 e.  Den = ((c0 I + alpha S) + beta Y) + smooth with one rounding per operation (no fused
+ *   multiply-add), u^x = exp2f(x log2f(u)), f = ((m / (G K)) e) u^(e - 1), qa = (f (1 - c0 T)) / Den, qb = ((f alpha) T) / Den.
+ * dct_ce_tversky_fwd writes out4 = {total, ce, sum w_i, tversky}, tversky_gc [G][C] = T_gc, the index itself, of every class, masked in or
+ *   not (for logging), and sums [G][C][3] = {I, S, Y}, which the backward call reads.  dct_ce_tversky_bwd reads out4 (its sum w_i) and sums
+ *   of the forward call.  dct_ce_tversky_step: fwd + bwd in two launches; out4, tversky_gc, sums and dlogits are bit for bit those of
+ *   dct_ce_tversky_fwd followed by dct_ce_tversky_bwd.  The forward partial sums are dct_ce_dice_*'s kernel and fold order: no float
+ *   atomics, bit-identical from run to run, and under per_image a permutation of the images permutes the rows of tversky_gc.
+ * Workspace: dct_ce_tversky_workspace_bytes(B, C, per_image) (= dct_ce_dice_workspace_bytes); no clearing needed.
+ * DCT_ERR_BAD_ARG: everything dct_ce_dice_* refuses with it (tversky_gc in place of dice_gc); alpha or beta negative or not finite;
+ *   alpha + beta == 0 (the index is constantly 1); gamma not finite or <= 0.  DCT_ERR_UNSUPPORTED, DCT_ERR_WORKSPACE: as dct_ce_dice_*.
+ * Out of scope: generalized Dice (the weight of an absent class needs a rule of its own), the squared-denominator form, probabilities as
+ *   input, Tversky as a consistency term. */
+size_t dct_ce_tversky_workspace_bytes(int B, int C, int per_image);
+int dct_ce_tversky_fwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C, int ignore_index,
+                       const float* weight /*nullable*/, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
+                       float ce_coef, float tversky_coef, float* out4, float* tversky_gc, float* sums, void* workspace,
+                       size_t workspace_bytes, dct_stream stream);
+int dct_ce_tversky_bwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C, int ignore_index,
+                       const float* weight, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
+                       float ce_coef, float tversky_coef, const float* out4, const float* sums, const float* gscale, float gmul,
+                       float* dlogits, int accumulate, dct_stream stream);
+int dct_ce_tversky_step(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C, int ignore_index,
+                        const float* weight, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
+                        float ce_coef, float tversky_coef, float* out4, float* tversky_gc, float* sums, const float* gscale, float gmul,
+                        float* dlogits, int accumulate, void* workspace, size_t workspace_bytes, dct_stream stream);
 /* Boundary loss (Kervadec et al., "Boundary loss for highly unbalanced segmentation"): the softmax weighted by the signed Euclidean
  * distance to the ground-truth contour, here on the device from the targets to the gradient.
  * Targets t [B][H][W] int64; classes 0..C-1, 2 <= C <= 8; spacing (sy, sx), both > 0 and finite; G_c = {t == c}.  A target outside [0, C)

@@ -12,6 +12,7 @@ t bench_dice_loss    python tools/bench_dice_loss.py
 t bench_boundary_loss python tools/bench_boundary_loss.py
 t bench_focal_loss   python tools/bench_focal_loss.py
 t bench_topk_ce      python tools/bench_topk_ce.py
+t bench_tversky      python tools/bench_tversky.py
 t bench_pseudo_label python tools/bench_pseudo_label.py
 t bench_pointwise    python tools/bench_pointwise.py
 t debug_conv_case    python tools/debug_conv_case.py
