@@ -1293,6 +1293,212 @@ __global__ __launch_bounds__(256) void pl_finalize_kernel(const float* partial, 
   if (threadIdx.x == 0) { out[0] = a / denom_a; out[1] = b / denom_b; }
 }
 
+// ---- soft pseudo-label consistency: sharpened teachers in place of the argmax (the rule: include/dct.h, dct_spl_*) ------------------
+// Sharpen(q, T) of one raw teacher vector q with first maximum k (bv = q[k]) and r = 1 / T: u[c] = exp2f(r (log2f(q[c]) - log2f(q[k]))),
+// 0 where q[c] == 0 and 1 exactly at k; t = u / (u[0] + ... + u[C-1]), added in class order.  Scale-free, so the ensemble hands in its
+// unscaled sums.  k is a compile-time-unrolled compare, never an index: nothing here may be addressed at run time (scratch).
+template <int C>
+__device__ __forceinline__ void spl_sharpen(const float (&q)[C], int k, float bv, float r, float (&t)[C]) {
+#pragma clang fp contract(off)    // the argument of exp2f is the rounded product of the rounded difference, as the rule states it
+  const float lk = log2f(bv);
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float u = 1.f;
+    if (c != k) u = q[c] == 0.f ? 0.f : exp2f(r * (log2f(q[c]) - lk));
+    t[c] = u;
+    sum = sum + u;
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) t[c] = t[c] / sum;
+}
+// The sharpened teachers of one pixel, as constants: k and the mask are pl_teachers' (the same compares on the same fp32 values, the
+// mask on the raw confidence before sharpening).  Out: t[j] = m_j * Sharpen(p_j) for cross (0 for a masked view and for j >= S),
+// t[0] = m * Sharpen(sum) for ensemble.  Returns the number of kept teachers.  A masked teacher is never sharpened.
+// The S teachers are HELD (SMAX C floats) and not recomputed per student: recomputing costs S times the 2 C transcendentals of every
+// teacher, holding costs 64 registers at SMAX = 8, C = 8, where the file of a 256-thread block (512 per lane) has them.
+template <int C, int SMAX>
+__device__ __forceinline__ int spl_teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, float r, float (&t)[SMAX][C]) {
+#pragma clang fp contract(off)    // as pl_teachers: the sums and q are formed from the ROUNDED probabilities
+  int kept = 0;
+#pragma unroll
+  for (int s = 0; s < SMAX; ++s) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) t[s][c] = 0.f;
+  }
+  if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float bv = p[s][0];
+        int best = 0;
+#pragma unroll
+        for (int c = 1; c < C; ++c) if (p[s][c] > bv) { bv = p[s][c]; best = c; }
+        if (bv >= tau) {
+          ++kept;
+          spl_sharpen<C>(p[s], best, bv, r, t[s]);
+        }
+      }
+    }
+  } else {
+    float sum[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) sum[c] = p[0][c];
+#pragma unroll
+    for (int s = 1; s < SMAX; ++s) {
+      if (s < S) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) sum[c] = sum[c] + p[s][c];
+      }
+    }
+    float bv = sum[0];
+    int best = 0;
+#pragma unroll
+    for (int c = 1; c < C; ++c) if (sum[c] > bv) { bv = sum[c]; best = c; }   // on the unscaled sums: scaling cannot create a tie
+    const float q = bv * invS;
+    if (q >= tau) {
+      kept = 1;
+      spl_sharpen<C>(sum, best, bv, r, t[0]);
+    }
+  }
+  return kept;
+}
+// n[c] of student i: cross: the other views' kept teachers added in ascending j (formed as that sum, never as a total minus the
+// student's own share: (t_0 + t_1) - t_0 is not t_1); ensemble: the one teacher.  i is a constant of the caller's unrolled loop.
+template <int C, int SMAX>
+__device__ __forceinline__ void spl_terms(const float (&t)[SMAX][C], int S, int teacher, int i, float (&n)[C]) {
+#pragma clang fp contract(off)
+  if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) n[c] = 0.f;
+#pragma unroll
+    for (int j = 0; j < SMAX; ++j) {
+      if (j < S && j != i) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) n[c] = n[c] + t[j][c];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) n[c] = t[0][c];
+  }
+}
+// pl_student over real-valued n: returns sum_c n[c] * -log(p[c] + eps) and d[c] = -(wgt n[c]) / (p[c] + eps).  No term: no log, d[c] = 0 exactly.
+template <int C>
+__device__ __forceinline__ float spl_student(const float (&p)[C], const float (&n)[C], float eps, float wgt, float (&d)[C]) {
+  float a = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    d[c] = 0.f;
+    if (n[c] != 0.f) {
+      const float pe = p[c] + eps;
+      a -= n[c] * logf(pe);
+      d[c] = -(wgt * n[c]) / pe;
+    }
+  }
+  return a;
+}
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void spl_map_fwd_kernel(PtrPack pk, int S, int teacher, float tau, float r, float eps, float invS, float wgt, float kden,
+                                                           float* map, float* keptmap, long long P) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float p[SMAX][C], t[SMAX][C];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
+    }
+    const int kept = spl_teachers<C, SMAX>(p, S, teacher, tau, invS, r, t);
+    float a = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float n[C], d[C];
+        spl_terms<C, SMAX>(t, S, teacher, s, n);
+        a += spl_student<C>(p[s], n, eps, wgt, d);
+      }
+    }
+    map[pix] = wgt * a;
+    if (keptmap) keptmap[pix] = (float)kept / kden;
+  }
+}
+// dprobs_s = dmap[pix] * d map / d p_s, the teachers recomputed from the probabilities
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void spl_map_bwd_kernel(PtrPack pk, int S, int teacher, float tau, float r, float eps, float invS, float wgt,
+                                                           const float* dmap, long long P) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float p[SMAX][C], t[SMAX][C];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
+    }
+    const float gp = dmap[pix];
+    spl_teachers<C, SMAX>(p, S, teacher, tau, invS, r, t);
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float n[C], d[C];
+        spl_terms<C, SMAX>(t, S, teacher, s, n);
+        spl_student<C>(p[s], n, eps, wgt, d);
+#pragma unroll
+        for (int c = 0; c < C; ++c) d[c] = d[c] != 0.f ? gp * d[c] : 0.f;     // a masked entry is 0 whatever dmap holds
+        store_px<C>(pk.out[s], pix, d, false);
+      }
+    }
+  }
+}
+// pl_step_kernel with the sharpened teachers: one pixel per trip, every load of the pixel issued before its first store; block partials
+// of (map value, kept teachers) for pl_finalize_kernel.
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void spl_step_kernel(PtrPack pk, PtrPack probs, int S, int teacher, float tau, float r, float eps, float invS, float wgt,
+                                                        long long P, const float* gscale, float gmul, int acc, int want_grad, float* partial) {
+  const float g = (gscale ? gscale[0] : 1.f) * gmul / (float)P;
+  float sum = 0.f, keptsum = 0.f;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float x[SMAX][C], old[SMAX][C];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        load_px<C>(pk.in[s], pix, x[s]);
+        if (want_grad && acc) load_px<C>(pk.out[s], pix, old[s]);
+      }
+    }
+    float p[SMAX][C], t[SMAX][C];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        softmax_px<C>(x[s], p[s]);
+        if (probs.out[s]) store_px<C>(probs.out[s], pix, p[s], false);
+      }
+    }
+    keptsum += (float)spl_teachers<C, SMAX>(p, S, teacher, tau, invS, r, t);
+    float a = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float n[C], d[C];
+        spl_terms<C, SMAX>(t, S, teacher, s, n);
+        a += spl_student<C>(p[s], n, eps, wgt, d);
+        if (want_grad) {
+          float dot = 0.f;
+#pragma unroll
+          for (int c = 0; c < C; ++c) dot += d[c] * p[s][c];
+          float o[C];
+#pragma unroll
+          for (int c = 0; c < C; ++c) o[c] = g * p[s][c] * (d[c] - dot);
+          if (acc) {
+#pragma clang fp contract(off)    // store_px's accumulate: round, then add
+#pragma unroll
+            for (int c = 0; c < C; ++c) o[c] = o[c] + old[s][c];
+          }
+          store_px<C>(pk.out[s], pix, o, false);
+        }
+      }
+    }
+    sum += wgt * a;
+  }
+  block_partial2(sum, keptsum, partial);
+}
+
 // ---- KL(y || p) -----------------------------------------------------------------------------------
 template <int C, bool FROM_LOGITS>
 __global__ __launch_bounds__(256) void kl_fwd_kernel(const float* pin, const float* yin, long long P, float eps, float* map, float* partial) {
@@ -2062,6 +2268,60 @@ extern "C" int dct_pl_logits_step(const float* const* logits, int S, int teacher
   if (S <= 2) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, 2>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
   else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
   else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * r.kden);
+  return dct_check_launch();
+}
+
+// ---- soft pseudo-label consistency --------------------------------------------------------------------
+namespace {
+// pl_rule plus the temperature: finite and > 0, and so is r = 1.f / T formed in fp32 (a subnormal T gives inf)
+bool spl_rule(int S, int teacher, float tau, float temperature, float eps, PlRule& r, float& rT) {
+  if (!pl_rule(S, teacher, tau, eps, r)) return false;
+  if (!(temperature > 0.f) || !__builtin_isfinite(temperature)) return false;      // (a NaN fails the first)
+  rT = 1.f / temperature;
+  return rT > 0.f && __builtin_isfinite(rT);
+}
+}  // namespace
+
+extern "C" int dct_spl_map_fwd(const float* const* probs, int S, int teacher, float tau, float temperature, float eps, float* map, float* kept,
+                               int64_t pixels, int C_, dct_stream stream) {
+  PtrPack pk;
+  PlRule r;
+  float rT;
+  if (!spl_rule(S, teacher, tau, temperature, eps, r, rT) || !fill_pack(pk, probs, nullptr, S) || !map || pixels < 1) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = wide_grid(pixels);
+  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_map_fwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, rT, eps, r.invS, r.wgt, r.kden, map, kept, (long long)pixels)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_map_fwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, rT, eps, r.invS, r.wgt, r.kden, map, kept, (long long)pixels)); }
+  return dct_check_launch();
+}
+extern "C" int dct_spl_map_bwd(const float* const* probs, int S, int teacher, float tau, float temperature, float eps, const float* dmap,
+                               float* const* dprobs, int64_t pixels, int C_, dct_stream stream) {
+  PtrPack pk;
+  PlRule r;
+  float rT;
+  if (!spl_rule(S, teacher, tau, temperature, eps, r, rT) || !dprobs || !fill_pack(pk, probs, dprobs, S) || !dmap || pixels < 1) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = wide_grid(pixels);
+  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_map_bwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, rT, eps, r.invS, r.wgt, dmap, (long long)pixels)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_map_bwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, rT, eps, r.invS, r.wgt, dmap, (long long)pixels)); }
+  return dct_check_launch();
+}
+extern "C" int dct_spl_logits_step(const float* const* logits, int S, int teacher, float tau, float temperature, float eps, int64_t pixels, int C_,
+                                   float* out2, float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
+                                   void* workspace, size_t workspace_bytes, dct_stream stream) {
+  PtrPack pk, pp;
+  PlRule r;
+  float rT;
+  if (!spl_rule(S, teacher, tau, temperature, eps, r, rT) || !fill_pack(pk, logits, dlogits, S) || !out2 || pixels < 1) return DCT_ERR_BAD_ARG;
+  for (int s = 0; s < MAXS; ++s) { pp.in[s] = nullptr; pp.out[s] = (probs && s < S) ? probs[s] : nullptr; }
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);
+  const int want = dlogits ? 1 : 0;
+  if (S <= 2) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, 2>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
   DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * r.kden);
   return dct_check_launch();
 }

@@ -744,3 +744,93 @@ class EnsemblePseudoLabel_2D(PseudoLabel_2D):
 
     def __init__(self, threshold=0.0, eps=1e-10):
         super().__init__('ensemble', threshold, eps)
+
+
+class _SPLMapFn(torch.autograd.Function):
+    """The soft pseudo-label consistency map on dct_spl_map_*; ``rule``: ``SoftPseudoLabel_2D.launch_args()``.  As ``_PLMapFn``: nothing
+    but the inputs is saved, the backward recomputes the sharpened teachers."""
+
+    @staticmethod
+    def forward(ctx, rule, *probs):
+        pps = [_pc(p) for p in probs]
+        ctx.save_for_backward(*pps)
+        ctx.rule = rule
+        out, kept = K.spl_map_fwd(pps, pps[0].shape[3], **rule)
+        kept = kept.view(pps[0].shape[:3])
+        ctx.mark_non_differentiable(kept)
+        return out.view(pps[0].shape[:3]), kept
+
+    @staticmethod
+    def backward(ctx, g, _):
+        pps = list(ctx.saved_tensors)
+        dps = K.spl_map_bwd(pps, g.to(torch.float32).contiguous().view(-1), pps[0].shape[3], **ctx.rule)
+        return (None,) + tuple(_nchw(d) for d in dps)
+
+
+class SoftPseudoLabel_2D(nn.Module):
+    """Soft pseudo-label consistency of S views (the rule: include/dct.h, dct_spl_*), with ``PseudoLabel_2D``'s call shape: a list of
+    [B,C,H,W] probabilities in, a [B,H,W] map out, whose mean over ALL pixels is the loss.  The teacher is the other views' prediction
+    (``teacher='cross'``, 2 or more views) or the summed prediction (``teacher='ensemble'``), sharpened with ``temperature`` T as
+    MixMatch's Sharpen(q, T) = q^(1/T) / sum q^(1/T): T = 1 is plain cross entropy against the teacher's probabilities, T -> 0 the hard
+    pseudo-label.  ``threshold`` masks a teacher by its raw confidence, before sharpening.  Teachers are constants.  After a call
+    ``last_kept`` is a device scalar, the kept fraction of the teacher terms (nothing synchronises).
+    Not a ``PseudoLabel_2D``: the trainer tells the criteria apart by exact type."""
+
+    def __init__(self, teacher='cross', temperature=0.5, threshold=0.0, eps=1e-10):
+        super().__init__()
+        name = type(self).__name__
+        if teacher not in K.PL_TEACHERS:
+            raise ValueError(f"dct_amd {name}: teacher must be 'cross' or 'ensemble', got {teacher!r}")
+        self.teacher = teacher
+        try:
+            self.temperature, self.threshold, self.eps = float(temperature), float(threshold), float(eps)
+        except (TypeError, ValueError):
+            raise ValueError(f"dct_amd {name}: temperature, threshold and eps must be numbers, got {temperature!r}, {threshold!r}, {eps!r}")
+        # (the kernels receive T as fp32 and form r = 1.f / T there: both must be finite and > 0)
+        t32 = torch.tensor(self.temperature, dtype=torch.float32)
+        r32 = 1.0 / t32
+        if not (0.0 < float(t32) < float('inf')) or not (0.0 < float(r32) < float('inf')):
+            raise ValueError(f"dct_amd {name}: temperature and 1 / temperature must be finite and > 0 in fp32, got {temperature}")
+        if not (0.0 <= self.threshold <= float('inf')):
+            raise ValueError(f"dct_amd {name}: threshold must be >= 0, got {threshold}")
+        if not (0.0 < self.eps < float('inf')) or float(torch.tensor(self.eps, dtype=torch.float32)) == 0.0:
+            raise ValueError(f"dct_amd {name}: eps must be finite and > 0 in fp32, got {eps}")
+        self.last_kept = None
+
+    def launch_args(self):
+        """The keyword arguments of hip_ops.spl_* (and what a captured step is valid for)."""
+        return dict(teacher=K.PL_TEACHERS[self.teacher], tau=self.threshold, temperature=self.temperature, eps=self.eps)
+
+    def min_views(self):
+        return 2 if self.teacher == 'cross' else 1
+
+    def forward(self, input: List[torch.Tensor]):
+        input = list(input)
+        name = type(self).__name__
+        if len(input) < self.min_views():
+            raise ValueError(f"dct_amd {name}: teacher='{self.teacher}' needs at least {self.min_views()} views, got {len(input)}")
+        if len(input) > MAX_VIEWS:
+            raise ValueError(f"dct_amd {name} handles up to {MAX_VIEWS} views per call, got {len(input)}")
+        if not all(p.is_cuda for p in input):
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        if DEBUG_ASSERTS:
+            for inprob in input:
+                assert _simplex(inprob, 1)
+        out, kept = _SPLMapFn.apply(self.launch_args(), *input)
+        self.last_kept = kept.mean()
+        return out
+
+
+class SoftCrossPseudoSupervision_2D(SoftPseudoLabel_2D):
+    """Soft cross pseudo supervision: ``SoftPseudoLabel_2D(teacher='cross')``."""
+
+    def __init__(self, temperature=0.5, threshold=0.0, eps=1e-10):
+        super().__init__('cross', temperature, threshold, eps)
+
+
+class SoftEnsemblePseudoLabel_2D(SoftPseudoLabel_2D):
+    """The sharpened mean prediction as everyone's target (one network: self-training on its own sharpened prediction):
+    ``SoftPseudoLabel_2D(teacher='ensemble')``."""
+
+    def __init__(self, temperature=0.5, threshold=0.0, eps=1e-10):
+        super().__init__('ensemble', temperature, threshold, eps)

@@ -553,6 +553,42 @@ int dct_pl_map_bwd(const float* const* probs, int S, int teacher, float tau, flo
 int dct_pl_logits_step(const float* const* logits, int S, int teacher, float tau, float eps, int64_t pixels, int C, float* out2,
                        float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
                        void* workspace, size_t workspace_bytes, dct_stream stream);
+/* ---- soft pseudo-label consistency: every view is trained on the SHARPENED soft predictions of the others (MixMatch's Sharpen(q, T)) ----
+ * Per pixel: S views (1 <= S <= 8) with fp32 probabilities p_s[0..C), C in 2..8, a teacher mode (DCT_PL_CROSS, S >= 2, or DCT_PL_ENSEMBLE,
+ * S >= 1), a confidence threshold tau >= 0, a temperature T > 0, finite, with r = 1.f / T formed in fp32, and eps > 0.
+ * Teachers are constants: no gradient flows through a sharpened target, a confidence or a mask.  Everything below is fp32.
+ *
+ * The raw teacher vector q, its first maximum k and the mask m are dct_pl_*'s, bit for bit:
+ *   cross     q_j = p_j,  k_j = first maximum of p_j,  m_j = (p_j[k_j] >= tau)
+ *   ensemble  q = ((p_0 + p_1) + ...), added in view order,  k = first maximum of the unscaled sums,  m = (q[k] * (1.f / (float)S) >= tau)
+ * The mask is taken on the raw confidence, before sharpening.
+ * Sharpening is scale-free, so it is taken from q as it stands (for the ensemble: the unscaled sums):
+ *   u[c] = exp2f(r * (log2f(q[c]) - log2f(q[k]))),   u[c] = 0 where q[c] == 0,   u[k] = 1 exactly,
+ *   t[c] = u[c] / (u[0] + ... + u[C-1]), added in class order.
+ * Student i, class c:   cross     n_ic = sum over j != i, in ascending j, of m_j * t_j[c]
+ *                       ensemble  n_ic = m * t[c]
+ *   n_ic is formed as that sum, never as a total minus the student's own share: with S = 2, (t_0 + t_1) - t_0 is not t_1, and the error
+ *   would be divided by p + eps afterwards.
+ * Value and gradient, in dct_pl_*'s form with real-valued n:
+ *   map = w * sum_i sum_c n_ic * -log(p_i[c] + eps),   d map / d p_i[c] = -(w * n_ic) / (p_i[c] + eps),   w = 1 / (S (S - 1)) resp. 1 / S;
+ *   where n_ic == 0 nothing is evaluated and the entry is 0 exactly.
+ * From logits: p_s = softmax(x_s) with dct_softmax_fwd's bits; d / d x_i[c] = g * p_i[c] * (d_i[c] - sum_c' d_i[c'] p_i[c']), g = gscale[0] * gmul / P
+ * (gscale NULL: 1); accumulate rounds, then adds.
+ * The mean is over all P pixels, never over the kept ones.  kept is dct_pl_*'s kept fraction and kept map, unchanged in meaning.
+ * Three consequences:
+ *   - T = 1 with the cross teacher is the mean cross entropy of every view against every other view's probabilities (t_j = p_j / sum_c p_j[c]);
+ *   - where every teacher's second-largest entry is at most half its largest and T = 2^-10 (r = 1024), every u[c != k] is exp2f of at most
+ *     about -1024, which is 0 in fp32: t is exactly one-hot and the rule is the hard pseudo-label's (dct_pl_*);
+ *   - with everything masked, the value and every gradient are exactly 0.
+ * Status codes are dct_pl_*'s, plus DCT_ERR_BAD_ARG for a temperature that is not finite and > 0, or whose 1.f / T is not finite and > 0 in fp32. */
+int dct_spl_map_fwd(const float* const* probs, int S, int teacher, float tau, float temperature, float eps, float* map, float* kept,
+                    int64_t pixels, int C, dct_stream stream);
+int dct_spl_map_bwd(const float* const* probs, int S, int teacher, float tau, float temperature, float eps, const float* dmap,
+                    float* const* dprobs, int64_t pixels, int C, dct_stream stream);
+/* dct_pl_logits_step's contract (workspace, out2, probs, dlogits, two launches) with the sharpened teachers */
+int dct_spl_logits_step(const float* const* logits, int S, int teacher, float tau, float temperature, float eps, int64_t pixels, int C,
+                        float* out2, float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
+                        void* workspace, size_t workspace_bytes, dct_stream stream);
 /* out[0] = mean_pix sum_c y*(log(y+eps)-log(p+eps)), p = softmax(p_logits), y = softmax(y_logits) */
 int dct_kl_logits_fwd(const float* p_logits, const float* y_logits, int64_t pixels, int C, float eps,
                       float* out1, void* workspace, size_t workspace_bytes, dct_stream stream);

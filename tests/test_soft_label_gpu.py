@@ -1,0 +1,344 @@
+"""The soft pseudo-label consistency kernels (dct_spl_map_fwd / dct_spl_map_bwd / dct_spl_logits_step) against tests/soft_label_ref.py.
+
+The raw teachers (first maximum, confidence, mask) are pseudo_label_ref's, derived on the CPU in fp32, and must match bit for bit: the
+kept map is compared with ``torch.equal``, and where the reference has no teacher term the kernel's loss and gradient must be 0
+exactly.  Given those, the sharpened targets, values and gradients are compared with float64 within the bounds soft_label_ref derives
+from the kernels' arithmetic.
+
+Shapes, inputs and thresholds are tests/test_pseudo_label_gpu.py's (rebuilt here): P in {1, 255, 257} for every S in {2, 3, 5, 8} and
+C in {2, 4, 8}, for the step kernel 262,144 and 262,145 pixels as well; random logits x 3, the underflow sentinels, the tie pixels
+including the collapsing pair; thresholds 0, one confidence from the data that keeps between 20 % and 80 % of the terms (asserted on
+the reference; not at P = 1), and 2.  Temperatures 0.5, 1 and 2, and the hard limit T = 2^-10 against the dct_pl_* kernels."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import pseudo_label_ref as PR
+import soft_label_ref as R
+from soft_label_ref import SUM_DEPTH, TINY, U
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+EPS = float(np.float32(1e-10))       # eps as the kernels receive it
+MARGIN_UFL = 120.0                   # the other probabilities underflow to 0 in fp32 (tests/test_loss_kernels_scale_gpu.py)
+TAU_NONE = 2.0
+SMALL = [(P, S, C) for P in (1, 255, 257) for S in (2, 3, 5, 8) for C in (2, 4, 8)]
+LARGE = [(262144, 2, 4), (262145, 2, 4), (262145, 3, 8), (262144, 5, 2), (262145, 8, 2)]
+TEACHERS = ["cross", "ensemble"]
+TEMPS = [0.5, 1.0, 2.0]
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    from dct_amd import hip_ops
+    return hip_ops
+
+
+def _nan(*shape):
+    return torch.full(shape, float("nan"), dtype=torch.float32, device=DEV)
+
+
+def _special(P):
+    """(sentinel pixels, tie pixels): the corners of the blocks and of the 1024-block grid stride."""
+    s1 = min(max(1, (P + 255) // 256), 1024) * 256
+    sen = sorted({i for i in (0, 255, 256, s1 - 1, s1, P - 1) if 0 <= i < P})
+    tie = sorted({i for i in (1, 2, 3, 254, s1 + 1, s1 + 2, P - 2) if 0 <= i < P} - set(sen))
+    return sen, tie
+
+
+@functools.lru_cache(maxsize=2)
+def _logits(P, S, C):
+    """test_pseudo_label_gpu._logits: S logit maps [P, C], fp32: random x 3; sentinels: view s is sure (by 120) of class s % C, so every
+    student's probability of a neighbour's class underflows to 0; ties: equal logits everywhere, mirrored pairs in the first two
+    views (their sums tie exactly).  (Shared by the temperatures of a shape: never written to.)"""
+    g = torch.Generator().manual_seed(1000 * P + 10 * S + C)
+    xs = [torch.randn(P, C, generator=g) * 3 for _ in range(S)]
+    sen, tie = _special(P)
+    for s in range(S):
+        xs[s][sen] = 0.0
+        xs[s][sen, s % C] = MARGIN_UFL
+        xs[s][tie] = 0.0
+    for n_, i in enumerate(tie):
+        if n_ % 2:
+            xs[0][i, 0], xs[0][i, 1] = 1.5, -0.5
+            xs[1][i, 0], xs[1][i, 1] = -0.5, 1.5
+    return tuple(xs)
+
+
+def _collapsing_pair(S):
+    inv = np.float32(1.0) / np.float32(S)
+    a = np.float32(1.75)
+    for _ in range(64):
+        b = np.nextafter(a, np.float32(2.0))
+        if np.float32(a * inv) == np.float32(b * inv):
+            return a, b
+        a = b
+    raise AssertionError("no collapsing pair found")
+
+
+def _probs(P, S, C):
+    """test_pseudo_label_gpu._probs: the fp32 softmax of ``_logits`` with hand-built pixels on top -- sentinels exactly one-hot (their
+    zeros are the rule's u = 0 where q == 0), and for S in (3, 5) one pixel whose class sums differ by one ulp but scale to the same
+    fp32: the argmax must be taken before scaling."""
+    ps = [torch.softmax(x, 1).contiguous() for x in _logits(P, S, C)]
+    sen, tie = _special(P)
+    for s in range(S):
+        ps[s][sen] = 0.0
+        ps[s][sen, s % C] = 1.0
+    if S in (3, 5) and tie:
+        a, b = _collapsing_pair(S)
+        i = tie[0]
+        for s in range(S):
+            ps[s][i] = 0.0
+        ps[0][i, :2] = 0.5
+        ps[1][i, :2] = 0.5
+        ps[2][i, 0], ps[2][i, 1] = float(a - np.float32(1.0)), float(b - np.float32(1.0))
+    return ps
+
+
+def _taus(q, P):
+    """0, a confidence out of the data that keeps between 20 % and 80 % of the teacher terms (more than one pixel), 2."""
+    if P == 1:
+        return [0.0, TAU_NONE]
+    flat = np.sort(q.reshape(-1))
+    tau = float(flat[int(0.55 * (flat.size - 1))])
+    frac = float((q >= np.float32(tau)).mean())
+    assert 0.2 <= frac <= 0.8, (tau, frac)
+    return [0.0, tau, TAU_NONE]
+
+
+def _check(got, ref, bound, what):
+    got = got.detach().cpu().double()
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    bad = ~((got - ref).abs() <= bound)
+    if bad.any():
+        i = int(torch.nonzero(bad.reshape(-1))[0])
+        raise AssertionError(f"{what}: {int(bad.sum())}/{bad.numel()} out of bound; first at flat {i}: got {got.reshape(-1)[i].item()!r} "
+                             f"ref {ref.reshape(-1)[i].item()!r} bound {bound.reshape(-1)[i].item()!r}")
+
+
+@pytest.mark.parametrize("temperature", TEMPS)
+@pytest.mark.parametrize("teacher", TEACHERS)
+@pytest.mark.parametrize("P,S,C", SMALL)
+def test_map_kernels(ops, P, S, C, teacher, temperature):
+    ps = _probs(P, S, C)
+    pn = [p.numpy() for p in ps]
+    pg = [p.to(DEV) for p in ps]
+    sen, tie = _special(P)
+    mode = ops.PL_TEACHERS[teacher]
+    g = torch.Generator().manual_seed(P + S + C)
+    dmap = torch.randn(P, generator=g)
+    for tau in _taus(PR.teachers_fp32(pn, teacher, 0.0)[2], P):
+        m, n, dn = R.soft_terms(pn, teacher, tau, temperature)
+        v, vb, d, db = R.map_and_grad(pn, n, dn, teacher, EPS)
+        kw = dict(teacher=mode, tau=tau, temperature=temperature, eps=EPS)
+        out, kept = ops.spl_map_fwd(pg, C, **kw)
+        out_nokept, none = ops.spl_map_fwd(pg, C, want_kept=False, **kw)
+        dps = ops.spl_map_bwd(pg, dmap.to(DEV), C, **kw)
+        torch.cuda.synchronize()
+        what = f"{teacher} P={P} S={S} C={C} T={temperature} tau={tau}"
+        # teachers, bit for bit
+        assert torch.equal(kept.cpu(), torch.from_numpy(PR.kept_map(m, teacher, S))), what
+        assert none is None and torch.equal(out, out_nokept)
+        nopix = n.sum((0, 2)) == 0
+        assert (out.cpu()[nopix] == 0).all(), what
+        for s in range(S):
+            assert (dps[s].cpu()[n[s] == 0] == 0).all(), what
+        if tau == 0.0:
+            assert m.all() and (kept == 1).all()
+        if tau == TAU_NONE:
+            assert not m.any() and (out == 0).all() and all((dp == 0).all() for dp in dps)
+        # values and gradients
+        _check(out, v, vb + TINY, what + " map")
+        for s in range(S):
+            ref = dmap.double()[:, None] * d[s]
+            _check(dps[s], ref, dmap.double().abs()[:, None] * db[s] + U * ref.abs() + TINY, what + f" dprobs {s}")
+        if tau == 0.0 and S <= C and teacher == "cross":
+            # the sentinels (one-hot views of distinct classes): the sharpened target of a one-hot view is that one-hot whatever T, so
+            # every term of a student on another view's class is log(0 + eps) = -23.03, S (S - 1) of them
+            w = PR.weight(teacher, S)
+            np.testing.assert_allclose(v[sen].numpy(), w * S * (S - 1) * -np.log(EPS), rtol=1e-12)
+            assert (v[sen] > 1e4 * vb[sen]).all()
+
+
+@functools.lru_cache(maxsize=2)
+def _softmax_and_conf(P, S, C, teacher):
+    """hip_ops.softmax_fwd's probabilities of ``_logits`` (softmax_px's bits) as numpy, and the raw confidences at threshold 0."""
+    from dct_amd import hip_ops
+    sm = [hip_ops.softmax_fwd(x.to(DEV), C) for x in _logits(P, S, C)]
+    pn = tuple(p.cpu().numpy() for p in sm)
+    return tuple(sm), pn, PR.teachers_fp32(pn, teacher, 0.0)[2]
+
+
+@pytest.mark.parametrize("temperature", TEMPS)
+@pytest.mark.parametrize("teacher", TEACHERS)
+@pytest.mark.parametrize("P,S,C", SMALL + LARGE)
+def test_step_kernel(ops, P, S, C, teacher, temperature):
+    xs = [x.to(DEV) for x in _logits(P, S, C)]
+    mode = ops.PL_TEACHERS[teacher]
+    gscale, gmul = 0.5, 2.0
+    gg = float(np.float32(gscale)) * gmul / P
+    gs = torch.tensor([gscale], device=DEV)
+    kden = S if teacher == "cross" else 1
+    g = torch.Generator().manual_seed(3 * P + S + C)
+    olds = [torch.randn(P, C, generator=g).to(DEV) for _ in range(S)]
+    sm, pn, q0 = _softmax_and_conf(P, S, C, teacher)
+    for tau in _taus(q0, P):
+        what = f"{teacher} P={P} S={S} C={C} T={temperature} tau={tau}"
+        kw = dict(gscale=gs, gmul=gmul, teacher=mode, tau=tau, temperature=temperature, eps=EPS)
+        dls = [_nan(P, C) for _ in range(S)]
+        out2, probs = ops.spl_logits_step(xs, C, dls, True, **kw)
+        acc = [o.clone() for o in olds]
+        out2a, none = ops.spl_logits_step(xs, C, acc, False, accumulate=True, **kw)
+        out2n, probs_n = ops.spl_logits_step(xs, C, None, True, **kw)
+        torch.cuda.synchronize()
+        # accumulate: the rounded gradient added to what was there, bit for bit; no gradients asked: the same values and maps
+        assert none is None and torch.equal(out2, out2a) and torch.equal(out2, out2n), what
+        for s in range(S):
+            assert torch.equal(acc[s], dls[s] + olds[s]), what
+            assert torch.equal(probs[s], probs_n[s]), what
+            assert torch.equal(probs[s], sm[s]), what                                   # softmax_fwd's bits
+        if tau == TAU_NONE:
+            # nothing kept: no float64 needed -- everything is exactly 0 and finite
+            assert out2.tolist() == [0.0, 0.0] and all((dl == 0).all() for dl in dls), what
+            continue
+        m, n, dn = R.soft_terms(pn, teacher, tau, temperature)
+        v, vb, d, db = R.map_and_grad(pn, n, dn, teacher, EPS)
+        # the kept fraction: whole numbers summed in fp32 (exact below 2^24), one fp32 division
+        frac = np.float32(m.sum()) / np.float32(np.float32(P) * np.float32(kden))
+        assert out2[1].item() == float(frac), (what, out2[1].item(), float(frac))
+        if tau == 0.0:
+            assert out2[1].item() == 1.0
+        ref = v.mean().item()
+        tol = (vb.sum().item() + SUM_DEPTH * U * v.abs().sum().item()) / P + 2 * U * abs(ref) + TINY
+        assert abs(out2[0].item() - ref) <= tol, (what, out2[0].item(), ref, tol)
+        for s in range(S):
+            gref, gb = R.logit_grad(pn[s], d[s], db[s], gg, C)
+            _check(dls[s], gref, gb, what + f" dlogits {s}")
+            assert (dls[s].cpu()[(n[s] == 0).all(1)] == 0).all(), what                  # a student without a teacher term: exactly 0
+
+
+@pytest.mark.parametrize("teacher", TEACHERS)
+@pytest.mark.parametrize("S", [2, 3])
+def test_hard_limit_is_the_hard_pseudo_label(ops, S, teacher):
+    """T = 2^-10 on teachers whose second-largest entry is at most half the largest (asserted on the reference): every u[c != k] is
+    exp2f of at most -1024, 0 in fp32, so the sharpened targets are exactly one-hot and the kernels must agree with dct_pl_* within
+    the sum of both references' bounds -- and the kept maps bit for bit."""
+    P, C, T = 257, 4, 2.0 ** -10
+    mode = ops.PL_TEACHERS[teacher]
+    g = torch.Generator().manual_seed(40 + S)
+    xs = [torch.randn(P, C, generator=g) for _ in range(S)]
+    for x in xs:
+        x[torch.arange(P), torch.arange(P) % C] += 8.0
+    xg = [x.to(DEV) for x in xs]
+    sm = [ops.softmax_fwd(x, C) for x in xg]
+    pn = [p.cpu().numpy() for p in sm]
+    gscale, gmul = 0.5, 2.0
+    gg = float(np.float32(gscale)) * gmul / P
+    gs = torch.tensor([gscale], device=DEV)
+    dmap = torch.randn(P, generator=g)
+    conf = PR.teachers_fp32(pn, teacher, 0.0)[2]
+    for tau in _taus(conf, P)[:2]:
+        q, k, m = R.teachers(pn, teacher, tau)
+        assert R.top_two_ratio_at_most_half(q)
+        t, dt = R.sharpen(q, k, T)
+        n, dn = R.terms(t, dt, m, teacher, S)
+        v, vb, d, db = R.map_and_grad(pn, n, dn, teacher, EPS)
+        nh = PR.term_counts(k, m, teacher, S, C)
+        vh, vhb, dh, dhrel = PR.map_and_grad(pn, nh, teacher, EPS)
+        what = f"{teacher} S={S} tau={tau}"
+        soft, kept = ops.spl_map_fwd(sm, C, teacher=mode, tau=tau, temperature=T, eps=EPS)
+        hard, kept_h = ops.pl_map_fwd(sm, C, mode, tau, EPS)
+        dsoft = ops.spl_map_bwd(sm, dmap.to(DEV), C, teacher=mode, tau=tau, temperature=T, eps=EPS)
+        dhard = ops.pl_map_bwd(sm, dmap.to(DEV), C, mode, tau, EPS)
+        ls, lh = [_nan(P, C) for _ in range(S)], [_nan(P, C) for _ in range(S)]
+        o2s, _ = ops.spl_logits_step(xg, C, ls, False, gscale=gs, gmul=gmul, teacher=mode, tau=tau, temperature=T, eps=EPS)
+        o2h, _ = ops.pl_logits_step(xg, C, lh, False, gscale=gs, gmul=gmul, teacher=mode, tau=tau, eps=EPS)
+        torch.cuda.synchronize()
+        assert torch.equal(kept, kept_h) and o2s[1].item() == o2h[1].item(), what
+        _check(soft, hard.cpu().double(), vb + vhb + 2 * TINY, what + " map")
+        for s in range(S):
+            a = dmap.double().abs()[:, None]
+            bound = a * db[s] + a * dhrel * dh[s].abs() + 2 * U * (a * dh[s].abs()) + 2 * TINY
+            _check(dsoft[s], dhard[s].cpu().double(), bound, what + f" dprobs {s}")
+            _, gb = R.logit_grad(pn[s], d[s], db[s], gg, C)
+            _, ghb = PR.logit_grad(pn[s], dh[s], gg, C)
+            _check(ls[s], lh[s].cpu().double(), gb + ghb, what + f" dlogits {s}")
+        tol = ((vb.sum().item() + SUM_DEPTH * U * v.abs().sum().item()) / P + 2 * U * abs(v.mean().item()) + TINY
+               + (vhb.sum().item() + SUM_DEPTH * U * vh.abs().sum().item()) / P + 2 * U * abs(vh.mean().item()) + TINY)
+        assert abs(o2s[0].item() - o2h[0].item()) <= tol, (what, o2s[0].item(), o2h[0].item(), tol)
+
+
+def test_status_codes(ops):
+    from dct_amd import _lib
+    lib = _lib.load()
+    P, C, S = 64, 4, 3
+    xs = [torch.randn(P, C, device=DEV) for _ in range(S)]
+    outs = [torch.empty(P, C, device=DEV) for _ in range(S)]
+    mp, out2 = torch.empty(P, device=DEV), torch.empty(2, device=DEV)
+    ws = ops._loss_ws(xs[0].device)
+    arr, oarr = ops._ptr_array(xs), ops._ptr_array(outs)
+    nullarr = (ctypes.c_void_p * S)(xs[0].data_ptr(), None, xs[2].data_ptr())
+    st = ops.stream()
+    BAD, UNS, WSP = -1, -2, -4
+
+    def fwd(S_=S, t=0, tau=0.5, T=0.5, eps=1e-10, a=arr, m_=mp.data_ptr(), P_=P, C_=C):
+        return lib.dct_spl_map_fwd(a, S_, t, tau, T, eps, m_, None, P_, C_, st)
+
+    def bwd(S_=S, t=0, tau=0.5, T=0.5, eps=1e-10, a=arr, dm=mp.data_ptr(), o=oarr, P_=P, C_=C):
+        return lib.dct_spl_map_bwd(a, S_, t, tau, T, eps, dm, o, P_, C_, st)
+
+    def step(S_=S, t=0, tau=0.5, T=0.5, eps=1e-10, a=arr, P_=P, C_=C, o2=out2.data_ptr(), w=ws.data_ptr(), wb=ws.numel()):
+        return lib.dct_spl_logits_step(a, S_, t, tau, T, eps, P_, C_, o2, None, None, 1.0, None, 0, w, wb, st)
+
+    for f in (fwd, bwd, step):
+        assert f() == 0 and f(t=1) == 0 and f(S_=1, t=1) == 0 and f(tau=float("inf")) == 0
+        assert f(T=2.0 ** -10) == 0 and f(T=1e30) == 0
+        assert f(S_=1, t=0) == BAD and f(S_=0, t=1) == BAD and f(S_=9) == BAD and f(S_=9, t=1) == BAD     # S outside the mode's range
+        assert f(t=2) == BAD and f(t=-1) == BAD                                                          # an unknown mode
+        assert f(tau=-0.1) == BAD and f(tau=float("nan")) == BAD
+        assert f(eps=0.0) == BAD and f(eps=-1e-10) == BAD and f(eps=float("nan")) == BAD
+        for T in (0.0, -1.0, float("nan"), float("inf"), 1e-46, 1e-39):     # (1e-46 is 0 in fp32; 1.f / 1e-39f is infinite)
+            assert f(T=T) == BAD, T
+        assert f(a=None) == BAD and f(a=nullarr) == BAD and f(P_=0) == BAD
+        assert f(C_=1) == UNS and f(C_=9) == UNS
+    assert fwd(m_=None) == BAD and bwd(dm=None) == BAD and bwd(o=None) == BAD and bwd(o=nullarr) == BAD and step(o2=None) == BAD
+    assert step(w=None) == WSP and step(wb=16) == WSP
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("name,teacher", [("soft_cps", "cross"), ("soft_pseudo_label", "ensemble")])
+def test_module_through_autograd_equals_the_raw_ops(ops, name, teacher):
+    from dct_amd.loss import get_loss_fn
+    B, C, H, W, S = 2, 4, 9, 13, 3
+    g = torch.Generator().manual_seed(5)
+    logits = [(torch.randn(B, C, H, W, generator=g) * 3).to(DEV) for _ in range(S)]
+    leaves = [torch.softmax(x, 1).requires_grad_(True) for x in logits]
+    q = PR.teachers_fp32([p.detach().permute(0, 2, 3, 1).reshape(-1, C).cpu().numpy() for p in leaves], teacher, 0.0)[2]
+    tau = _taus(q, B * H * W)[1]
+    crit = get_loss_fn(name, threshold=tau, temperature=0.25)
+    out = crit(leaves)
+    assert out.shape == (B, H, W) and torch.is_tensor(crit.last_kept) and crit.last_kept.is_cuda and crit.last_kept.dim() == 0
+    seed = torch.randn(B, H, W, generator=g).to(DEV)
+    (out * seed).sum().backward()
+    pcs = [p.detach().permute(0, 2, 3, 1).contiguous() for p in leaves]
+    assert crit.launch_args()["temperature"] == 0.25
+    mp, kept = ops.spl_map_fwd(pcs, C, **crit.launch_args())
+    dps = ops.spl_map_bwd(pcs, seed.reshape(-1).contiguous(), C, **crit.launch_args())
+    other, _ = ops.spl_map_fwd(pcs, C, **dict(crit.launch_args(), temperature=0.5))
+    torch.cuda.synchronize()
+    assert torch.equal(out.detach().reshape(-1), mp) and not torch.equal(mp, other)       # (the temperature reaches the kernel)
+    assert torch.equal(crit.last_kept, kept.mean()) and 0.2 <= crit.last_kept.item() <= 0.8
+    for p, dp in zip(leaves, dps):
+        assert torch.equal(p.grad.permute(0, 2, 3, 1).reshape(-1, C), dp.reshape(-1, C))
+    assert torch.isfinite(out.mean())
+    if teacher == "cross":
+        with pytest.raises(ValueError, match="at least 2 views"):
+            crit(leaves[:1])
+    else:
+        assert crit(leaves[:1]).shape == (B, H, W)
