@@ -161,6 +161,9 @@ SIGNATURES = {
     "dct_spl_map_fwd": (_i, [_P, _i, _i, _f, _f, _f, _P, _P, _i64, _i, _P]),
     "dct_spl_map_bwd": (_i, [_P, _i, _i, _f, _f, _f, _P, _P, _i64, _i, _P]),
     "dct_spl_logits_step": (_i, [_P, _i, _i, _f, _f, _f, _i64, _i, _P, _P, _P, _f, _P, _i, _P, _sz, _P]),
+    "dct_mse_map_fwd": (_i, [_P, _i, _i, _f, _P, _P, _i64, _i, _P]),
+    "dct_mse_map_bwd": (_i, [_P, _i, _i, _f, _P, _P, _i64, _i, _P]),
+    "dct_mse_logits_step": (_i, [_P, _i, _i, _f, _i64, _i, _P, _P, _P, _f, _P, _i, _P, _sz, _P]),
     "dct_kl_logits_fwd": (_i, [_P, _P, _i64, _i, _f, _P, _P, _sz, _P]),
     "dct_kl_logits_bwd": (_i, [_P, _P, _i64, _i, _f, _P, _f, _P, _i, _P]),
     "dct_argmax": (_i, [_P, _P, _i64, _i, _P]),

@@ -1499,6 +1499,188 @@ __global__ __launch_bounds__(256) void spl_step_kernel(PtrPack pk, PtrPack probs
   block_partial2(sum, keptsum, partial);
 }
 
+// ---- softmax-MSE consistency: the squared distance to the other views' (or the mean) prediction (the rule: include/dct.h, dct_mse_*) ---
+// The masks of one pixel, as constants: pl_teachers' compares on the same fp32 values (first maximum, sums in view order, argmax before
+// scaling), without its class counts, which a squared distance has no use for.  Out: cross: m[j] = p_j[k_j] >= tau (false for j >= S);
+// ensemble: q[c] = sum[c] * invS and m[0] = q[k] >= tau.  Returns the number of kept teachers.
+template <int C, int SMAX>
+__device__ __forceinline__ int mse_teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, bool (&m)[SMAX], float (&q)[C]) {
+#pragma clang fp contract(off)    // as pl_teachers: the sums and q are formed from the ROUNDED probabilities
+  int kept = 0;
+#pragma unroll
+  for (int s = 0; s < SMAX; ++s) m[s] = false;
+#pragma unroll
+  for (int c = 0; c < C; ++c) q[c] = 0.f;
+  if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float bv = p[s][0];
+#pragma unroll
+        for (int c = 1; c < C; ++c) if (p[s][c] > bv) bv = p[s][c];
+        if (bv >= tau) { m[s] = true; ++kept; }
+      }
+    }
+  } else {
+    float sum[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) sum[c] = p[0][c];
+#pragma unroll
+    for (int s = 1; s < SMAX; ++s) {
+      if (s < S) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) sum[c] = sum[c] + p[s][c];
+      }
+    }
+    float bv = sum[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) if (sum[c] > bv) bv = sum[c];                  // on the unscaled sums: scaling cannot create a tie
+#pragma unroll
+    for (int c = 0; c < C; ++c) q[c] = sum[c] * invS;
+    if (bv * invS >= tau) { m[0] = true; kept = 1; }
+  }
+  return kept;
+}
+// student i of one pixel: returns a_i (the pixel's map value is wgt times the sum over i) and d[c] = d map / d p_i[c].  Every difference
+// is the difference of two probabilities (never a total minus the student's own share), every square a rounded product added in class
+// order, a masked teacher's differences are 0.  i is a constant of the caller's unrolled loop: nothing is addressed at run time, and
+// only d[C] and two sums are live beside the probabilities.
+template <int C, int SMAX>
+__device__ __forceinline__ float mse_student(const float (&p)[SMAX][C], const bool (&m)[SMAX], const float (&q)[C], int S, int teacher, int i,
+                                             float wgt, float (&d)[C]) {
+#pragma clang fp contract(off)    // the squares are rounded before they are added, as the rule states them and as the reference bounds them
+  float a = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) d[c] = 0.f;
+  if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+    for (int j = 0; j < SMAX; ++j) {
+      if (j < S && j != i) {
+        float sq = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const float e = m[j] ? p[i][c] - p[j][c] : 0.f;
+          sq = sq + e * e;
+          d[c] = d[c] + e;
+        }
+        a = a + sq;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float e = m[0] ? p[i][c] - q[c] : 0.f;
+      a = a + e * e;
+      d[c] = e;
+    }
+  }
+  const float w2 = 2.f * wgt;
+#pragma unroll
+  for (int c = 0; c < C; ++c) d[c] = w2 * d[c];
+  return a;
+}
+// kden: the teacher terms of a pixel (cross: S, ensemble: 1); wgt: 1 / (C S (S - 1)) resp. 1 / (C S)
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void mse_map_fwd_kernel(PtrPack pk, int S, int teacher, float tau, float invS, float wgt, float kden,
+                                                           float* map, float* keptmap, long long P) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float p[SMAX][C], q[C];
+    bool m[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
+    }
+    const int kept = mse_teachers<C, SMAX>(p, S, teacher, tau, invS, m, q);
+    float a = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float d[C];
+        a += mse_student<C, SMAX>(p, m, q, S, teacher, s, wgt, d);
+      }
+    }
+    map[pix] = wgt * a;
+    if (keptmap) keptmap[pix] = (float)kept / kden;
+  }
+}
+// dprobs_s = dmap[pix] * d map / d p_s, the masks recomputed from the probabilities
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void mse_map_bwd_kernel(PtrPack pk, int S, int teacher, float tau, float invS, float wgt,
+                                                           const float* dmap, long long P) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float p[SMAX][C], q[C];
+    bool m[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
+    }
+    const float gp = dmap[pix];
+    mse_teachers<C, SMAX>(p, S, teacher, tau, invS, m, q);
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float d[C];
+        mse_student<C, SMAX>(p, m, q, S, teacher, s, wgt, d);
+#pragma unroll
+        for (int c = 0; c < C; ++c) d[c] = d[c] != 0.f ? gp * d[c] : 0.f;     // a masked entry is 0 whatever dmap holds
+        store_px<C>(pk.out[s], pix, d, false);
+      }
+    }
+  }
+}
+// pl_step_kernel with the squared distances: one pixel per trip, every load of the pixel issued before its first store; block partials
+// of (map value, kept teachers) for pl_finalize_kernel.  No logarithm and no division per class.
+template <int C, int SMAX>
+__global__ __launch_bounds__(256) void mse_step_kernel(PtrPack pk, PtrPack probs, int S, int teacher, float tau, float invS, float wgt,
+                                                        long long P, const float* gscale, float gmul, int acc, int want_grad, float* partial) {
+  const float g = (gscale ? gscale[0] : 1.f) * gmul / (float)P;
+  float sum = 0.f, keptsum = 0.f;
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+    float x[SMAX][C], old[SMAX][C];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        load_px<C>(pk.in[s], pix, x[s]);
+        if (want_grad && acc) load_px<C>(pk.out[s], pix, old[s]);
+      }
+    }
+    float p[SMAX][C], q[C];
+    bool m[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        softmax_px<C>(x[s], p[s]);
+        if (probs.out[s]) store_px<C>(probs.out[s], pix, p[s], false);
+      }
+    }
+    keptsum += (float)mse_teachers<C, SMAX>(p, S, teacher, tau, invS, m, q);
+    float a = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < S) {
+        float d[C];
+        a += mse_student<C, SMAX>(p, m, q, S, teacher, s, wgt, d);
+        if (want_grad) {
+          float dot = 0.f;
+#pragma unroll
+          for (int c = 0; c < C; ++c) dot += d[c] * p[s][c];
+          float o[C];
+#pragma unroll
+          for (int c = 0; c < C; ++c) o[c] = g * p[s][c] * (d[c] - dot);
+          if (acc) {
+#pragma clang fp contract(off)    // store_px's accumulate: round, then add
+#pragma unroll
+            for (int c = 0; c < C; ++c) o[c] = o[c] + old[s][c];
+          }
+          store_px<C>(pk.out[s], pix, o, false);
+        }
+      }
+    }
+    sum += wgt * a;
+  }
+  block_partial2(sum, keptsum, partial);
+}
+
 // ---- KL(y || p) -----------------------------------------------------------------------------------
 template <int C, bool FROM_LOGITS>
 __global__ __launch_bounds__(256) void kl_fwd_kernel(const float* pin, const float* yin, long long P, float eps, float* map, float* partial) {
@@ -2322,6 +2504,64 @@ extern "C" int dct_spl_logits_step(const float* const* logits, int S, int teache
   if (S <= 2) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, 2>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
   else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
   else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * r.kden);
+  return dct_check_launch();
+}
+
+// ---- softmax-MSE consistency --------------------------------------------------------------------------
+namespace {
+// the host-side constants of the rule, without C: 1 / S, the teacher terms of a pixel and the ordered pairs (cross) or views (ensemble)
+// the weight divides by beside C
+struct MseRule { float invS, kden; int terms; };
+bool mse_rule(int S, int teacher, float tau, MseRule& r) {
+  if (teacher != DCT_PL_CROSS && teacher != DCT_PL_ENSEMBLE) return false;
+  if (S < (teacher == DCT_PL_CROSS ? 2 : 1) || S > MAXS) return false;
+  if (!(tau >= 0.f)) return false;                           // (a NaN fails it)
+  r.invS = 1.f / (float)S;
+  r.kden = teacher == DCT_PL_CROSS ? (float)S : 1.f;
+  r.terms = teacher == DCT_PL_CROSS ? S * (S - 1) : S;
+  return true;
+}
+// w = 1 / (C S (S - 1)) resp. 1 / (C S), formed where C is known to be in 2..8
+inline float mse_wgt(int C, const MseRule& r) { return 1.f / (float)(C * r.terms); }
+}  // namespace
+
+extern "C" int dct_mse_map_fwd(const float* const* probs, int S, int teacher, float tau, float* map, float* kept, int64_t pixels, int C_,
+                               dct_stream stream) {
+  PtrPack pk;
+  MseRule r;
+  if (!mse_rule(S, teacher, tau, r) || !fill_pack(pk, probs, nullptr, S) || !map || pixels < 1) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = wide_grid(pixels);
+  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_map_fwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, r.invS, mse_wgt(C, r), r.kden, map, kept, (long long)pixels)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_map_fwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, r.invS, mse_wgt(C, r), r.kden, map, kept, (long long)pixels)); }
+  return dct_check_launch();
+}
+extern "C" int dct_mse_map_bwd(const float* const* probs, int S, int teacher, float tau, const float* dmap, float* const* dprobs,
+                               int64_t pixels, int C_, dct_stream stream) {
+  PtrPack pk;
+  MseRule r;
+  if (!mse_rule(S, teacher, tau, r) || !dprobs || !fill_pack(pk, probs, dprobs, S) || !dmap || pixels < 1) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = wide_grid(pixels);
+  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_map_bwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, r.invS, mse_wgt(C, r), dmap, (long long)pixels)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_map_bwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, r.invS, mse_wgt(C, r), dmap, (long long)pixels)); }
+  return dct_check_launch();
+}
+extern "C" int dct_mse_logits_step(const float* const* logits, int S, int teacher, float tau, int64_t pixels, int C_, float* out2,
+                                   float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
+                                   void* workspace, size_t workspace_bytes, dct_stream stream) {
+  PtrPack pk, pp;
+  MseRule r;
+  if (!mse_rule(S, teacher, tau, r) || !fill_pack(pk, logits, dlogits, S) || !out2 || pixels < 1) return DCT_ERR_BAD_ARG;
+  for (int s = 0; s < MAXS; ++s) { pp.in[s] = nullptr; pp.out[s] = (probs && s < S) ? probs[s] : nullptr; }
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);
+  const int want = dlogits ? 1 : 0;
+  if (S <= 2) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_step_kernel<C, 2>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, r.invS, mse_wgt(C, r), (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, r.invS, mse_wgt(C, r), (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
+  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, r.invS, mse_wgt(C, r), (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
   DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * r.kden);
   return dct_check_launch();
 }

@@ -885,6 +885,36 @@ def spl_logits_step(logits: List[torch.Tensor], C_, dlogits: List[torch.Tensor] 
     return out, probs
 
 
+def mse_map_fwd(probs: List[torch.Tensor], C_, teacher=PL_CROSS, tau=0.0, want_kept: bool = True):
+    """-> (map [P], kept map [P] or None) of the softmax-MSE consistency term over S probability maps (the rule: include/dct.h, dct_mse_*)."""
+    P = probs[0].numel() // C_
+    out = torch.empty(P, dtype=torch.float32, device=probs[0].device)
+    kept = torch.empty_like(out) if want_kept else None
+    call("dct_mse_map_fwd", _ptr_array(probs), len(probs), int(teacher), float(tau), ptr(out), ptr(kept), P, C_, stream())
+    return out, kept
+
+
+def mse_map_bwd(probs: List[torch.Tensor], dmap, C_, teacher=PL_CROSS, tau=0.0):
+    outs = [torch.empty_like(p) for p in probs]
+    call("dct_mse_map_bwd", _ptr_array(probs), len(probs), int(teacher), float(tau), ptr(dmap), _ptr_array(outs), probs[0].numel() // C_, C_,
+         stream())
+    return outs
+
+
+def mse_logits_step(logits: List[torch.Tensor], C_, dlogits: List[torch.Tensor] = None, want_probs: bool = True, gscale=None, gmul=1.0,
+                    accumulate=False, teacher=PL_CROSS, tau=0.0):
+    """`pl_logits_step` with the squared distance between the softmax outputs: -> (out2 = (mean loss over all pixels, kept fraction),
+    [softmax(logits_s)] or None), the logit gradients into ``dlogits`` (None: no gradients), in ONE pass + the finalize (dct_mse_logits_step)."""
+    dev = logits[0].device
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = _loss_ws(dev)
+    probs = [torch.empty_like(lp) for lp in logits] if want_probs else None
+    call("dct_mse_logits_step", _ptr_array(logits), len(logits), int(teacher), float(tau), logits[0].numel() // C_, C_, ptr(out),
+         _ptr_array(probs) if probs is not None else None, ptr(gscale), float(gmul),
+         _ptr_array(dlogits) if dlogits is not None else None, int(accumulate), ptr(ws), ws.numel(), stream())
+    return out, probs
+
+
 def kl_logits_fwd(p_logits, y_logits, C_, eps=1e-10):
     out = torch.empty(1, dtype=torch.float32, device=p_logits.device)
     ws = _loss_ws(out.device)

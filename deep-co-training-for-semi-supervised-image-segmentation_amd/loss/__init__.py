@@ -3,6 +3,7 @@ from .loss import CrossEntropyLoss2d, CrossEntropyDiceLoss2d, DiceLoss, JSD_2D, 
 from .loss import BoundaryLoss, CrossEntropyBoundaryLoss2d, signed_distance_map  # noqa: F401
 from .loss import PseudoLabel_2D, CrossPseudoSupervision_2D, EnsemblePseudoLabel_2D  # noqa: F401
 from .loss import SoftPseudoLabel_2D, SoftCrossPseudoSupervision_2D, SoftEnsemblePseudoLabel_2D  # noqa: F401
+from .loss import MSEConsistency_2D, CrossMSE_2D, EnsembleMSE_2D  # noqa: F401
 from .loss import FocalLoss2d  # noqa: F401
 from .loss import TopKCrossEntropyLoss2d  # noqa: F401
 from .loss import CrossEntropyTverskyLoss2d, FocalTverskyLoss, TverskyLoss  # noqa: F401
@@ -24,7 +25,9 @@ LOSS = {'cross_entropy': CrossEntropyLoss2d,
         'cps': CrossPseudoSupervision_2D,
         'pseudo_label': EnsemblePseudoLabel_2D,
         'soft_cps': SoftCrossPseudoSupervision_2D,
-        'soft_pseudo_label': SoftEnsemblePseudoLabel_2D}
+        'soft_pseudo_label': SoftEnsemblePseudoLabel_2D,
+        'cross_mse': CrossMSE_2D,
+        'mean_mse': EnsembleMSE_2D}
 
 
 def get_loss_fn(name: str, **kwargs):

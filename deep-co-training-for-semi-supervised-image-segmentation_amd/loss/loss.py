@@ -834,3 +834,86 @@ class SoftEnsemblePseudoLabel_2D(SoftPseudoLabel_2D):
 
     def __init__(self, temperature=0.5, threshold=0.0, eps=1e-10):
         super().__init__('ensemble', temperature, threshold, eps)
+
+
+class _MSEMapFn(torch.autograd.Function):
+    """The softmax-MSE consistency map on dct_mse_map_*; ``rule``: ``MSEConsistency_2D.launch_args()``.  As ``_PLMapFn``: nothing but the
+    inputs is saved, the backward recomputes the masks."""
+
+    @staticmethod
+    def forward(ctx, rule, *probs):
+        pps = [_pc(p) for p in probs]
+        ctx.save_for_backward(*pps)
+        ctx.rule = rule
+        out, kept = K.mse_map_fwd(pps, pps[0].shape[3], **rule)
+        kept = kept.view(pps[0].shape[:3])
+        ctx.mark_non_differentiable(kept)
+        return out.view(pps[0].shape[:3]), kept
+
+    @staticmethod
+    def backward(ctx, g, _):
+        pps = list(ctx.saved_tensors)
+        dps = K.mse_map_bwd(pps, g.to(torch.float32).contiguous().view(-1), pps[0].shape[3], **ctx.rule)
+        return (None,) + tuple(_nchw(d) for d in dps)
+
+
+class MSEConsistency_2D(nn.Module):
+    """Softmax-MSE consistency of S views (the rule: include/dct.h, dct_mse_*), with ``PseudoLabel_2D``'s call shape: a list of [B,C,H,W]
+    probabilities in, a [B,H,W] map out, whose mean over ALL pixels is the loss.  Every view is pulled towards every other view's
+    prediction (``teacher='cross'``, 2 or more views) or towards the mean prediction (``teacher='ensemble'``) by the squared distance,
+    averaged over the classes: bounded by 2 / C per pixel, no eps, no logarithm.  ``threshold`` masks a teacher by its confidence, as for
+    the pseudo-label criteria; 0 keeps every teacher.  Teachers are constants.  After a call ``last_kept`` is a device scalar, the kept
+    fraction of the teacher terms (nothing synchronises).
+    Not a ``PseudoLabel_2D``: the trainer tells the criteria apart by exact type."""
+
+    def __init__(self, teacher='cross', threshold=0.0):
+        super().__init__()
+        name = type(self).__name__
+        if teacher not in K.PL_TEACHERS:
+            raise ValueError(f"dct_amd {name}: teacher must be 'cross' or 'ensemble', got {teacher!r}")
+        self.teacher = teacher
+        try:
+            self.threshold = float(threshold)
+        except (TypeError, ValueError):
+            raise ValueError(f"dct_amd {name}: threshold must be a number, got {threshold!r}")
+        if not (0.0 <= self.threshold <= float('inf')):
+            raise ValueError(f"dct_amd {name}: threshold must be >= 0, got {threshold}")
+        self.last_kept = None
+
+    def launch_args(self):
+        """The keyword arguments of hip_ops.mse_* (and what a captured step is valid for)."""
+        return dict(teacher=K.PL_TEACHERS[self.teacher], tau=self.threshold)
+
+    def min_views(self):
+        return 2 if self.teacher == 'cross' else 1
+
+    def forward(self, input: List[torch.Tensor]):
+        input = list(input)
+        name = type(self).__name__
+        if len(input) < self.min_views():
+            raise ValueError(f"dct_amd {name}: teacher='{self.teacher}' needs at least {self.min_views()} views, got {len(input)}")
+        if len(input) > MAX_VIEWS:
+            raise ValueError(f"dct_amd {name} handles up to {MAX_VIEWS} views per call, got {len(input)}")
+        if not all(p.is_cuda for p in input):
+            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
+        if DEBUG_ASSERTS:
+            for inprob in input:
+                assert _simplex(inprob, 1)
+        out, kept = _MSEMapFn.apply(self.launch_args(), *input)
+        self.last_kept = kept.mean()
+        return out
+
+
+class CrossMSE_2D(MSEConsistency_2D):
+    """The squared distance to every other view's prediction: ``MSEConsistency_2D(teacher='cross')``."""
+
+    def __init__(self, threshold=0.0):
+        super().__init__('cross', threshold)
+
+
+class EnsembleMSE_2D(MSEConsistency_2D):
+    """The squared distance to the mean prediction (temporal-ensembling style, the mean held constant):
+    ``MSEConsistency_2D(teacher='ensemble')``."""
+
+    def __init__(self, threshold=0.0):
+        super().__init__('ensemble', threshold)

@@ -115,10 +115,10 @@ class ExecutionPlan:
 class _StepContext(object):
     """What one issue of the step carries from its forward passes to its optimizers; dropped when the step returns (the join closure
     holds this step's streams, the pass buffers' owners its tapes)."""
-    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice", "pl", "focal", "topk", "tversky", "spl")
+    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice", "pl", "focal", "topk", "tversky", "spl", "mse")
 
     def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None, pl=None, focal=None, topk=None,
-                 spl=None, tversky=None):
+                 spl=None, mse=None, tversky=None):
         self.sched, self.route = sched, route
         # the gradient exchange as far as it is issued from inside the step (between two graphs it is the replay's business)
         self.sync = grad_sync if any(e in ("model", "buckets") for e in route.exchange) else None
@@ -137,6 +137,7 @@ class _StepContext(object):
         self.focal = focal                  # a focal criterion's launch arguments (FocalLoss2d.launch_args), or None
         self.topk = topk                    # a top-k criterion's launch arguments (TopKCrossEntropyLoss2d.launch_args), or None
         self.spl = spl                      # a soft pseudo-label consistency criterion's launch arguments (SoftPseudoLabel_2D.launch_args), or None
+        self.mse = mse                      # a softmax-MSE consistency criterion's launch arguments (MSEConsistency_2D.launch_args), or None
         self.tversky = tversky              # a Tversky / focal Tversky / CE + Tversky criterion's launch arguments (CrossEntropyTverskyLoss2d.launch_args), or None
 
     def on(self, streams, i):
@@ -304,17 +305,18 @@ class CoTrainer(Trainer):
         gpu = self.device.type == 'cuda'
         fused_criteria = False
         if gpu:
-            from ..loss.loss import (CrossEntropyDiceLoss2d, CrossEntropyLoss2d, CrossEntropyTverskyLoss2d, CrossPseudoSupervision_2D, DiceLoss,
-                                     EnsemblePseudoLabel_2D, FocalLoss2d, FocalTverskyLoss, JSD_2D, PseudoLabel_2D, SoftCrossPseudoSupervision_2D,
-                                     SoftEnsemblePseudoLabel_2D, SoftPseudoLabel_2D, TopKCrossEntropyLoss2d, TverskyLoss)
+            from ..loss.loss import (CrossEntropyDiceLoss2d, CrossEntropyLoss2d, CrossEntropyTverskyLoss2d, CrossMSE_2D, CrossPseudoSupervision_2D, DiceLoss,
+                                     EnsembleMSE_2D, EnsemblePseudoLabel_2D, FocalLoss2d, FocalTverskyLoss, JSD_2D, MSEConsistency_2D, PseudoLabel_2D,
+                                     SoftCrossPseudoSupervision_2D, SoftEnsemblePseudoLabel_2D, SoftPseudoLabel_2D, TopKCrossEntropyLoss2d, TverskyLoss)
             sup = self.criterions['sup']
             # (class weights, focal, top-k, Dice, CE + Dice and the Tversky family ride the fused kernels; the sum and the per-pixel map go through the module: the generic step)
             fused_sup = (type(sup) in (CrossEntropyLoss2d, FocalLoss2d) and sup.reduction == 'mean') or type(sup) in (
                 CrossEntropyDiceLoss2d, DiceLoss, TopKCrossEntropyLoss2d, CrossEntropyTverskyLoss2d, TverskyLoss, FocalTverskyLoss)
             cons = self.criterions['jsd']
-            # (the pseudo-label criteria ride dct_pl_logits_step, the soft ones dct_spl_logits_step; a cross teacher with a single network goes through the module, which refuses it)
+            # (the pseudo-label criteria ride dct_pl_logits_step, the soft ones dct_spl_logits_step, softmax-MSE dct_mse_logits_step; a cross teacher with a single network goes through the module, which refuses it)
             fused_cons = type(cons) is JSD_2D or (type(cons) in (PseudoLabel_2D, CrossPseudoSupervision_2D, EnsemblePseudoLabel_2D,
-                                                                 SoftPseudoLabel_2D, SoftCrossPseudoSupervision_2D, SoftEnsemblePseudoLabel_2D)
+                                                                 SoftPseudoLabel_2D, SoftCrossPseudoSupervision_2D, SoftEnsemblePseudoLabel_2D,
+                                                                 MSEConsistency_2D, CrossMSE_2D, EnsembleMSE_2D)
                                                   and len(nets) >= cons.min_views())
             fused_criteria = fused_sup and fused_cons
         if self._group_max is None and gpu and all(n.plan_net and n.supports_pass_groups for n in nets):
@@ -494,9 +496,13 @@ class CoTrainer(Trainer):
     def _jsd(self, ctx, lps, dl_outs):
         """Value, the S softmax maps and the S logit gradients in ONE pass over the logits (dct_jsd_logits_step: bit for bit the five
         separate launches; dct_pl_logits_step when the consistency criterion is a pseudo-label one, dct_spl_logits_step when it is a soft
-        pseudo-label one: their ``last_kept`` is set to the kept fraction on the device).  -> (value, NCHW softmax maps)."""
+        pseudo-label one, dct_mse_logits_step when it is a softmax-MSE one: their ``last_kept`` is set to the kept fraction on the device).  -> (value, NCHW softmax maps)."""
         from .. import hip_ops as K
         from ..loss.loss import _nchw
+        if ctx.mse is not None:
+            out2, probs = K.mse_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot, **ctx.mse)
+            self.criterions['jsd'].last_kept = out2[1]
+            return out2[0], [_nchw(p_) for p_ in probs]
         if ctx.spl is not None:
             out2, probs = K.spl_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot, **ctx.spl)
             self.criterions['jsd'].last_kept = out2[1]
@@ -650,17 +656,18 @@ class CoTrainer(Trainer):
         ``lam_dev`` (float32[2] device tensor holding lambda_cot, lambda_adv): the loss weights are then read on the
         device, as a captured graph needs."""
         nets = [s.torchnet for s in self.segmentators]
-        from ..loss.loss import CrossEntropyTverskyLoss2d, FocalLoss2d, SoftPseudoLabel_2D, TopKCrossEntropyLoss2d
+        from ..loss.loss import CrossEntropyTverskyLoss2d, FocalLoss2d, MSEConsistency_2D, SoftPseudoLabel_2D, TopKCrossEntropyLoss2d
         sup, cons = self.criterions['sup'], self.criterions['jsd']
         rule = sup.launch_args(self.C) if hasattr(sup, "launch_args") else None
         focal, topk, tversky = type(sup) is FocalLoss2d, type(sup) is TopKCrossEntropyLoss2d, isinstance(sup, CrossEntropyTverskyLoss2d)
         soft = isinstance(cons, SoftPseudoLabel_2D)         # (only the three exact types reach the fused step: _step_facts)
+        mse = isinstance(cons, MSEConsistency_2D)           # (likewise)
         ctx = _StepContext(self._sched, route, self.grad_sync, (float(self.cot_scheduler.value), float(self.adv_scheduler.value)),
                            lam_dev, sup.ignore_index, sup.device_weight(self.device, self.C),
                            None if focal or topk or tversky else rule,
-                           cons.launch_args() if hasattr(cons, "launch_args") and not soft else None,
+                           cons.launch_args() if hasattr(cons, "launch_args") and not soft and not mse else None,
                            rule if focal else None, rule if topk else None, tversky=rule if tversky else None,
-                           spl=cons.launch_args() if soft else None)
+                           spl=cons.launch_args() if soft else None, mse=cons.launch_args() if mse else None)
         streams = self._streams() if route.model_streams else None
         if route.kind in ("wide", "wide_grouped"):
             return self._run_step_wide(ctx, lab, unl, train_adv, adv_choice, nets)

@@ -589,6 +589,46 @@ int dct_spl_map_bwd(const float* const* probs, int S, int teacher, float tau, fl
 int dct_spl_logits_step(const float* const* logits, int S, int teacher, float tau, float temperature, float eps, int64_t pixels, int C,
                         float* out2, float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
                         void* workspace, size_t workspace_bytes, dct_stream stream);
+/* ---- softmax-MSE consistency: every view is pulled towards the other views' (or the mean) prediction by the squared distance ----
+ * Per pixel: S views (1 <= S <= 8) with fp32 probabilities p_s[0..C), C in 2..8, a teacher mode (DCT_PL_CROSS, S >= 2, or DCT_PL_ENSEMBLE,
+ * S >= 1) and a confidence threshold tau >= 0.  There is no eps: nothing is divided and no logarithm is taken.
+ * Teachers are constants: no gradient flows through a teacher vector, a confidence or a mask.  Everything below is fp32.
+ *
+ * The first maximum k, the confidence and the mask m are dct_pl_*'s, bit for bit:
+ *   cross     teacher j is p_j,  k_j = first maximum of p_j,  m_j = (p_j[k_j] >= tau)
+ *   ensemble  sum = ((p_0 + p_1) + ...), added in view order,  k = first maximum of the unscaled sums,
+ *             q[c] = sum[c] * (1.f / (float)S),  m = (q[k] >= tau);  the student's own share inside q is held constant too.
+ * Student i:  cross     e_ij[c] = p_i[c] - p_j[c],   a_i = sum over j != i, in ascending j, of m_j * (e_ij[0]^2 + ... + e_ij[C-1]^2)
+ *                       d map / d p_i[c] = 2 w * sum over j != i, in ascending j, of m_j * e_ij[c],         w = 1.f / (float)(C S (S - 1))
+ *             ensemble  e_i[c] = p_i[c] - q[c],      a_i = m * (e_i[0]^2 + ... + e_i[C-1]^2)
+ *                       d map / d p_i[c] = 2 w * m * e_i[c],                                                w = 1.f / (float)(C S)
+ *   map = w * (a_0 + a_1 + ...), added in view order.
+ *   Every e is formed as the difference of two probabilities, never as a total minus the student's own share: (t_0 + t_1) - t_0 is not
+ *   t_1 (see dct_spl_*), and views that agree bit for bit must give a value and every gradient of exactly 0.
+ *   Contraction: every square is a ROUNDED product, added in class order; the sums over j and i are chains of rounded adds, each starting
+ *   from 0; 2 w is exact and its product with the sum of differences is rounded once.  No multiply of this rule folds into an add.
+ * From logits: p_s = softmax(x_s) with dct_softmax_fwd's bits; d / d x_i[c] = g * p_i[c] * (d_i[c] - sum_c' d_i[c'] p_i[c']), g = gscale[0] * gmul / P
+ * (gscale NULL: 1); accumulate rounds, then adds.
+ * The mean is over all P pixels, never over the kept ones.  kept is dct_pl_*'s kept fraction and kept map, unchanged in meaning.
+ * Consequences:
+ *   - every pixel's map value lies in [0, 2 / C]: two points of the simplex are at most sqrt(2) apart, and w counts the terms;
+ *   - two one-hot views of different classes give exactly 2 / C under the cross teacher with S = 2 (4 w, a power of two times w);
+ *   - views that agree bit for bit give a value and every gradient of exactly 0: under the cross teacher at any S, under the ensemble
+ *     teacher at S = 1 and 2, where sum and q are exact (from three views on the fp32 mean of equal numbers may differ from them in the
+ *     last bit);
+ *   - with everything masked, the value and every gradient are exactly 0;
+ *   - S = 1 with the ensemble teacher is exactly 0 (q = p * 1.f).
+ * Status codes are dct_pl_*'s without the eps cases: DCT_ERR_BAD_ARG for S outside the mode's range, an unknown mode, a negative or NaN
+ * tau, a null pointer (an entry of a pointer array included), pixels < 1; DCT_ERR_UNSUPPORTED for C outside 2..8; DCT_ERR_WORKSPACE as
+ * dct_jsd_logits_step. */
+int dct_mse_map_fwd(const float* const* probs, int S, int teacher, float tau, float* map, float* kept, int64_t pixels, int C,
+                    dct_stream stream);
+int dct_mse_map_bwd(const float* const* probs, int S, int teacher, float tau, const float* dmap, float* const* dprobs, int64_t pixels,
+                    int C, dct_stream stream);
+/* dct_pl_logits_step's contract (workspace, out2, probs, dlogits, two launches) with the squared distances */
+int dct_mse_logits_step(const float* const* logits, int S, int teacher, float tau, int64_t pixels, int C, float* out2,
+                        float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
+                        void* workspace, size_t workspace_bytes, dct_stream stream);
 /* out[0] = mean_pix sum_c y*(log(y+eps)-log(p+eps)), p = softmax(p_logits), y = softmax(y_logits) */
 int dct_kl_logits_fwd(const float* p_logits, const float* y_logits, int64_t pixels, int C, float eps,
                       float* out1, void* workspace, size_t workspace_bytes, dct_stream stream);

@@ -15,6 +15,7 @@ t bench_topk_ce      python tools/bench_topk_ce.py
 t bench_tversky      python tools/bench_tversky.py
 t bench_pseudo_label python tools/bench_pseudo_label.py
 t bench_soft_label   python tools/bench_soft_label.py
+t bench_mse_consistency python tools/bench_mse_consistency.py
 t bench_pointwise    python tools/bench_pointwise.py
 t debug_conv_case    python tools/debug_conv_case.py
 t debug_enet_blocks  python tools/debug_enet_blocks.py
