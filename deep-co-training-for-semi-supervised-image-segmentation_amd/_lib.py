@@ -168,6 +168,10 @@ SIGNATURES = {
     "dct_kl_logits_bwd": (_i, [_P, _P, _i64, _i, _f, _P, _f, _P, _i, _P]),
     "dct_argmax": (_i, [_P, _P, _i64, _i, _P]),
     "dct_fgsm_step": (_i, [_P, _P, _f, _P, _P, _i64, _P]),
+    "dct_vat_workspace_bytes": (_sz, [_i64, _i64]),
+    "dct_vat_noise": (_i, [_P, _i64, _i64, _u64, _P, _u64, _P, _sz, _P]),
+    "dct_vat_sumsq": (_i, [_P, _i64, _i64, _P, _sz, _P]),
+    "dct_vat_perturb": (_i, [_P, _P, C.c_double, _i64, _i64, _P, _sz, _P, _P, _P, _P, _P]),
     "dct_adam_flat": (_i, [_P, _P, _P, _P, _i64, _f, _f, C.c_double, C.c_double, _f, _f, _f, _P, _P]),
     "dct_adam_flat_dev": (_i, [_P, _P, _P, _P, _i64, _P, _P, C.c_double, C.c_double, _f, _f, _f, _P, _P]),
     "dct_grad_sumsq_workspace_bytes": (_sz, [_i64]),

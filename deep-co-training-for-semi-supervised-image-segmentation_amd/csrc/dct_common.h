@@ -78,6 +78,25 @@ __device__ __forceinline__ float block_sum_256(float v, float* smem4) {
   return smem4[0] + smem4[1] + smem4[2] + smem4[3];
 }
 
+// ---- Philox4x32-10 (Salmon et al., SC'11): key = the 64-bit seed, counter = (ctr lo, ctr hi, 0, 0).  The dropout masks (pointwise.hip) and the
+// VAT noise (vat.hip) draw from it.
+__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned long long ctr, unsigned out[4]) {
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0u, c3 = 0u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
+    const unsigned n1 = (unsigned)p1;
+    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    const unsigned n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // ---- streaming stores (round 5) -------------------------------------------------------------------------------------------------
 // A 16-byte store of an activation / gradient tensor that nobody reads before hundreds of megabytes of other traffic have gone through
 // the memory-side cache.  tools/probe_store_bw: with the default policy a 132 MB fill whose lines are not resident runs at 3.1 TB/s

@@ -829,22 +829,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_codes_skip_kernel(const unsig
 }
 
 // ---- dropout (Philox4x32-10) ---------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned long long ctr, unsigned out[4]) {
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0u, c3 = 0u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-    const unsigned n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    const unsigned n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// (philox4x32_10: dct_common.h -- the VAT noise of csrc/vat.hip draws from the same generator)
 // thread per 4 consecutive channels of a pixel
 // calls (nullable): device-resident call counter in TWO 64-bit words that successive launches use in turn.  This launch reads calls[parity] = n, is
 // call number n + 1 -- the Philox offset is that << 40 (what the host passes as `offset` otherwise), so a captured HIP graph draws a fresh mask on

@@ -941,6 +941,55 @@ def fgsm_step(x, g, eps, want_noise=True):
     return xa, noise
 
 
+def _vat_shape(t):
+    assert t.dim() >= 2 and t.dtype == torch.float32 and t.is_contiguous(), "dct_amd: VAT launches take dense fp32 [N, ...] tensors"
+    return int(t.shape[0]), t.numel() // int(t.shape[0])
+
+
+def vat_workspace(N, per, device):
+    """The float64 block partials of N samples of ``per`` elements (dct_vat_workspace_bytes): written by vat_noise / vat_sumsq, read by the
+    vat_perturb launches behind them.  A tensor of its own, not the per-stream scratch: it lives across other launches."""
+    nbytes = _lib.load().dct_vat_workspace_bytes(int(N), int(per))
+    if nbytes == 0:
+        raise ValueError(f"dct_amd: VAT over {N} samples of {per} elements is out of range")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def vat_noise(d, seed, calls=None, offset=0, workspace=None):
+    """d (dense fp32 [N, ...], overwritten) = Gaussian noise of draw number ``calls[0] + 1`` (``calls``: int64[1] on the device, only read:
+    the graph-replayable form) or ``offset``, and every sample's sum-of-squares partials into ``workspace``.  -> (d, workspace)"""
+    N, per = _vat_shape(d)
+    ws = workspace if workspace is not None else vat_workspace(N, per, d.device)
+    if calls is not None:
+        assert calls.dtype == torch.int64 and calls.numel() >= 1 and calls.device == d.device
+    call("dct_vat_noise", ptr(d), N, per, int(seed) & ((1 << 64) - 1), ptr(calls), int(offset), ptr(ws), ws.numel() * 8, stream())
+    return d, ws
+
+
+def vat_sumsq(g, workspace=None):
+    """Every sample's sum-of-squares partials of g (dense fp32 [N, ...]) into ``workspace``.  -> workspace"""
+    N, per = _vat_shape(g)
+    ws = workspace if workspace is not None else vat_workspace(N, per, g.device)
+    call("dct_vat_sumsq", ptr(g), N, per, ptr(ws), ws.numel() * 8, stream())
+    return ws
+
+
+def vat_perturb(x, d, radius, workspace, want_r=True, want_norms=False, calls_advance=None):
+    """x + (radius / ||d||_n) * d per sample n, with the norms from ``workspace`` (the partials of d: vat_noise / vat_sumsq); a sample whose
+    norm is 0 or not finite comes back unchanged.  ``calls_advance`` (int64[1] on the device): the launch adds 1 to it -- for the first
+    perturb launch behind a vat_noise launch that read it.  -> (x_out, r or None, float64 norms [N] or None)"""
+    N, per = _vat_shape(x)
+    assert _vat_shape(d) == (N, per) and d.device == x.device
+    xo = torch.empty_like(x)
+    r = torch.empty_like(x) if want_r else None
+    norms = torch.empty(N, dtype=torch.float64, device=x.device) if want_norms else None
+    if calls_advance is not None:
+        assert calls_advance.dtype == torch.int64 and calls_advance.numel() >= 1 and calls_advance.device == x.device
+    call("dct_vat_perturb", ptr(x), ptr(d), float(radius), N, per, ptr(workspace), workspace.numel() * 8, ptr(xo), ptr(r), ptr(norms),
+         ptr(calls_advance), stream())
+    return xo, r, norms
+
+
 def adam_flat(p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, bf16_shadow=None, grad_scale=1.0):
     call("dct_adam_flat", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(step_size), float(bc2_sqrt), float(beta1),
          float(beta2), float(eps), float(weight_decay), float(grad_scale), ptr(bf16_shadow), stream())

@@ -36,7 +36,7 @@ from .. import scheduler
 from ..metrics import AgreementMeter, AverageValueMeter, CalibrationMeter, DiceMeter, HausdorffMeter, keep_largest_component
 from ..models import Segmentator
 from ..utils import iterator_, map_, dict_merge, tqdm_
-from ..utils.AEGenerator import FSGMGenerator
+from ..utils.AEGenerator import FSGMGenerator, VATGenerator, VATNoise
 from . import step_route
 from .step_route import NetFacts, StepFacts, plan_execution, plan_step
 from .stream_sched import EagerSchedule, StreamDealer, own_stream
@@ -221,7 +221,10 @@ class CoTrainer(Trainer):
             **{k: v for k, v in cot_scheduler_dict.items() if k != 'name'})
         self.adv_scheduler = getattr(scheduler, adv_scheduler_dict['name'])(
             **{k: v for k, v in adv_scheduler_dict.items() if k != 'name'})
+        # generator: 'fgsm' (default; eplision = the per-pixel step) | 'vat' (eplision = the L2 radius per image, xi, ip): validated where
+        # the step reads it (step_route.adv_settings)
         self.adv_training_dict = adv_training_dict
+        self.vat_noise = None               # the 'vat' generator's VATNoise (seed + draw counter); made at the first VAT step unless set
 
         if checkpoint is not None:
             self._load_checkpoint(checkpoint)
@@ -333,7 +336,7 @@ class CoTrainer(Trainer):
             gpu=gpu, fused_criteria=fused_criteria, ddp=self.grad_sync is not None,
             # replay needs every per-step scalar on the device: only the fused Adam keeps its step count / lr there
             optimizers_graphable=all(hasattr(s.optimizer, "refresh_lr") and hasattr(s.optimizer, "_steps") for s in self.segmentators),
-            group_max=self._group_max or 0)
+            group_max=self._group_max or 0, adv_generator=str((self.adv_training_dict or {}).get('generator', 'fgsm')))
 
     def _fused_ok(self) -> bool:
         return step_route.fused(self._step_facts())
@@ -364,6 +367,8 @@ class CoTrainer(Trainer):
             self.grad_sync.prepare()        # (a grad_sync attached after construction) before anything is captured
         if train_adv and adv_choice is None:
             adv_choice = self._draw_adv_choice()
+        if train_adv and step_route.adv_settings(self.adv_training_dict)[0] == 'vat':      # (validates the dictionary: ValueError)
+            self._vat_noise().state(self.device)    # the noise object and its device word exist before anything is routed or captured
         # the kernels take raw pointers: images fp32, labels int64, both dense (a loader may hand over uint8 labels or
         # half images; the reference's modules would cast or raise, the C ABI would reinterpret the bytes)
         def _img(t):
@@ -542,6 +547,44 @@ class CoTrainer(Trainer):
         x_adv, noise = K.fgsm_step(x.detach().contiguous(), gx.contiguous(), eps)
         return x_adv, noise, lp, tape
 
+    def _vat_noise(self) -> VATNoise:
+        """The 'vat' generator's noise object (``self.vat_noise``; made on first use, the rank mixed into its seed under data parallelism)."""
+        if self.vat_noise is None:
+            self.vat_noise = VATNoise()
+        if self.grad_sync is not None:
+            self.vat_noise.mix_rank(int(self.grad_sync.rank))
+        return self.vat_noise
+
+    def _vat_fused(self, ctx, net, x):
+        """VATGenerator (utils/AEGenerator.py; the rule: include/dct.h "VAT") on the fused kernels: the clean pass, one noise launch, then
+        ``ip`` times [perturb by xi, forward, KL logit gradient, backward to the input only, norms], and the perturbation by eplision:
+        1 + ip training-mode passes of ``net`` and ip input-gradient passes.  Only the direction of the input gradient is used, so the KL
+        logit gradient carries the loss scale (fp16 nets) and never lambda_adv: ``lam_dev`` is not read here.  Returns what _fgsm_fused
+        returns (the tape of the clean pass is not back-propagated)."""
+        from .. import hip_ops as K
+        _, xi, eps, ip = step_route.adv_settings(self.adv_training_dict)
+        noise = self._vat_noise()
+        lp, tape = net.plan_forward(x, True)
+        x = x.detach().contiguous()
+        d, ws = noise.draw(x)
+        advance = noise.state(x.device)             # the first perturb launch behind the noise launch moves the counter on
+        for _ in range(ip):
+            x_probe, _, _ = K.vat_perturb(x, d, xi, ws, want_r=False, calls_advance=advance)
+            advance = None
+            lp_probe, probe_tape = net.plan_forward(x_probe, True)
+            dl = K.kl_logits_bwd(lp_probe, lp, self.C, torch.empty_like(lp_probe), gmul=ctx.loss_scale)
+            d = net.plan_backward(probe_tape, dl, need_dx=True, need_dw=False).contiguous()
+            K.vat_sumsq(d, ws)
+        noise.advanced()
+        x_adv, r, _ = K.vat_perturb(x, d, eps, ws)
+        return x_adv, r, lp, tape
+
+    def _adv_examples_fused(self, ctx, net, x, gt):
+        """The adversarial batch of the sequential step, from the generator ``adv_training_dict`` names."""
+        if step_route.adv_settings(self.adv_training_dict)[0] == 'vat':
+            return self._vat_fused(ctx, net, x)
+        return self._fgsm_fused(ctx, net, x, gt)
+
     # Diagnostic (tools/phase_stamps.py): with ``self.phase_stamps`` = a zeroed int64 device tensor [S, 4, 1 + PHASE_RING], one-thread stamp
     # launches date the phases of the step on each model's stream (site k = 0 forward starts, 1 forward + loss done, 2 backward done,
     # 3 optimizer done) into a ring per site.  They are kernel nodes: a captured step replays them, so pipelined replays leave a timeline.
@@ -669,6 +712,8 @@ class CoTrainer(Trainer):
                            rule if focal else None, rule if topk else None, tversky=rule if tversky else None,
                            spl=cons.launch_args() if soft else None, mse=cons.launch_args() if mse else None)
         streams = self._streams() if route.model_streams else None
+        if train_adv and route.kind != "sequential" and step_route.adv_settings(self.adv_training_dict)[0] != 'fgsm':
+            raise RuntimeError(f"dct_amd: the {route.kind} layout is scheduled around FGSM; the planner routes other generators sequentially")
         if route.kind in ("wide", "wide_grouped"):
             return self._run_step_wide(ctx, lab, unl, train_adv, adv_choice, nets)
         if route.kind == "adv_chain":
@@ -762,7 +807,7 @@ class CoTrainer(Trainer):
             img_b, gt_b = lab[b]
             with on(b):
                 x = torch.cat((img_b, unl[0]), dim=0)
-                x_adv, noise, lp_real, _ = self._fgsm_fused(ctx, nets[b], x, gt_b)
+                x_adv, noise, lp_real, _ = self._adv_examples_fused(ctx, nets[b], x, gt_b)
             # (queued after the FGSM chain and its completion mark, and before model a's wait for that mark: streams that share
             # a hardware queue run in issue order -- the critical chain goes first, its mark must not land behind another
             # stream's segment, and nothing may be parked behind model a's blocked wait)
@@ -1255,12 +1300,18 @@ class CoTrainer(Trainer):
 
     # ------------------------------------------------------------------------------ adversarial term
     def _adv_from_batches(self, segmentators: Sequence[Segmentator], lab_b: Tuple[Tensor, Tensor], unl_img: Tensor,
-                          eplision: float = 0.05) -> Tensor:
+                          eplision: Optional[float] = None, generator: str = 'fgsm', xi: Optional[float] = None,
+                          ip: Optional[int] = None) -> Tensor:
         """KL( a(x_adv) || b(x).detach() ) with x = cat(labeled batch of b, unlabeled batch), x_adv from
-        FGSM on b (:371-392,440-442)."""
+        FGSM on b (:371-392,440-442), or from VAT on b with ``generator='vat'`` (step_route.adv_settings holds the defaults)."""
         assert segmentators.__len__() == 2, 'only implemented for 2 segmentators'
         img_2, gt_2 = lab_b
-        fsgm = self._fsgm_cls(segmentators[1].torchnet, eplision=eplision)
+        given = dict(generator=generator, eplision=eplision, xi=xi, ip=ip)
+        generator, xi, eplision, ip = step_route.adv_settings({k: v for k, v in given.items() if v is not None})
+        if generator == 'vat':
+            fsgm = self._vat_cls(segmentators[1].torchnet, xi=xi, eplision=eplision, ip=ip, noise=self._vat_noise())
+        else:
+            fsgm = self._fsgm_cls(segmentators[1].torchnet, eplision=eplision)
         img_adv, noise, real_preds = fsgm(torch.cat((img_2, unl_img), dim=0), gt=gt_2, criterion=self.criterions['sup'])
         adv_preds = segmentators[0].predict(img_adv, logit=False)
         kl = self._kl_cls(reduce=True)
@@ -1268,6 +1319,7 @@ class CoTrainer(Trainer):
         return sum(adv_losses) / adv_losses.__len__()
 
     _fsgm_cls = FSGMGenerator
+    _vat_cls = VATGenerator
 
     @property
     def _kl_cls(self):

@@ -38,7 +38,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .step_route import plan_step
+from .step_route import adv_settings, plan_step
 
 
 def _is_refused_capture(err: BaseException) -> bool:
@@ -75,6 +75,14 @@ class StepGraphCache(object):
         tr = self.tr
         sig: List = [execution, route, bool(train_jsd), bool(train_adv), tuple(adv_choice) if adv_choice is not None else None,
                      lam[0] != 0.0, lam[1] != 0.0]
+        # the adversarial block: (generator, xi, eplision, ip) are launch arguments and a launch count, so another value is another
+        # capture; VAT's seed and the address of its draw counter are launch arguments too (the counter's value is read on the device)
+        if train_adv:
+            adv = adv_settings(tr.adv_training_dict)
+            noise = getattr(tr, "vat_noise", None) if adv[0] == "vat" else None
+            sig.append(adv + ((noise.seed, noise.state(tr.device).data_ptr()) if noise is not None else ()))
+        else:
+            sig.append(None)
         for img, gt in lab:
             sig.append((tuple(img.shape), img.dtype, tuple(gt.shape), gt.dtype))
         if unl is not None:
@@ -124,6 +132,8 @@ class StepGraphCache(object):
             out.append((seg.optimizer, "_steps"))
             if hasattr(seg.torchnet, "_drop_calls"):
                 out.append((seg.torchnet, "_drop_calls"))
+        if getattr(self.tr, "vat_noise", None) is not None:     # (made before a VAT step is routed: CoTrainer._run_step)
+            out.append((self.tr.vat_noise, "_calls"))
         return out
 
     # ------------------------------------------------------------------------------ run

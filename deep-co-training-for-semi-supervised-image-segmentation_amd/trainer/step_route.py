@@ -53,6 +53,7 @@ class StepFacts:
     ddp: bool = False
     optimizers_graphable: bool = False
     group_max: int = 0                          # members the library packs into one grouped launch
+    adv_generator: str = "fgsm"                 # who makes the adversarial examples: fgsm | vat (adv_settings)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -73,12 +74,43 @@ class StepRoute:
     loss_scale: float = 1.0
 
 
+ADV_GENERATORS = ("fgsm", "vat")
+
+
+def adv_settings(adv_training_dict) -> Tuple[str, Optional[float], float, Optional[int]]:
+    """``CoTrainer.adv_training_dict`` as (generator, xi, eplision, ip), validated: what the adversarial block of a step is issued
+    with, and part of a captured step's signature.  'fgsm' (the default): eplision is the per-pixel step (0.05), xi and ip are None.
+    'vat' (utils/AEGenerator.py::VATGenerator): eplision is the L2 radius per image (10), xi the probe radius (10), ip the number of
+    power iterations (1).  ValueError for an unknown generator and for an xi, eplision or ip that is not positive."""
+    d = dict(adv_training_dict or {})
+    gen = d.get("generator", "fgsm")
+    if gen not in ADV_GENERATORS:
+        raise ValueError(f"dct_amd: adv_training_dict['generator'] is {gen!r}; known generators: {', '.join(ADV_GENERATORS)}")
+    vat = gen == "vat"
+
+    def positive(name, default):
+        v = float(d.get(name, default))
+        if not (v > 0.0) or v == float("inf"):
+            raise ValueError(f"dct_amd: adv_training_dict[{name!r}] must be positive and finite, got {d.get(name)!r}")
+        return v
+    eps = positive("eplision", 10.0 if vat else 0.05)
+    if not vat:
+        return gen, None, eps, None
+    xi = positive("xi", 10.0)
+    ip = d.get("ip", 1)
+    if isinstance(ip, bool) or int(ip) != ip or int(ip) < 1:
+        raise ValueError(f"dct_amd: adv_training_dict['ip'] must be a whole number >= 1, got {ip!r}")
+    return gen, xi, eps, int(ip)
+
+
 def fused(facts: StepFacts) -> bool:
     return bool(facts.gpu and facts.fused_criteria and all(n.plan_net for n in facts.nets) and facts.S <= MAX_FUSED_MODELS)
 
 
 def adv_chain_eligible(plan, facts: StepFacts) -> bool:
     c = facts.adv_choice
+    if facts.train_adv and facts.adv_generator != "fgsm":
+        return False            # the layout is scheduled around FGSM's single forward pass and its tape; VAT has 1 + ip passes on model b
     return bool(plan.adv_chain_layout and facts.train_jsd and facts.train_adv and facts.unlabeled and c is not None and
                 facts.S == 2 and c[0] != c[1] and plan.batch_lab_unlab and plan.model_streams and not facts.ddp and
                 all(n.batch_independent and n.supports_grad_overwrite and not n.dropout_masks_set for n in facts.nets))
@@ -143,7 +175,10 @@ def plan_step(plan, facts: StepFacts, mode: str, four_queues: Callable[[], bool]
     common = dict(adv_chain_eligible=eligible, joint_pass=joint, model_streams=model_streams, defer_optimizer=two_graphs,
                   loss_scale=_loss_scale(plan, facts))
 
-    if (plan.wide_forward and pass_on and jsd and not joint and
+    # (the four-queue layouts give the adversarial chain's queue to FGSM's one forward + input-gradient pass: another generator stays sequential)
+    fgsm = not facts.train_adv or facts.adv_generator == "fgsm"
+
+    if (fgsm and plan.wide_forward and pass_on and jsd and not joint and
             all(n.supports_deferred_running_stats and n.supports_pass_streams for n in nets) and ready and four_queues()):
         grouped = bool(plan.group_passes and all(n.supports_pass_groups for n in nets) and facts.labeled_shapes_equal and S <= facts.group_max)
         return StepRoute(kind="wide_grouped" if grouped else "wide", pass_streams=(True,) * S, early_backward=off,

@@ -641,6 +641,51 @@ int dct_argmax(const float* x, int64_t* cls, int64_t pixels, int C, dct_stream s
 int dct_fgsm_step(const float* x, const float* g, float eps, float* x_adv, float* noise, int64_t n,
                   dct_stream stream);
 
+/* ---- VAT: virtual adversarial examples (Miyato et al., "Virtual Adversarial Training"; the reference's VATGenerator,
+ * generalframework/utils/AEGenerator.py:54-119, which is broken as written -- SURVEY row 4 -- so the rule is restated here) ----
+ * The label-free generator of the adversarial term: the direction in which the prediction itself moves fastest, measured by the
+ * KL(clean || perturbed) the adversarial term already uses, scaled to an L2 ball per image.
+ *
+ * x: fp32 [N, Cin, H, W], per = Cin * H * W, f: a network that returns logits, xi > 0, eps > 0, ip >= 1.
+ *   1. l = f(x), the clean logits, held constant; softmax(l) is the target of every KL below and is returned too.
+ *   2. d = a direction the caller supplies, or else Gaussian noise: flat element e of the [N * per] tensor takes word e & 3 of
+ *      philox4x32_10(seed, (call << 40) + (e >> 2)) (the dropout kernels' generator).  Words (r0, r1) and (r2, r3) give two normals
+ *      each by Box-Muller: u1 = ((ra >> 8) + 1) * 2^-24 in (0, 1], u2 = (rb >> 8) * 2^-24 in [0, 1), rho = sqrtf(-2 logf(u1)),
+ *      even element rho * cosf(2 pi u2), odd element rho * sinf(2 pi u2); the precise functions, never the fast intrinsics.
+ *   3. ip times:  u = d / ||d||_n;  l^ = f(x + xi * u);  d = dD / d(x + xi * u), D = the mean over pixels of
+ *      KL(softmax(l) || softmax(l^)): dct_kl_logits_fwd / dct_kl_logits_bwd with p = l^, y = l.
+ *   4. r = eps * d / ||d||_n,  x_adv = x + r.  The result is (x_adv, r, softmax(l)).
+ * ||d||_n is the L2 norm of sample n over its per elements; the sum of squares is taken in float64 in an order fixed by (N, per) alone.
+ * There is NO additive epsilon: at xi = 1e-6 a three-channel toy net gave gradient norms of 5e-9, which the usual + 1e-8 would shrink
+ * threefold.  A sample whose norm is 0 or not finite gets a zero perturbation: x_adv = x exactly, r = 0.
+ * Only the direction of d is used in step 3, so the KL logit gradient there carries the step's loss scale and never lambda_adv (which
+ * may be 0).
+ * Every forward pass of the generator is an ordinary training-mode pass of f, as FGSM's is: dropout draws a fresh mask, BatchNorm uses
+ * the batch statistics and updates the running statistics.
+ *
+ * The launches.  A sample is cut into dct_vat_workspace_bytes(N, per) / (8 N) blocks, a function of per alone (at most 64); the
+ * workspace holds one float64 partial sum of squares per block.  Thread, lane, wave and block order are fixed, so the same tensor gives
+ * the same bits, and dct_vat_noise leaves the partials dct_vat_sumsq would leave for the d it wrote.  16-byte accesses where a sample's
+ * first element is 16-byte aligned (an odd per misaligns every second sample), scalar ones there and on the tail.
+ *   dct_vat_noise:   d = the noise of rule 2 and its partials in one pass.  call = calls ? calls[0] + 1 : offset; the launch only READS
+ *                    calls[0] (a 64-bit word on the device), so a captured step draws fresh noise on every replay once the word moves.
+ *   dct_vat_sumsq:   the partials of g (the input gradient of step 3).
+ *   dct_vat_perturb: every block folds its sample's partials in the one fixed order -- all blocks of a sample get the same scale bit
+ *                    for bit, no finalize launch between -- and writes x_out = x + s * d, r_out = s * d (nullable), s =
+ *                    (float)(radius / norm), product and sum rounded separately; norms_out (nullable): float64 [N].  calls_advance
+ *                    (nullable): thread 0 of block 0 stores calls_advance[0] + 1; no block of this launch reads that word.  Pass it to
+ *                    the first perturb launch behind a noise launch only.  (The dropout counter's two-word scheme needs an even number
+ *                    of launches per captured step; a step holds ONE noise launch.)
+ * DCT_ERR_BAD_ARG: a null d / g / x / x_out / workspace, N or per < 1, more than 2^42 elements, a pointer off its type's alignment, a
+ * radius that is not positive and finite; DCT_ERR_WORKSPACE: less than dct_vat_workspace_bytes(N, per) (0 for a shape out of range). */
+size_t dct_vat_workspace_bytes(int64_t N, int64_t per);
+int dct_vat_noise(float* d, int64_t N, int64_t per, uint64_t seed, const uint64_t* calls, uint64_t offset, void* workspace,
+                  size_t workspace_bytes, dct_stream stream);
+int dct_vat_sumsq(const float* g, int64_t N, int64_t per, void* workspace, size_t workspace_bytes, dct_stream stream);
+int dct_vat_perturb(const float* x, const float* d, double radius, int64_t N, int64_t per, const void* workspace,
+                    size_t workspace_bytes, float* x_out, float* r_out, double* norms_out, uint64_t* calls_advance,
+                    dct_stream stream);
+
 /* ---- K12: Adam over one flat fp32 buffer (torch.optim.Adam, segmentators.py:41; step :248) --
  * g' = grad_scale*g + wd*p; m = m + (g'-m)*(1-b1); v = v*b2 + (1-b2)*g'^2;   (grad_scale: 1, or the inverse of the
  * power-of-two loss-gradient scale of an fp16 step)

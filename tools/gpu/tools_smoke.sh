@@ -16,6 +16,7 @@ t bench_tversky      python tools/bench_tversky.py
 t bench_pseudo_label python tools/bench_pseudo_label.py
 t bench_soft_label   python tools/bench_soft_label.py
 t bench_mse_consistency python tools/bench_mse_consistency.py
+t bench_vat          python tools/bench_vat.py --reps 5
 t bench_pointwise    python tools/bench_pointwise.py
 t debug_conv_case    python tools/debug_conv_case.py
 t debug_enet_blocks  python tools/debug_enet_blocks.py
