@@ -152,6 +152,8 @@ extern int g_dct_skip_families;
 enum { DCT_DIAG_IGEMM_SPLIT_MAX_TILES = 1002, DCT_DIAG_IGEMM_SPLIT_MIN_KITERS = 1003,      // planner studies (tools/bench_conv.py --ab-knob)
        DCT_DIAG_IGEMM_POOL = 1005,           // 0: a requested pooling always runs as its own launch behind the conv
        DCT_DIAG_IGEMM_HALO_TALL_MIN_BLOCKS = 1009,   // block threshold of the 16 x 16 shared-halo patches (its sweep)
+       DCT_DIAG_IGEMM_PACKED_MIN_SLICES = 1010,      // fewest channel slices of a packed-rows block (default 4) ...
+       DCT_DIAG_IGEMM_PACKED_SPLITS = 1011,          // ... and >= 1: its channel-slice splits, forced (tests/test_conv_packed_ring_gpu.py)
        DCT_DIAG_STEM_DGRAD_MFMA = 1008,      // 0: the stem's data gradient on the vector-ALU kernel for every shape
        DCT_DIAG_SKIP_FAMILIES = 1100 };      // mask of the DCT_FAM_* below
 enum { DCT_FAM_IGEMM2 = 1, DCT_FAM_IGEMM3M = 2, DCT_FAM_IGEMM3P = 4, DCT_FAM_WGRAD2 = 8, DCT_FAM_WGRAD3 = 16, DCT_FAM_FOLDS = 32,

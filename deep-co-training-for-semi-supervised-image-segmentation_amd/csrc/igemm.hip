@@ -975,8 +975,13 @@ __global__ __launch_bounds__(NWM * NWN * 64) __attribute__((amdgpu_waves_per_eu(
 // the step).  Halo and weight pieces are buffer loads to LDS with constant lane offsets (out-of-image halo lanes hold an offset the
 // descriptor rejects and stage zeros), the step's offsets are 32-bit scalars advanced by adds, tap offsets advance without a
 // division.  Same LDS image, same reads, same MFMA order: bit-identical.
-template <int BN, int NWM, int NWN, bool LEAN>
+// RING (knob DCT_TUNE_IGEMM_PACKED_RING): the LEAN loop on ONE halo stage and THREE weight stages (72 KiB).  The weight stage
+// of round k + 2 is issued in round k behind a raw s_barrier, and a counted s_waitcnt vmcnt lets the stage of round k + 1 stay in flight
+// across that barrier: a weight piece has two rounds to arrive instead of one.  The halo of the next channel slice is staged in the
+// open, between two barriers, behind tap 8 (as igemm3m_tall_kernel does).  Same LDS images, same reads, same MFMA order: bit-identical.
+template <int BN, int NWM, int NWN, bool LEAN, bool RING = false>
 __global__ __launch_bounds__(NWM * NWN * 64) void igemm3p_kernel(IgemmParams p, int PR, int tiles_per_img, int chunks_per_split) {
+  static_assert(!RING || LEAN, "the weight ring is a form of the lean loop");
   constexpr int NW = NWM * NWN;
   constexpr int BM = 128, APIECES = 24, A_BYTES = APIECES * 1024;                  // <= 192 halo rows of 128 B
   constexpr int B_BYTES = BN * 128, BPIECES = BN / 8;
@@ -1058,7 +1063,91 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3p_kernel(IgemmParams p, 
 
   const int nch = p.Cin / 64;
   const int cbeg = bzi * chunks_per_split, cend = min(nch, cbeg + chunks_per_split);
-  if constexpr (LEAN) {
+  if constexpr (RING) {
+    static_assert(A_BYTES + 3 * B_BYTES <= 80 * 1024 && A_BYTES + 3 * B_BYTES >= BM * BN * 4 + 2 * BM * 4, "ring stages / epilogue tile against 80 KiB");
+    // LDS byte addresses of this wave's first halo piece and of its first weight piece in ring slot 0
+    const unsigned ldsA = smem_l + wave * 1024, ldsB = smem_l + A_BYTES + wave * 1024;
+    auto stA = [&](unsigned soff) {
+#pragma unroll
+      for (int i = 0; i < NPA; ++i) buf_lds16(rsX, ldsA + i * NW * 1024, aoffb[i], soff);
+    };
+    auto stB = [&](unsigned slot_off, unsigned soff) {
+#pragma unroll
+      for (int i = 0; i < NPB; ++i) buf_lds16(rsW, ldsB + slot_off + i * NW * 1024, woffb[i], soff);
+    };
+    const unsigned cin2 = (unsigned)p.Cin * 2;
+    unsigned xo = (unsigned)cbeg * 128;                         // byte offset of the current channel slice in a pixel
+    unsigned wo = xo;                                           // (tap * Cin + c * 64) * 2 of the NEXT weight stage to fetch ...
+    int ft = 0;                                                 // ... and its tap
+    auto next_stage = [&]() {                                   // the following tap of that slice, or tap 0 of the slice behind it
+#ifndef DCT_V3P_FREEZE_W
+      if (ft < 8) wo += cin2; else wo += 128u - 8u * cin2;
+#endif
+      ft = ft < 8 ? ft + 1 : 0;
+    };
+    const int nsteps = 9 * (cend - cbeg);                       // >= 9: every split holds a slice
+    stA(xo);
+    stB(0u, wo); next_stage();
+    stB((unsigned)B_BYTES, wo); next_stage();
+    const unsigned Wl0 = smem_l + A_BYTES + (wn * WTN + l31) * 128 + ((half ^ aswz) * 16);
+    const bool wave_live = wm * 32 < PR * p.Wo;
+    unsigned rs = 0, fs = 2u * B_BYTES;                         // byte offsets of the ring slots round k reads / fills: (k % 3, (k + 2) % 3) * B_BYTES
+    int t = 0, tapoff = 0, scol = 0;                            // tap index, r * pitch + s, s
+    bool halo_issued = false;                                   // the halo of this round's slice went out behind the last round
+#pragma unroll 1
+    for (int k = 0; k < nsteps; ++k) {
+      // this wave's pieces of stage k have landed (those of stage k + 1, the youngest, may stay in flight; a halo issued behind them may not)
+      if (k + 1 < nsteps && !halo_issued) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPB) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();                             // ... and everybody's; the readers of round k - 1 are past their reads
+      __builtin_amdgcn_sched_barrier(0);
+      if (k + 2 < nsteps) { stB(fs, wo); next_stage(); }
+      __builtin_amdgcn_sched_barrier(0);
+      if (wave_live) {
+      const int rho = rho0 + tapoff;
+      const unsigned Wl = Wl0 + rs;
+      const unsigned Xl = smem_l + rho * 128 + ((half ^ ((rho >> 1) & 7)) * 16);
+      bf16x8 a[2][TN], b[2];
+      auto issue = [&](int set, int kk) {
+#pragma unroll
+        for (int i = 0; i < TN; ++i) rd128((Wl + i * 32 * 128) ^ (kk * 32), a[set][i]);
+        rd128(Xl ^ (kk * 32), b[set]);
+      };
+      issue(0, 0);
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const int set = kk & 1;
+        if (kk + 1 < 4) { issue(set ^ 1, kk + 1); lgkm_wait3<TN + 1>(); } else { lgkm_wait3<0>(); }
+#pragma unroll
+        for (int i = 0; i < TN; ++i) touch8(a[set][i]);
+        touch8(b[set]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < TN; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[set][i], b[set], acc[i], 0, 0, 0);
+      }
+      }
+      fs = rs;
+      rs = rs == 2u * B_BYTES ? 0u : rs + (unsigned)B_BYTES;
+      ++t; ++scol;
+      const bool w3 = scol == 3, w9 = t == 9;
+      tapoff += w3 ? pitch - 2 : 1;
+      scol = w3 ? 0 : scol;
+      tapoff = w9 ? 0 : tapoff;
+      t = w9 ? 0 : t;
+      xo += w9 ? 128u : 0u;
+      // slice change: every wave is past its last read of the halo stage (lgkmcnt(0) in front of the round's last MFMAs) once it is
+      // past this barrier; the next slice's halo then goes out in the open and the top of the next round waits for all of it
+      halo_issued = w9 && k + 1 < nsteps;
+      if (halo_issued) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        stA(xo);
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // (nothing is in flight: the last round waited for everything)
+    __syncthreads();                                            // the epilogue tile overwrites the stages
+  } else if constexpr (LEAN) {
     // LDS byte addresses of this wave's first halo / weight piece in stage 0 (pieces of one kind are NW KiB apart)
     const unsigned ldsA = smem_l + wave * 1024, ldsB = smem_l + 2 * A_BYTES + wave * 1024;
     auto stA = [&](int ab_, unsigned soff) {
@@ -1087,7 +1176,10 @@ __global__ __launch_bounds__(NWM * NWN * 64) void igemm3p_kernel(IgemmParams p, 
     for (int k = 0; k < nsteps; ++k) {
       // next weight stage: the following tap of this slice, or tap 0 of the next slice
       if (k + 1 < nsteps) {
+#ifndef DCT_V3P_FREEZE_W      // diagnostic build (`make BUILD=build_freeze OUT=../libdct_hip_freeze.so EXTRA=-DDCT_V3P_FREEZE_W`, selected by DCT_LIB_PATH
+                              // under tools/bench_conv.py): every round re-reads the block's first, L2-hot weight stage.  WRONG results: timing only
         if (t < 8) wo += cin2; else wo += 128u - 8u * cin2;
+#endif
         stB(bb ^ 1, wo);
       }
       if (t == 0 && k + 9 < nsteps) stA(ab ^ 1, xo + 128u);
@@ -1402,7 +1494,7 @@ static void launch_v3_tall(const IgemmParams& p, int tiles_x, int tiles_y, int i
 }
 
 // Packed-rows shared-halo kernel (igemm3p_kernel) for small images: geometry and split over channel slices.
-struct PlanP { int use, PR, tiles_per_img, splits, cps; };
+struct PlanP { int use, PR, tiles_per_img, splits, cps, ring; };
 int g_tune_igemm_packed = 1;     // packed-rows shared-halo kernel for the deep levels (0: they stay on the per-tap kernel).  Round 1 had it
                                  // level on the step because every layer under 400 blocks was split over channel slices (fp32 slabs);
                                  // with the split only under 100 blocks -- the two model streams supply the parallelism -- it is
@@ -1415,8 +1507,16 @@ int g_tune_igemm_packed_fill = 50;     // percent: least fill of the packed 128-
                                        // captured cfg2 step 60 / 50 / 40 are 1.0 / 1.25 / 1.2 % ahead of 76 (two alternating rounds on one box,
                                        // profiles/r05_knob_sweep.txt): the centre's second convolution (81-pixel images: 63 %), enc3a / enc2a / enc2b and
                                        // enc3b's data gradient (69-75 %) leave the per-tap kernel, which re-reads its input once per tap
+int g_tune_igemm_packed_min_slices = 4;  // diagnostic (1010): fewest channel slices a packed-rows block keeps (the tests of the loop's prologue take it to 1)
+int g_tune_igemm_packed_splits = -1;     // diagnostic (1011): >= 1 forces the channel-slice splits of a packed-rows layer (at most one per slice)
+int g_tune_igemm_packed_ring = 1;        // weight ring of the lean loop (igemm3p_kernel RING): 0 = two halo and two weight stages, 1 = every packed-rows launch.
+                                         // In isolation the ring LOSES 0-10 % per layer (its halo re-stage is exposed; profiles/ring3p_conv_per_layer.txt) and a build
+                                         // whose rounds all re-read one L2-hot weight stage is level with the two-stage loop (back to back a layer's weights stay in
+                                         // the caches: no arrival wait to hide); in the step, where they are cold, igemm3p is -6.0 % on a single stream (44.7 -> 42.0 us
+                                         // per launch, profiles/ring3p_cfg2_single_stream_kernel_stats.txt) and the captured cfg2 step -2.1 % (4.7843 -> 4.6841 ms, six
+                                         // alternating fresh processes per arm on one box, margin 0.0663 ms; knob 0 level with the parent: profiles/ring3p_step_ab.txt)
 static PlanP make_plan_p(const dct_view* x, const dct_view* y, const dct_conv_desc* d, int dtype, int N) {
-  PlanP pp = {0, 0, 0, 1, 0};
+  PlanP pp = {0, 0, 0, 1, 0, 0};
   if (!g_tune_igemm_halo || !g_tune_igemm_packed || dtype != DCT_BF16 || d->R != 3 || d->S != 3 || d->stride != 1 || d->dil != 1 ||
       d->scatter2x2 || x->c % 64 || N % 128 || y->w > 126)
     return pp;
@@ -1432,28 +1532,36 @@ static PlanP make_plan_p(const dct_view* x, const dct_view* y, const dct_conv_de
   if ((double)Ho * Wo / (tiles * 128.0) < g_tune_igemm_packed_fill * 0.01) return pp;
   const int nch = x->c / 64;
   const long long blocks0 = (long long)y->n * tiles * (N / 128);
+  const int min_slices = g_tune_igemm_packed_min_slices;
   int splits = 1;
-  if (blocks0 < g_tune_igemm_packed_split) {
+  if (g_tune_igemm_packed_splits >= 1) {
+    splits = g_tune_igemm_packed_splits < nch ? g_tune_igemm_packed_splits : nch;
+  } else if (blocks0 < g_tune_igemm_packed_split) {
     splits = (int)((g_tune_igemm_packed_split + 48 + blocks0 - 1) / blocks0);
     if (splits > nch) splits = nch;
-    while (splits > 1 && nch / splits < 4) --splits;
+    while (splits > 1 && nch / splits < min_slices) --splits;
   }
-  if (nch / splits < 4 || blocks0 * splits < (g_tune_igemm_packed_split < 256 ? g_tune_igemm_packed_split : 256)) return pp;
+  if ((g_tune_igemm_packed_splits < 1 && nch / splits < min_slices) ||
+      blocks0 * splits < (g_tune_igemm_packed_split < 256 ? g_tune_igemm_packed_split : 256))
+    return pp;
   pp.cps = (nch + splits - 1) / splits;
   pp.splits = (nch + pp.cps - 1) / pp.cps;
   pp.use = 1; pp.PR = PR; pp.tiles_per_img = tiles;
+  pp.ring = g_tune_igemm_packed_ring ? 1 : 0;
   return pp;
 }
-template <bool LEAN>
+template <bool LEAN, bool RING = false>
 static void launch_v3p_k(const IgemmParams& p, const PlanP& pp, dim3 grid, hipStream_t st) {
-  constexpr size_t lds = 2 * (size_t)(24 * 1024) + 2 * (size_t)128 * 128;
+  // two halo and two weight stages (80 KiB), or one halo stage and the three-slot weight ring (72 KiB)
+  constexpr size_t lds = RING ? (size_t)(24 * 1024) + 3 * (size_t)128 * 128 : 2 * (size_t)(24 * 1024) + 2 * (size_t)128 * 128;
+  static_assert(lds <= 80 * 1024, "a second block must fit the CU's LDS");
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm3p_kernel<128, 4, 2, LEAN>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm3p_kernel<128, 4, 2, LEAN, RING>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  DCT_LAUNCH_FAM(DCT_FAM_IGEMM3P, DCT_PROF_IGEMM, (igemm3p_kernel<128, 4, 2, LEAN>), grid, dim3(512), lds, st, p, pp.PR, pp.tiles_per_img, pp.cps);
+  DCT_LAUNCH_FAM(DCT_FAM_IGEMM3P, DCT_PROF_IGEMM, (igemm3p_kernel<128, 4, 2, LEAN, RING>), grid, dim3(512), lds, st, p, pp.PR, pp.tiles_per_img, pp.cps);
 }
 // dct_tune_set(DCT_TUNE_IGEMM_XCD): 0 = natural 3-D grids; 1 = the per-tap and packed-rows kernels deal their blocks XCD by XCD
 // (xcd_remap) on layers whose packed weights outweigh their activations; 2 = on every layer they run
@@ -1475,12 +1583,20 @@ static void fold_splits(const IgemmParams& p, int splits, hipStream_t st) {     
   if (splits > 1)
     DCT_LAUNCH_FAM(DCT_FAM_FOLDS, DCT_PROF_IGEMM, (splitk_epilogue_kernel<T>), dim3(div_up((long long)p.M * (p.N / 4), 256)), dim3(256), 0, st, p, splits);
 }
+// the loop form a packed-rows launch runs (the plan note names it): 0 plain, 1 lean, 2 lean on the weight ring
+static int v3p_loop(const IgemmParams& p, const PlanP& pp) {
+  // lean loop: buffer descriptors need the activations and the packed weights under 2 GiB each
+  if (!((g_tune_lean & 2) && p.x_bytes < (1ll << 31) && p.w_bytes < (1ll << 31))) return 0;
+  return pp.ring ? 2 : 1;
+}
 static void launch_v3p(const IgemmParams& p0, const PlanP& pp, int images, hipStream_t st) {
   IgemmParams p = p0;
   const dim3 grid = xcd_grid(p, dim3((unsigned)(images * pp.tiles_per_img), p.N / 128, pp.splits), false);
-  // lean loop: buffer descriptors need the activations and the packed weights under 2 GiB each
-  if ((g_tune_lean & 2) && p.x_bytes < (1ll << 31) && p.w_bytes < (1ll << 31)) launch_v3p_k<true>(p, pp, grid, st);
-  else launch_v3p_k<false>(p, pp, grid, st);
+  switch (v3p_loop(p, pp)) {
+    case 2: launch_v3p_k<true, true>(p, pp, grid, st); break;
+    case 1: launch_v3p_k<true>(p, pp, grid, st); break;
+    default: launch_v3p_k<false>(p, pp, grid, st); break;
+  }
   fold_splits<bf16_t>(p, pp.splits, st);
 }
 
@@ -1688,8 +1804,9 @@ extern "C" int dct_conv2d(const dct_view* x, const void* w_packed, const float* 
     case ROUTE_PACKED:
       if (cp.packed.splits > 1) p.partial = (float*)workspace;
       launch_v3p(p, cp.packed, y->n, st);
-      DCT_PLAN_NOTE("igemm3p packed rows (%d rows of %d px per 128-px tile): %d x %d blocks x %d channel-slice splits", cp.packed.PR, p.Wo,
-                    y->n * cp.packed.tiles_per_img, p.N / 128, cp.packed.splits);
+      DCT_PLAN_NOTE("igemm3p packed rows (%d rows of %d px per 128-px tile): %d x %d blocks x %d channel-slice splits%s", cp.packed.PR, p.Wo,
+                    y->n * cp.packed.tiles_per_img, p.N / 128, cp.packed.splits,
+                    v3p_loop(p, cp.packed) == 2 ? ", weight ring (three stages, two rounds ahead)" : "");
       break;
     case ROUTE_TAP:
       if (cp.tap.splits > 1) p.partial = (float*)workspace;
@@ -1724,6 +1841,9 @@ extern "C" int dct_tune_set(int knob, int value) {
     case DCT_TUNE_IGEMM_PACKED: g_tune_igemm_packed = value; return DCT_OK;
     case DCT_TUNE_IGEMM_HALO_MIN_BLOCKS: g_tune_igemm_halo_min_blocks = value; return DCT_OK;
     case DCT_TUNE_IGEMM_HALO_COVER: g_tune_igemm_halo_cover = value; return DCT_OK;
+    case DCT_DIAG_IGEMM_PACKED_MIN_SLICES: if (value < 1) return DCT_ERR_BAD_ARG; g_tune_igemm_packed_min_slices = value; return DCT_OK;
+    case DCT_DIAG_IGEMM_PACKED_SPLITS: g_tune_igemm_packed_splits = value; return DCT_OK;
+    case DCT_TUNE_IGEMM_PACKED_RING: if (value < 0 || value > 1) return DCT_ERR_BAD_ARG; g_tune_igemm_packed_ring = value; return DCT_OK;
     case DCT_TUNE_IGEMM_HALO_TALL: if (value < 0 || value > 2) return DCT_ERR_BAD_ARG; g_tune_igemm_halo_tall = value; return DCT_OK;
     case DCT_DIAG_IGEMM_HALO_TALL_MIN_BLOCKS: if (value < 1) return DCT_ERR_BAD_ARG; g_tune_igemm_halo_tall_min_blocks = value; return DCT_OK;
     case DCT_TUNE_IGEMM_SPLIT_TARGET: if (value < 64) return DCT_ERR_BAD_ARG; g_tune_igemm_split_target = value; return DCT_OK;

@@ -1047,6 +1047,9 @@ enum { DCT_TUNE_IGEMM_SPLIT = 1,   /* >= 1: force the split-K factor; -1 (defaul
                                                 (each weight is fetched into ONE L2 slice); 0: natural 3-D grids; 2: on every layer */
        DCT_TUNE_IGEMM_HALO_TALL = 40,        /* 16 x 16 patches on one halo stage in the shared-halo kernel (two blocks per CU, 32 MFMAs per wave and barrier
                                                 round; bit-identical to the 8 x 16 patches): 0 = never, 1 (default) = planner's choice, 2 = every layer the form can run */
+       DCT_TUNE_IGEMM_PACKED_RING = 41,      /* lean loop of the packed-rows kernel on one halo stage and a three-slot weight ring (72 KiB; a weight stage is issued two
+                                                barrier rounds ahead behind a counted vmcnt; bit-identical): 0 = two halo and two weight stages, 1 (default) =
+                                                every packed-rows launch */
        DCT_TUNE_LEAN = 38 };                 /* bit mask (default 31: all set) of the instruction-lean loop forms, each bit-identical to
                                                 the plain form it replaces (0 = the plain forms, the tests' reference): bit 0 = filter-row weight gradient,
                                                 bit 1 = packed-rows conv kernel, bit 2 = per-tap weight gradient, bit 3 = per-tap conv kernel, bit 4 (with bit 0, round 5) =
