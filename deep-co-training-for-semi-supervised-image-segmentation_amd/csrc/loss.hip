@@ -1110,70 +1110,50 @@ __global__ __launch_bounds__(256) void jsd_step_kernel(PtrPack pk, PtrPack probs
   block_partial2(sum, 0.f, partial);
 }
 
-// ---- pseudo-label consistency: cross pseudo supervision / voted pseudo-label (the rule: include/dct.h, dct_pl_*) --------------------
-// The teachers of one pixel, as constants.  cross: every view j names k_j = first maximum of p_j and is kept when p_j[k_j] >= tau;
-// ensemble: one teacher, the first maximum of the fp32 sums taken in view order, kept when sum[k] * invS >= tau.  Out: cnt[c] = the kept
-// teachers that name class c, own[s] = the class view s named itself as a kept teacher (-1: none; a view is no teacher of itself), so
-// that student s meets n = cnt[c] - (own[s] == c) teacher terms of class c.  Returns the number of kept teachers.
+// ---- view consistency: hard pseudo-labels, sharpened soft pseudo-labels, softmax-MSE (the rules: include/dct.h, dct_pl_* / dct_spl_* / dct_mse_*) ----
+// One kernel family over a rule, as for the cross entropies above.  What every rule starts from exists once, so that first maximum,
+// confidence and mask are the same compares on the same fp32 values under all three (include/dct.h promises them bit for bit):
+// cross: every view j names k_j = first maximum of p_j and is kept when p_j[k_j] >= tau; ensemble: one teacher, the first maximum of the
+// fp32 sums taken in view order, kept when sum[k] * invS >= tau.
 // The mode is a uniform branch (a kernel argument), not a template parameter: the two derivations are a few compares per pixel of an
 // HBM-bound pass, and everything behind them (logs, gradients, stores) is one code path.
+// Nothing here may be addressed at run time (scratch): k is a compile-time-unrolled compare, never an index, and i, j are constants of
+// unrolled loops.
+// The first maximum of v: returns k, bv = v[k].
+template <int C>
+__device__ __forceinline__ int cons_first_max(const float (&v)[C], float& bv) {
+  bv = v[0];
+  int best = 0;
+#pragma unroll
+  for (int c = 1; c < C; ++c) if (v[c] > bv) { bv = v[c]; best = c; }
+  return best;
+}
+// The ensemble's raw teacher: sum = the views added in view order, best / bv = its first maximum (on the unscaled sums: scaling cannot
+// create a tie).  Returns the confidence q = sum[k] * invS.
 template <int C, int SMAX>
-__device__ __forceinline__ int pl_teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, float (&cnt)[C], int (&own)[SMAX]) {
+__device__ __forceinline__ float cons_ensemble(const float (&p)[SMAX][C], int S, float invS, float (&sum)[C], int& best, float& bv) {
 #pragma clang fp contract(off)    // the sums and q are formed from the ROUNDED probabilities, as the rule states them: no product of softmax_px may fold into an add here
-  int kept = 0;
 #pragma unroll
-  for (int c = 0; c < C; ++c) cnt[c] = 0.f;
-  if (teacher == DCT_PL_CROSS) {
+  for (int c = 0; c < C; ++c) sum[c] = p[0][c];
 #pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      own[s] = -1;
-      if (s < S) {
-        float bv = p[s][0];
-        int best = 0;
+  for (int s = 1; s < SMAX; ++s) {
+    if (s < S) {
 #pragma unroll
-        for (int c = 1; c < C; ++c) if (p[s][c] > bv) { bv = p[s][c]; best = c; }
-        if (bv >= tau) {
-          own[s] = best;
-          ++kept;
-#pragma unroll
-          for (int c = 0; c < C; ++c) cnt[c] = cnt[c] + (best == c ? 1.f : 0.f);
-        }
-      }
-    }
-  } else {
-    float sum[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) sum[c] = p[0][c];
-#pragma unroll
-    for (int s = 1; s < SMAX; ++s) {
-      own[s] = -1;
-      if (s < S) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) sum[c] = sum[c] + p[s][c];
-      }
-    }
-    own[0] = -1;
-    float bv = sum[0];
-    int best = 0;
-#pragma unroll
-    for (int c = 1; c < C; ++c) if (sum[c] > bv) { bv = sum[c]; best = c; }   // on the unscaled sums: scaling cannot create a tie
-    const float q = bv * invS;
-    if (q >= tau) {
-      kept = 1;
-#pragma unroll
-      for (int c = 0; c < C; ++c) cnt[c] = best == c ? 1.f : 0.f;
+      for (int c = 0; c < C; ++c) sum[c] = sum[c] + p[s][c];
     }
   }
-  return kept;
+  best = cons_first_max<C>(sum, bv);
+  return bv * invS;
 }
-// student s of one pixel: returns sum_c n * -log(p[c] + eps) over its n = cnt[c] - (own == c) teacher terms (the pixel's map value is wgt
-// times the sum over s) and d[c] = d map / d p[c] = -(wgt n) / (p[c] + eps).  No term: no log, and d[c] = 0 exactly.
-template <int C>
-__device__ __forceinline__ float pl_student(const float (&p)[C], const float (&cnt)[C], int own, float eps, float wgt, float (&d)[C]) {
+// Student i against n = terms(c) teacher terms of class c: returns sum_c n * -log(p[c] + eps) (the pixel's map value is wgt times the sum
+// over i) and d[c] = d map / d p[c] = -(wgt n) / (p[c] + eps).  No term: no log, and d[c] = 0 exactly.  terms is a callable so that the
+// hard rule forms its n inside this loop: an n[C] formed ahead of it costs the map kernel 6 registers and a wave per SIMD at C = 8.
+template <int C, class Terms>
+__device__ __forceinline__ float cons_log_student(const float (&p)[C], Terms terms, float eps, float wgt, float (&d)[C]) {
   float a = 0.f;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    const float n = cnt[c] - (own == c ? 1.f : 0.f);
+    const float n = terms(c);
     d[c] = 0.f;
     if (n != 0.f) {
       const float pe = p[c] + eps;
@@ -1183,48 +1163,255 @@ __device__ __forceinline__ float pl_student(const float (&p)[C], const float (&c
   }
   return a;
 }
-// kden: the teacher terms of a pixel (cross: S, ensemble: 1); wgt: 1 / (S (S - 1)) resp. 1 / S
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void pl_map_fwd_kernel(PtrPack pk, int S, int teacher, float tau, float eps, float invS, float wgt, float kden,
-                                                          float* map, float* keptmap, long long P) {
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    float p[SMAX][C], cnt[C];
-    int own[SMAX];
+
+// A rule is what the three criteria differ in.  It carries its scalars (a kernel argument) and offers
+//   State<C, SMAX>                                      the teachers of one pixel, as constants;
+//   teachers(p, S, teacher, tau, invS, state) -> kept   fills the state, returns the number of kept teachers;
+//   student(p, state, S, teacher, i, wgt, d) -> a       student i's value a_i (the map value is wgt times the sum over i) and
+//                                                       d[c] = d map / d p_i[c]; i is a constant of the caller's unrolled loop;
+//   kPerClass                                           whether the host's weight divides by C as well.
+// Hard pseudo-labels (cross pseudo supervision / voted pseudo-label).  State: cnt[c] = the kept teachers that name class c, own[s] = the
+// class view s named itself as a kept teacher (-1: none; a view is no teacher of itself), so that student s meets
+// n = cnt[c] - (own[s] == c) teacher terms of class c.
+struct HardRule {
+  static constexpr bool kPerClass = false;
+  float eps;
+  template <int C, int SMAX> struct State { float cnt[C]; int own[SMAX]; };
+  template <int C, int SMAX>
+  __device__ __forceinline__ int teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, State<C, SMAX>& st) const {
+#pragma clang fp contract(off)    // as cons_ensemble: nothing here may fold a product of softmax_px into an add
+    int kept = 0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) st.cnt[c] = 0.f;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) st.own[s] = -1;
+    if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+      for (int s = 0; s < SMAX; ++s) {
+        if (s < S) {
+          float bv;
+          const int best = cons_first_max<C>(p[s], bv);
+          if (bv >= tau) {
+            st.own[s] = best;
+            ++kept;
+#pragma unroll
+            for (int c = 0; c < C; ++c) st.cnt[c] = st.cnt[c] + (best == c ? 1.f : 0.f);
+          }
+        }
+      }
+    } else {
+      float sum[C], bv;
+      int best;
+      if (cons_ensemble<C, SMAX>(p, S, invS, sum, best, bv) >= tau) {
+        kept = 1;
+#pragma unroll
+        for (int c = 0; c < C; ++c) st.cnt[c] = best == c ? 1.f : 0.f;
+      }
+    }
+    return kept;
+  }
+  template <int C, int SMAX>
+  __device__ __forceinline__ float student(const float (&p)[SMAX][C], const State<C, SMAX>& st, int, int, int i, float wgt, float (&d)[C]) const {
+    return cons_log_student<C>(p[i], [&](int c) { return st.cnt[c] - (st.own[i] == c ? 1.f : 0.f); }, eps, wgt, d);
+  }
+};
+
+// Sharpened soft pseudo-labels: Sharpen(q, T) in place of the argmax, r = 1 / T.  State: t[j] = m_j * Sharpen(p_j) for cross (0 for a
+// masked view and for j >= S), t[0] = m * Sharpen(sum) for ensemble; the mask is on the raw confidence, and a masked teacher is never
+// sharpened.  The S teachers are HELD (SMAX C floats) and not recomputed per student: recomputing costs S times the 2 C transcendentals
+// of every teacher, holding costs 64 registers at SMAX = 8, C = 8, where the file of a 256-thread block (512 per lane) has them.
+struct SoftRule {
+  static constexpr bool kPerClass = false;
+  float eps, r;
+  template <int C, int SMAX> struct State { float t[SMAX][C]; };
+  // Sharpen(q, T) of one raw teacher vector q with first maximum k (bv = q[k]): u[c] = exp2f(r (log2f(q[c]) - log2f(q[k]))), 0 where
+  // q[c] == 0 and 1 exactly at k; t = u / (u[0] + ... + u[C-1]), added in class order.  Scale-free, so the ensemble hands in its
+  // unscaled sums.
+  template <int C>
+  __device__ __forceinline__ void sharpen(const float (&q)[C], int k, float bv, float (&t)[C]) const {
+#pragma clang fp contract(off)    // the argument of exp2f is the rounded product of the rounded difference, as the rule states it
+    const float lk = log2f(bv);
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      float u = 1.f;
+      if (c != k) u = q[c] == 0.f ? 0.f : exp2f(r * (log2f(q[c]) - lk));
+      t[c] = u;
+      sum = sum + u;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) t[c] = t[c] / sum;
+  }
+  template <int C, int SMAX>
+  __device__ __forceinline__ int teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, State<C, SMAX>& st) const {
+#pragma clang fp contract(off)    // as cons_ensemble
+    int kept = 0;
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
-      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
+#pragma unroll
+      for (int c = 0; c < C; ++c) st.t[s][c] = 0.f;
     }
-    const int kept = pl_teachers<C, SMAX>(p, S, teacher, tau, invS, cnt, own);
+    if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+      for (int s = 0; s < SMAX; ++s) {
+        if (s < S) {
+          float bv;
+          const int best = cons_first_max<C>(p[s], bv);
+          if (bv >= tau) {
+            ++kept;
+            sharpen<C>(p[s], best, bv, st.t[s]);
+          }
+        }
+      }
+    } else {
+      float sum[C], bv;
+      int best;
+      if (cons_ensemble<C, SMAX>(p, S, invS, sum, best, bv) >= tau) {
+        kept = 1;
+        sharpen<C>(sum, best, bv, st.t[0]);
+      }
+    }
+    return kept;
+  }
+  // n[c] of student i: cross: the other views' kept teachers added in ascending j (formed as that sum, never as a total minus the
+  // student's own share: (t_0 + t_1) - t_0 is not t_1); ensemble: the one teacher.
+  template <int C, int SMAX>
+  __device__ __forceinline__ float student(const float (&p)[SMAX][C], const State<C, SMAX>& st, int S, int teacher, int i, float wgt, float (&d)[C]) const {
+    float n[C];
+    {
+#pragma clang fp contract(off)
+      if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) n[c] = 0.f;
+#pragma unroll
+        for (int j = 0; j < SMAX; ++j) {
+          if (j < S && j != i) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) n[c] = n[c] + st.t[j][c];
+          }
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) n[c] = st.t[0][c];
+      }
+    }
+    return cons_log_student<C>(p[i], [&](int c) { return n[c]; }, eps, wgt, d);
+  }
+};
+
+// Softmax-MSE: the squared distance to the other views' (or the mean) prediction; no scalar of its own.  State: cross: m[j] =
+// p_j[k_j] >= tau (false for j >= S); ensemble: q[c] = sum[c] * invS and m[0] = q[k] >= tau.
+struct MseRule {
+  static constexpr bool kPerClass = true;
+  template <int C, int SMAX> struct State { bool m[SMAX]; float q[C]; };
+  template <int C, int SMAX>
+  __device__ __forceinline__ int teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, State<C, SMAX>& st) const {
+#pragma clang fp contract(off)    // as cons_ensemble: q is formed from the ROUNDED sums
+    int kept = 0;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) st.m[s] = false;
+#pragma unroll
+    for (int c = 0; c < C; ++c) st.q[c] = 0.f;
+    if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+      for (int s = 0; s < SMAX; ++s) {
+        if (s < S) {
+          float bv;
+          cons_first_max<C>(p[s], bv);
+          if (bv >= tau) { st.m[s] = true; ++kept; }
+        }
+      }
+    } else {
+      float sum[C], bv;
+      int best;
+      const float conf = cons_ensemble<C, SMAX>(p, S, invS, sum, best, bv);
+#pragma unroll
+      for (int c = 0; c < C; ++c) st.q[c] = sum[c] * invS;
+      if (conf >= tau) { st.m[0] = true; kept = 1; }
+    }
+    return kept;
+  }
+  // Every difference is the difference of two probabilities (never a total minus the student's own share), every square a rounded
+  // product added in class order, a masked teacher's differences are 0.  Only d[C] and two sums are live beside the probabilities.
+  template <int C, int SMAX>
+  __device__ __forceinline__ float student(const float (&p)[SMAX][C], const State<C, SMAX>& st, int S, int teacher, int i, float wgt, float (&d)[C]) const {
+#pragma clang fp contract(off)    // the squares are rounded before they are added, as the rule states them and as the reference bounds them
+    float a = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) d[c] = 0.f;
+    if (teacher == DCT_PL_CROSS) {
+#pragma unroll
+      for (int j = 0; j < SMAX; ++j) {
+        if (j < S && j != i) {
+          float sq = 0.f;
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            const float e = st.m[j] ? p[i][c] - p[j][c] : 0.f;
+            sq = sq + e * e;
+            d[c] = d[c] + e;
+          }
+          a = a + sq;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float e = st.m[0] ? p[i][c] - st.q[c] : 0.f;
+        a = a + e * e;
+        d[c] = e;
+      }
+    }
+    const float w2 = 2.f * wgt;
+#pragma unroll
+    for (int c = 0; c < C; ++c) d[c] = w2 * d[c];
+    return a;
+  }
+};
+
+// What the three kernels take beside the rule: wgt = the weight of one teacher term in the map (1 / (S (S - 1)) resp. 1 / S, divided by C
+// as well under kPerClass), kden = the teacher terms of a pixel (cross: S, ensemble: 1)
+struct ConsArgs { int S, teacher; float tau, invS, wgt, kden; long long P; };
+
+// The map over S probability maps, and optionally the per-pixel kept fraction
+template <int C, int SMAX, class Rule>
+__global__ __launch_bounds__(256) void cons_map_fwd_kernel(Rule rule, ConsArgs ca, PtrPack pk, float* map, float* keptmap) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < ca.P; pix += (long long)gridDim.x * 256) {
+    float p[SMAX][C];
+    typename Rule::template State<C, SMAX> st;
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) {
+      if (s < ca.S) load_px<C>(pk.in[s], pix, p[s]);
+    }
+    const int kept = rule.teachers(p, ca.S, ca.teacher, ca.tau, ca.invS, st);
     float a = 0.f;
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
+      if (s < ca.S) {
         float d[C];
-        a += pl_student<C>(p[s], cnt, own[s], eps, wgt, d);
+        a += rule.student(p, st, ca.S, ca.teacher, s, ca.wgt, d);
       }
     }
-    map[pix] = wgt * a;
-    if (keptmap) keptmap[pix] = (float)kept / kden;
+    map[pix] = ca.wgt * a;
+    if (keptmap) keptmap[pix] = (float)kept / ca.kden;
   }
 }
 // dprobs_s = dmap[pix] * d map / d p_s, the teachers recomputed from the probabilities
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void pl_map_bwd_kernel(PtrPack pk, int S, int teacher, float tau, float eps, float invS, float wgt,
-                                                          const float* dmap, long long P) {
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    float p[SMAX][C], cnt[C];
-    int own[SMAX];
+template <int C, int SMAX, class Rule>
+__global__ __launch_bounds__(256) void cons_map_bwd_kernel(Rule rule, ConsArgs ca, PtrPack pk, const float* dmap) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < ca.P; pix += (long long)gridDim.x * 256) {
+    float p[SMAX][C];
+    typename Rule::template State<C, SMAX> st;
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
-      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
+      if (s < ca.S) load_px<C>(pk.in[s], pix, p[s]);
     }
-    pl_teachers<C, SMAX>(p, S, teacher, tau, invS, cnt, own);
     const float gp = dmap[pix];
+    rule.teachers(p, ca.S, ca.teacher, ca.tau, ca.invS, st);
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
+      if (s < ca.S) {
         float d[C];
-        pl_student<C>(p[s], cnt, own[s], eps, wgt, d);
+        rule.student(p, st, ca.S, ca.teacher, s, ca.wgt, d);
 #pragma unroll
         for (int c = 0; c < C; ++c) d[c] = d[c] != 0.f ? gp * d[c] : 0.f;     // a masked entry is 0 whatever dmap holds
         store_px<C>(pk.out[s], pix, d, false);
@@ -1233,38 +1420,44 @@ __global__ __launch_bounds__(256) void pl_map_bwd_kernel(PtrPack pk, int S, int 
   }
 }
 // The step's consistency section from logits in one pass, on jsd_step_kernel's structure and grid: block partials of (map value, kept
-// teachers), the S softmax maps (softmax_fwd_kernel's bits) and the S logit gradients g p (d - sum_c' d p) (jsd_bwd_kernel<_, true>'s
-// form; accumulate: round, then add).  One pixel per trip, every load of the pixel issued before its first store.
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void pl_step_kernel(PtrPack pk, PtrPack probs, int S, int teacher, float tau, float eps, float invS, float wgt,
-                                                       long long P, const float* gscale, float gmul, int acc, int want_grad, float* partial) {
-  const float g = (gscale ? gscale[0] : 1.f) * gmul / (float)P;
+// teachers) for pl_finalize_kernel, the S softmax maps (softmax_fwd_kernel's bits) and the S logit gradients g p (d - sum_c' d p)
+// (jsd_bwd_kernel<_, true>'s form; accumulate: round, then add).  One pixel per trip, every load of the pixel issued before its first store.
+template <int C, int SMAX, class Rule>
+__global__ __launch_bounds__(256) void cons_step_kernel(Rule rule, ConsArgs ca, PtrPack pk, PtrPack probs, const float* gscale, float gmul, int acc,
+                                                         int want_grad, float* partial) {
+  const float g = (gscale ? gscale[0] : 1.f) * gmul / (float)ca.P;
   float sum = 0.f, keptsum = 0.f;
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
+  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < ca.P; pix += (long long)gridDim.x * 256) {
     float x[SMAX][C], old[SMAX][C];
+    // More than two views: nothing outstanding at the top of a trip.  The compiler's wait-count pass does not know that a view's load
+    // and its use hang on the same uniform guard, so it carries the loads of the last trip across the back edge as pending; where the
+    // register allocator forms a load's address in the load's own destination registers (it does for the vector loads of C = 2 and 4,
+    // or not, from one build to the next), that puts a vmcnt(0) in front of every view's loads: eight round trips in a row in place of
+    // one (measured: 3-6 % of the call at five views).  The two-view kernels the trainer launches show none of it and stay as they were.
+    if constexpr (SMAX > 2) __builtin_amdgcn_s_waitcnt(0x0f70);       // vmcnt(0), the other counters left alone
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
+      if (s < ca.S) {
         load_px<C>(pk.in[s], pix, x[s]);
         if (want_grad && acc) load_px<C>(pk.out[s], pix, old[s]);
       }
     }
-    float p[SMAX][C], cnt[C];
-    int own[SMAX];
+    float p[SMAX][C];
+    typename Rule::template State<C, SMAX> st;
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
+      if (s < ca.S) {
         softmax_px<C>(x[s], p[s]);
         if (probs.out[s]) store_px<C>(probs.out[s], pix, p[s], false);
       }
     }
-    keptsum += (float)pl_teachers<C, SMAX>(p, S, teacher, tau, invS, cnt, own);
+    keptsum += (float)rule.teachers(p, ca.S, ca.teacher, ca.tau, ca.invS, st);
     float a = 0.f;
 #pragma unroll
     for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
+      if (s < ca.S) {
         float d[C];
-        a += pl_student<C>(p[s], cnt, own[s], eps, wgt, d);
+        a += rule.student(p, st, ca.S, ca.teacher, s, ca.wgt, d);
         if (want_grad) {
           float dot = 0.f;
 #pragma unroll
@@ -1281,7 +1474,7 @@ __global__ __launch_bounds__(256) void pl_step_kernel(PtrPack pk, PtrPack probs,
         }
       }
     }
-    sum += wgt * a;
+    sum += ca.wgt * a;
   }
   block_partial2(sum, keptsum, partial);
 }
@@ -1291,394 +1484,6 @@ __global__ __launch_bounds__(256) void pl_finalize_kernel(const float* partial, 
   float a, b;
   fold_partials(partial, blocks, a, b);
   if (threadIdx.x == 0) { out[0] = a / denom_a; out[1] = b / denom_b; }
-}
-
-// ---- soft pseudo-label consistency: sharpened teachers in place of the argmax (the rule: include/dct.h, dct_spl_*) ------------------
-// Sharpen(q, T) of one raw teacher vector q with first maximum k (bv = q[k]) and r = 1 / T: u[c] = exp2f(r (log2f(q[c]) - log2f(q[k]))),
-// 0 where q[c] == 0 and 1 exactly at k; t = u / (u[0] + ... + u[C-1]), added in class order.  Scale-free, so the ensemble hands in its
-// unscaled sums.  k is a compile-time-unrolled compare, never an index: nothing here may be addressed at run time (scratch).
-template <int C>
-__device__ __forceinline__ void spl_sharpen(const float (&q)[C], int k, float bv, float r, float (&t)[C]) {
-#pragma clang fp contract(off)    // the argument of exp2f is the rounded product of the rounded difference, as the rule states it
-  const float lk = log2f(bv);
-  float sum = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    float u = 1.f;
-    if (c != k) u = q[c] == 0.f ? 0.f : exp2f(r * (log2f(q[c]) - lk));
-    t[c] = u;
-    sum = sum + u;
-  }
-#pragma unroll
-  for (int c = 0; c < C; ++c) t[c] = t[c] / sum;
-}
-// The sharpened teachers of one pixel, as constants: k and the mask are pl_teachers' (the same compares on the same fp32 values, the
-// mask on the raw confidence before sharpening).  Out: t[j] = m_j * Sharpen(p_j) for cross (0 for a masked view and for j >= S),
-// t[0] = m * Sharpen(sum) for ensemble.  Returns the number of kept teachers.  A masked teacher is never sharpened.
-// The S teachers are HELD (SMAX C floats) and not recomputed per student: recomputing costs S times the 2 C transcendentals of every
-// teacher, holding costs 64 registers at SMAX = 8, C = 8, where the file of a 256-thread block (512 per lane) has them.
-template <int C, int SMAX>
-__device__ __forceinline__ int spl_teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, float r, float (&t)[SMAX][C]) {
-#pragma clang fp contract(off)    // as pl_teachers: the sums and q are formed from the ROUNDED probabilities
-  int kept = 0;
-#pragma unroll
-  for (int s = 0; s < SMAX; ++s) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) t[s][c] = 0.f;
-  }
-  if (teacher == DCT_PL_CROSS) {
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        float bv = p[s][0];
-        int best = 0;
-#pragma unroll
-        for (int c = 1; c < C; ++c) if (p[s][c] > bv) { bv = p[s][c]; best = c; }
-        if (bv >= tau) {
-          ++kept;
-          spl_sharpen<C>(p[s], best, bv, r, t[s]);
-        }
-      }
-    }
-  } else {
-    float sum[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) sum[c] = p[0][c];
-#pragma unroll
-    for (int s = 1; s < SMAX; ++s) {
-      if (s < S) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) sum[c] = sum[c] + p[s][c];
-      }
-    }
-    float bv = sum[0];
-    int best = 0;
-#pragma unroll
-    for (int c = 1; c < C; ++c) if (sum[c] > bv) { bv = sum[c]; best = c; }   // on the unscaled sums: scaling cannot create a tie
-    const float q = bv * invS;
-    if (q >= tau) {
-      kept = 1;
-      spl_sharpen<C>(sum, best, bv, r, t[0]);
-    }
-  }
-  return kept;
-}
-// n[c] of student i: cross: the other views' kept teachers added in ascending j (formed as that sum, never as a total minus the
-// student's own share: (t_0 + t_1) - t_0 is not t_1); ensemble: the one teacher.  i is a constant of the caller's unrolled loop.
-template <int C, int SMAX>
-__device__ __forceinline__ void spl_terms(const float (&t)[SMAX][C], int S, int teacher, int i, float (&n)[C]) {
-#pragma clang fp contract(off)
-  if (teacher == DCT_PL_CROSS) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) n[c] = 0.f;
-#pragma unroll
-    for (int j = 0; j < SMAX; ++j) {
-      if (j < S && j != i) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) n[c] = n[c] + t[j][c];
-      }
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < C; ++c) n[c] = t[0][c];
-  }
-}
-// pl_student over real-valued n: returns sum_c n[c] * -log(p[c] + eps) and d[c] = -(wgt n[c]) / (p[c] + eps).  No term: no log, d[c] = 0 exactly.
-template <int C>
-__device__ __forceinline__ float spl_student(const float (&p)[C], const float (&n)[C], float eps, float wgt, float (&d)[C]) {
-  float a = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    d[c] = 0.f;
-    if (n[c] != 0.f) {
-      const float pe = p[c] + eps;
-      a -= n[c] * logf(pe);
-      d[c] = -(wgt * n[c]) / pe;
-    }
-  }
-  return a;
-}
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void spl_map_fwd_kernel(PtrPack pk, int S, int teacher, float tau, float r, float eps, float invS, float wgt, float kden,
-                                                           float* map, float* keptmap, long long P) {
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    float p[SMAX][C], t[SMAX][C];
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
-    }
-    const int kept = spl_teachers<C, SMAX>(p, S, teacher, tau, invS, r, t);
-    float a = 0.f;
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        float n[C], d[C];
-        spl_terms<C, SMAX>(t, S, teacher, s, n);
-        a += spl_student<C>(p[s], n, eps, wgt, d);
-      }
-    }
-    map[pix] = wgt * a;
-    if (keptmap) keptmap[pix] = (float)kept / kden;
-  }
-}
-// dprobs_s = dmap[pix] * d map / d p_s, the teachers recomputed from the probabilities
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void spl_map_bwd_kernel(PtrPack pk, int S, int teacher, float tau, float r, float eps, float invS, float wgt,
-                                                           const float* dmap, long long P) {
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    float p[SMAX][C], t[SMAX][C];
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
-    }
-    const float gp = dmap[pix];
-    spl_teachers<C, SMAX>(p, S, teacher, tau, invS, r, t);
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        float n[C], d[C];
-        spl_terms<C, SMAX>(t, S, teacher, s, n);
-        spl_student<C>(p[s], n, eps, wgt, d);
-#pragma unroll
-        for (int c = 0; c < C; ++c) d[c] = d[c] != 0.f ? gp * d[c] : 0.f;     // a masked entry is 0 whatever dmap holds
-        store_px<C>(pk.out[s], pix, d, false);
-      }
-    }
-  }
-}
-// pl_step_kernel with the sharpened teachers: one pixel per trip, every load of the pixel issued before its first store; block partials
-// of (map value, kept teachers) for pl_finalize_kernel.
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void spl_step_kernel(PtrPack pk, PtrPack probs, int S, int teacher, float tau, float r, float eps, float invS, float wgt,
-                                                        long long P, const float* gscale, float gmul, int acc, int want_grad, float* partial) {
-  const float g = (gscale ? gscale[0] : 1.f) * gmul / (float)P;
-  float sum = 0.f, keptsum = 0.f;
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    float x[SMAX][C], old[SMAX][C];
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        load_px<C>(pk.in[s], pix, x[s]);
-        if (want_grad && acc) load_px<C>(pk.out[s], pix, old[s]);
-      }
-    }
-    float p[SMAX][C], t[SMAX][C];
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        softmax_px<C>(x[s], p[s]);
-        if (probs.out[s]) store_px<C>(probs.out[s], pix, p[s], false);
-      }
-    }
-    keptsum += (float)spl_teachers<C, SMAX>(p, S, teacher, tau, invS, r, t);
-    float a = 0.f;
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        float n[C], d[C];
-        spl_terms<C, SMAX>(t, S, teacher, s, n);
-        a += spl_student<C>(p[s], n, eps, wgt, d);
-        if (want_grad) {
-          float dot = 0.f;
-#pragma unroll
-          for (int c = 0; c < C; ++c) dot += d[c] * p[s][c];
-          float o[C];
-#pragma unroll
-          for (int c = 0; c < C; ++c) o[c] = g * p[s][c] * (d[c] - dot);
-          if (acc) {
-#pragma clang fp contract(off)    // store_px's accumulate: round, then add
-#pragma unroll
-            for (int c = 0; c < C; ++c) o[c] = o[c] + old[s][c];
-          }
-          store_px<C>(pk.out[s], pix, o, false);
-        }
-      }
-    }
-    sum += wgt * a;
-  }
-  block_partial2(sum, keptsum, partial);
-}
-
-// ---- softmax-MSE consistency: the squared distance to the other views' (or the mean) prediction (the rule: include/dct.h, dct_mse_*) ---
-// The masks of one pixel, as constants: pl_teachers' compares on the same fp32 values (first maximum, sums in view order, argmax before
-// scaling), without its class counts, which a squared distance has no use for.  Out: cross: m[j] = p_j[k_j] >= tau (false for j >= S);
-// ensemble: q[c] = sum[c] * invS and m[0] = q[k] >= tau.  Returns the number of kept teachers.
-template <int C, int SMAX>
-__device__ __forceinline__ int mse_teachers(const float (&p)[SMAX][C], int S, int teacher, float tau, float invS, bool (&m)[SMAX], float (&q)[C]) {
-#pragma clang fp contract(off)    // as pl_teachers: the sums and q are formed from the ROUNDED probabilities
-  int kept = 0;
-#pragma unroll
-  for (int s = 0; s < SMAX; ++s) m[s] = false;
-#pragma unroll
-  for (int c = 0; c < C; ++c) q[c] = 0.f;
-  if (teacher == DCT_PL_CROSS) {
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        float bv = p[s][0];
-#pragma unroll
-        for (int c = 1; c < C; ++c) if (p[s][c] > bv) bv = p[s][c];
-        if (bv >= tau) { m[s] = true; ++kept; }
-      }
-    }
-  } else {
-    float sum[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) sum[c] = p[0][c];
-#pragma unroll
-    for (int s = 1; s < SMAX; ++s) {
-      if (s < S) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) sum[c] = sum[c] + p[s][c];
-      }
-    }
-    float bv = sum[0];
-#pragma unroll
-    for (int c = 1; c < C; ++c) if (sum[c] > bv) bv = sum[c];                  // on the unscaled sums: scaling cannot create a tie
-#pragma unroll
-    for (int c = 0; c < C; ++c) q[c] = sum[c] * invS;
-    if (bv * invS >= tau) { m[0] = true; kept = 1; }
-  }
-  return kept;
-}
-// student i of one pixel: returns a_i (the pixel's map value is wgt times the sum over i) and d[c] = d map / d p_i[c].  Every difference
-// is the difference of two probabilities (never a total minus the student's own share), every square a rounded product added in class
-// order, a masked teacher's differences are 0.  i is a constant of the caller's unrolled loop: nothing is addressed at run time, and
-// only d[C] and two sums are live beside the probabilities.
-template <int C, int SMAX>
-__device__ __forceinline__ float mse_student(const float (&p)[SMAX][C], const bool (&m)[SMAX], const float (&q)[C], int S, int teacher, int i,
-                                             float wgt, float (&d)[C]) {
-#pragma clang fp contract(off)    // the squares are rounded before they are added, as the rule states them and as the reference bounds them
-  float a = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) d[c] = 0.f;
-  if (teacher == DCT_PL_CROSS) {
-#pragma unroll
-    for (int j = 0; j < SMAX; ++j) {
-      if (j < S && j != i) {
-        float sq = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          const float e = m[j] ? p[i][c] - p[j][c] : 0.f;
-          sq = sq + e * e;
-          d[c] = d[c] + e;
-        }
-        a = a + sq;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float e = m[0] ? p[i][c] - q[c] : 0.f;
-      a = a + e * e;
-      d[c] = e;
-    }
-  }
-  const float w2 = 2.f * wgt;
-#pragma unroll
-  for (int c = 0; c < C; ++c) d[c] = w2 * d[c];
-  return a;
-}
-// kden: the teacher terms of a pixel (cross: S, ensemble: 1); wgt: 1 / (C S (S - 1)) resp. 1 / (C S)
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void mse_map_fwd_kernel(PtrPack pk, int S, int teacher, float tau, float invS, float wgt, float kden,
-                                                           float* map, float* keptmap, long long P) {
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    float p[SMAX][C], q[C];
-    bool m[SMAX];
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
-    }
-    const int kept = mse_teachers<C, SMAX>(p, S, teacher, tau, invS, m, q);
-    float a = 0.f;
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        float d[C];
-        a += mse_student<C, SMAX>(p, m, q, S, teacher, s, wgt, d);
-      }
-    }
-    map[pix] = wgt * a;
-    if (keptmap) keptmap[pix] = (float)kept / kden;
-  }
-}
-// dprobs_s = dmap[pix] * d map / d p_s, the masks recomputed from the probabilities
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void mse_map_bwd_kernel(PtrPack pk, int S, int teacher, float tau, float invS, float wgt,
-                                                           const float* dmap, long long P) {
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    float p[SMAX][C], q[C];
-    bool m[SMAX];
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) load_px<C>(pk.in[s], pix, p[s]);
-    }
-    const float gp = dmap[pix];
-    mse_teachers<C, SMAX>(p, S, teacher, tau, invS, m, q);
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        float d[C];
-        mse_student<C, SMAX>(p, m, q, S, teacher, s, wgt, d);
-#pragma unroll
-        for (int c = 0; c < C; ++c) d[c] = d[c] != 0.f ? gp * d[c] : 0.f;     // a masked entry is 0 whatever dmap holds
-        store_px<C>(pk.out[s], pix, d, false);
-      }
-    }
-  }
-}
-// pl_step_kernel with the squared distances: one pixel per trip, every load of the pixel issued before its first store; block partials
-// of (map value, kept teachers) for pl_finalize_kernel.  No logarithm and no division per class.
-template <int C, int SMAX>
-__global__ __launch_bounds__(256) void mse_step_kernel(PtrPack pk, PtrPack probs, int S, int teacher, float tau, float invS, float wgt,
-                                                        long long P, const float* gscale, float gmul, int acc, int want_grad, float* partial) {
-  const float g = (gscale ? gscale[0] : 1.f) * gmul / (float)P;
-  float sum = 0.f, keptsum = 0.f;
-  for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < P; pix += (long long)gridDim.x * 256) {
-    float x[SMAX][C], old[SMAX][C];
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        load_px<C>(pk.in[s], pix, x[s]);
-        if (want_grad && acc) load_px<C>(pk.out[s], pix, old[s]);
-      }
-    }
-    float p[SMAX][C], q[C];
-    bool m[SMAX];
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        softmax_px<C>(x[s], p[s]);
-        if (probs.out[s]) store_px<C>(probs.out[s], pix, p[s], false);
-      }
-    }
-    keptsum += (float)mse_teachers<C, SMAX>(p, S, teacher, tau, invS, m, q);
-    float a = 0.f;
-#pragma unroll
-    for (int s = 0; s < SMAX; ++s) {
-      if (s < S) {
-        float d[C];
-        a += mse_student<C, SMAX>(p, m, q, S, teacher, s, wgt, d);
-        if (want_grad) {
-          float dot = 0.f;
-#pragma unroll
-          for (int c = 0; c < C; ++c) dot += d[c] * p[s][c];
-          float o[C];
-#pragma unroll
-          for (int c = 0; c < C; ++c) o[c] = g * p[s][c] * (d[c] - dot);
-          if (acc) {
-#pragma clang fp contract(off)    // store_px's accumulate: round, then add
-#pragma unroll
-            for (int c = 0; c < C; ++c) o[c] = o[c] + old[s][c];
-          }
-          store_px<C>(pk.out[s], pix, o, false);
-        }
-      }
-    }
-    sum += wgt * a;
-  }
-  block_partial2(sum, keptsum, partial);
 }
 
 // ---- KL(y || p) -----------------------------------------------------------------------------------
@@ -2398,172 +2203,131 @@ extern "C" int dct_jsd_logits_step(const float* const* logits, int S, int64_t pi
   return dct_check_launch();
 }
 
-// ---- pseudo-label consistency -------------------------------------------------------------------------
+// ---- view consistency: the nine entry points on three launchers over the rule ---------------------------------------------------------
 namespace {
-// the rule's host-side constants: 1 / S as the ensemble confidence scales by it, the weight of one teacher term in the map, the teacher
-// terms of a pixel
-struct PlRule { float invS, wgt, kden; };
-bool pl_rule(int S, int teacher, float tau, float eps, PlRule& r) {
+// What every rule checks, and the host-side constants: 1 / S as the ensemble confidence scales by it, the teacher terms of a pixel and
+// the ordered pairs (cross) or views (ensemble) that the weight divides by
+bool cons_rule(int S, int teacher, float tau, int64_t pixels, ConsArgs& a, int& terms) {
   if (teacher != DCT_PL_CROSS && teacher != DCT_PL_ENSEMBLE) return false;
   if (S < (teacher == DCT_PL_CROSS ? 2 : 1) || S > MAXS) return false;
-  if (!(tau >= 0.f) || !(eps > 0.f)) return false;          // (a NaN fails both)
-  r.invS = 1.f / (float)S;
-  r.wgt = teacher == DCT_PL_CROSS ? 1.f / (float)(S * (S - 1)) : r.invS;
-  r.kden = teacher == DCT_PL_CROSS ? (float)S : 1.f;
+  if (!(tau >= 0.f) || pixels < 1) return false;             // (a NaN fails the first)
+  a = ConsArgs{S, teacher, tau, 1.f / (float)S, 0.f, teacher == DCT_PL_CROSS ? (float)S : 1.f, (long long)pixels};
+  terms = teacher == DCT_PL_CROSS ? S * (S - 1) : S;
   return true;
+}
+// w = 1 / (S (S - 1)) resp. 1 / S, under kPerClass 1 / (C S (S - 1)) resp. 1 / (C S): formed where C is known to be in 2..8
+template <class Rule, int C>
+inline ConsArgs cons_weighted(ConsArgs a, int terms) {
+  a.wgt = 1.f / (float)((Rule::kPerClass ? C : 1) * terms);
+  return a;
+}
+// the rules' own checks (a NaN fails each first comparison); the temperature: finite and > 0, and so is r = 1.f / T formed in fp32 (a
+// subnormal T gives inf)
+inline bool eps_ok(float eps) { return eps > 0.f; }
+bool soft_rule(float temperature, float eps, SoftRule& rule) {
+  rule = SoftRule{eps, 1.f / temperature};
+  return eps_ok(eps) && temperature > 0.f && __builtin_isfinite(temperature) && rule.r > 0.f && __builtin_isfinite(rule.r);
 }
 }  // namespace
 
-extern "C" int dct_pl_map_fwd(const float* const* probs, int S, int teacher, float tau, float eps, float* map, float* kept,
-                              int64_t pixels, int C_, dct_stream stream) {
+// The SMAX instantiation of `kernel` for C_, with the rule, the weighted arguments and what follows
+#define CONS_LAUNCH(kernel, SMAX_, grid, ...)                                                                                          \
+  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (kernel<C, SMAX_, Rule>), dim3(grid), dim3(256), 0, st, rule, cons_weighted<Rule, C>(a, terms), __VA_ARGS__))
+
+// The status of a bad call: BAD_ARG (the rule's check first), then UNSUPPORTED at dispatch; the step: BAD_ARG, WORKSPACE, UNSUPPORTED.
+template <class Rule>
+static int cons_map_fwd(const Rule& rule, bool rule_ok, const float* const* probs, int S, int teacher, float tau, float* map, float* kept,
+                        int64_t pixels, int C_, dct_stream stream) {
   PtrPack pk;
-  PlRule r;
-  if (!pl_rule(S, teacher, tau, eps, r) || !fill_pack(pk, probs, nullptr, S) || !map || pixels < 1) return DCT_ERR_BAD_ARG;
+  ConsArgs a;
+  int terms;
+  if (!rule_ok || !cons_rule(S, teacher, tau, pixels, a, terms) || !fill_pack(pk, probs, nullptr, S) || !map) return DCT_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = wide_grid(pixels);
-  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_map_fwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, eps, r.invS, r.wgt, r.kden, map, kept, (long long)pixels)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_map_fwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, eps, r.invS, r.wgt, r.kden, map, kept, (long long)pixels)); }
+  if (S <= 4) { CONS_LAUNCH(cons_map_fwd_kernel, 4, grid, pk, map, kept); }
+  else { CONS_LAUNCH(cons_map_fwd_kernel, MAXS, grid, pk, map, kept); }
   return dct_check_launch();
+}
+template <class Rule>
+static int cons_map_bwd(const Rule& rule, bool rule_ok, const float* const* probs, int S, int teacher, float tau, const float* dmap,
+                        float* const* dprobs, int64_t pixels, int C_, dct_stream stream) {
+  PtrPack pk;
+  ConsArgs a;
+  int terms;
+  if (!rule_ok || !cons_rule(S, teacher, tau, pixels, a, terms) || !dprobs || !fill_pack(pk, probs, dprobs, S) || !dmap) return DCT_ERR_BAD_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = wide_grid(pixels);
+  if (S <= 4) { CONS_LAUNCH(cons_map_bwd_kernel, 4, grid, pk, dmap); }
+  else { CONS_LAUNCH(cons_map_bwd_kernel, MAXS, grid, pk, dmap); }
+  return dct_check_launch();
+}
+template <class Rule>
+static int cons_step(const Rule& rule, bool rule_ok, const float* const* logits, int S, int teacher, float tau, int64_t pixels, int C_, float* out2,
+                     float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate, void* workspace,
+                     size_t workspace_bytes, dct_stream stream) {
+  PtrPack pk, pp;
+  ConsArgs a;
+  int terms;
+  if (!rule_ok || !cons_rule(S, teacher, tau, pixels, a, terms) || !fill_pack(pk, logits, dlogits, S) || !out2) return DCT_ERR_BAD_ARG;
+  for (int s = 0; s < MAXS; ++s) { pp.in[s] = nullptr; pp.out[s] = (probs && s < S) ? probs[s] : nullptr; }
+  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = grid_for(pixels);       // dct_jsd_logits_step's grid
+  const int want = dlogits ? 1 : 0;
+  if (S <= 2) { CONS_LAUNCH(cons_step_kernel, 2, grid, pk, pp, gscale, gmul, accumulate, want, (float*)workspace); }
+  else if (S <= 4) { CONS_LAUNCH(cons_step_kernel, 4, grid, pk, pp, gscale, gmul, accumulate, want, (float*)workspace); }
+  else { CONS_LAUNCH(cons_step_kernel, MAXS, grid, pk, pp, gscale, gmul, accumulate, want, (float*)workspace); }
+  DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * a.kden);
+  return dct_check_launch();
+}
+#undef CONS_LAUNCH
+
+extern "C" int dct_pl_map_fwd(const float* const* probs, int S, int teacher, float tau, float eps, float* map, float* kept,
+                              int64_t pixels, int C_, dct_stream stream) {
+  return cons_map_fwd(HardRule{eps}, eps_ok(eps), probs, S, teacher, tau, map, kept, pixels, C_, stream);
 }
 extern "C" int dct_pl_map_bwd(const float* const* probs, int S, int teacher, float tau, float eps, const float* dmap, float* const* dprobs,
                               int64_t pixels, int C_, dct_stream stream) {
-  PtrPack pk;
-  PlRule r;
-  if (!pl_rule(S, teacher, tau, eps, r) || !dprobs || !fill_pack(pk, probs, dprobs, S) || !dmap || pixels < 1) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = wide_grid(pixels);
-  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_map_bwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, eps, r.invS, r.wgt, dmap, (long long)pixels)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_map_bwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, eps, r.invS, r.wgt, dmap, (long long)pixels)); }
-  return dct_check_launch();
+  return cons_map_bwd(HardRule{eps}, eps_ok(eps), probs, S, teacher, tau, dmap, dprobs, pixels, C_, stream);
 }
 extern "C" int dct_pl_logits_step(const float* const* logits, int S, int teacher, float tau, float eps, int64_t pixels, int C_, float* out2,
                                   float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
                                   void* workspace, size_t workspace_bytes, dct_stream stream) {
-  PtrPack pk, pp;
-  PlRule r;
-  if (!pl_rule(S, teacher, tau, eps, r) || !fill_pack(pk, logits, dlogits, S) || !out2 || pixels < 1) return DCT_ERR_BAD_ARG;
-  for (int s = 0; s < MAXS; ++s) { pp.in[s] = nullptr; pp.out[s] = (probs && s < S) ? probs[s] : nullptr; }
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);
-  const int want = dlogits ? 1 : 0;
-  if (S <= 2) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, 2>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (pl_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * r.kden);
-  return dct_check_launch();
+  return cons_step(HardRule{eps}, eps_ok(eps), logits, S, teacher, tau, pixels, C_, out2, probs, gscale, gmul, dlogits, accumulate, workspace,
+                   workspace_bytes, stream);
 }
-
-// ---- soft pseudo-label consistency --------------------------------------------------------------------
-namespace {
-// pl_rule plus the temperature: finite and > 0, and so is r = 1.f / T formed in fp32 (a subnormal T gives inf)
-bool spl_rule(int S, int teacher, float tau, float temperature, float eps, PlRule& r, float& rT) {
-  if (!pl_rule(S, teacher, tau, eps, r)) return false;
-  if (!(temperature > 0.f) || !__builtin_isfinite(temperature)) return false;      // (a NaN fails the first)
-  rT = 1.f / temperature;
-  return rT > 0.f && __builtin_isfinite(rT);
-}
-}  // namespace
-
 extern "C" int dct_spl_map_fwd(const float* const* probs, int S, int teacher, float tau, float temperature, float eps, float* map, float* kept,
                                int64_t pixels, int C_, dct_stream stream) {
-  PtrPack pk;
-  PlRule r;
-  float rT;
-  if (!spl_rule(S, teacher, tau, temperature, eps, r, rT) || !fill_pack(pk, probs, nullptr, S) || !map || pixels < 1) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = wide_grid(pixels);
-  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_map_fwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, rT, eps, r.invS, r.wgt, r.kden, map, kept, (long long)pixels)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_map_fwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, rT, eps, r.invS, r.wgt, r.kden, map, kept, (long long)pixels)); }
-  return dct_check_launch();
+  SoftRule rule;
+  const bool ok = soft_rule(temperature, eps, rule);
+  return cons_map_fwd(rule, ok, probs, S, teacher, tau, map, kept, pixels, C_, stream);
 }
 extern "C" int dct_spl_map_bwd(const float* const* probs, int S, int teacher, float tau, float temperature, float eps, const float* dmap,
                                float* const* dprobs, int64_t pixels, int C_, dct_stream stream) {
-  PtrPack pk;
-  PlRule r;
-  float rT;
-  if (!spl_rule(S, teacher, tau, temperature, eps, r, rT) || !dprobs || !fill_pack(pk, probs, dprobs, S) || !dmap || pixels < 1) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = wide_grid(pixels);
-  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_map_bwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, rT, eps, r.invS, r.wgt, dmap, (long long)pixels)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_map_bwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, rT, eps, r.invS, r.wgt, dmap, (long long)pixels)); }
-  return dct_check_launch();
+  SoftRule rule;
+  const bool ok = soft_rule(temperature, eps, rule);
+  return cons_map_bwd(rule, ok, probs, S, teacher, tau, dmap, dprobs, pixels, C_, stream);
 }
 extern "C" int dct_spl_logits_step(const float* const* logits, int S, int teacher, float tau, float temperature, float eps, int64_t pixels, int C_,
                                    float* out2, float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
                                    void* workspace, size_t workspace_bytes, dct_stream stream) {
-  PtrPack pk, pp;
-  PlRule r;
-  float rT;
-  if (!spl_rule(S, teacher, tau, temperature, eps, r, rT) || !fill_pack(pk, logits, dlogits, S) || !out2 || pixels < 1) return DCT_ERR_BAD_ARG;
-  for (int s = 0; s < MAXS; ++s) { pp.in[s] = nullptr; pp.out[s] = (probs && s < S) ? probs[s] : nullptr; }
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);
-  const int want = dlogits ? 1 : 0;
-  if (S <= 2) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, 2>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (spl_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, rT, eps, r.invS, r.wgt, (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * r.kden);
-  return dct_check_launch();
+  SoftRule rule;
+  const bool ok = soft_rule(temperature, eps, rule);
+  return cons_step(rule, ok, logits, S, teacher, tau, pixels, C_, out2, probs, gscale, gmul, dlogits, accumulate, workspace, workspace_bytes, stream);
 }
-
-// ---- softmax-MSE consistency --------------------------------------------------------------------------
-namespace {
-// the host-side constants of the rule, without C: 1 / S, the teacher terms of a pixel and the ordered pairs (cross) or views (ensemble)
-// the weight divides by beside C
-struct MseRule { float invS, kden; int terms; };
-bool mse_rule(int S, int teacher, float tau, MseRule& r) {
-  if (teacher != DCT_PL_CROSS && teacher != DCT_PL_ENSEMBLE) return false;
-  if (S < (teacher == DCT_PL_CROSS ? 2 : 1) || S > MAXS) return false;
-  if (!(tau >= 0.f)) return false;                           // (a NaN fails it)
-  r.invS = 1.f / (float)S;
-  r.kden = teacher == DCT_PL_CROSS ? (float)S : 1.f;
-  r.terms = teacher == DCT_PL_CROSS ? S * (S - 1) : S;
-  return true;
-}
-// w = 1 / (C S (S - 1)) resp. 1 / (C S), formed where C is known to be in 2..8
-inline float mse_wgt(int C, const MseRule& r) { return 1.f / (float)(C * r.terms); }
-}  // namespace
-
 extern "C" int dct_mse_map_fwd(const float* const* probs, int S, int teacher, float tau, float* map, float* kept, int64_t pixels, int C_,
                                dct_stream stream) {
-  PtrPack pk;
-  MseRule r;
-  if (!mse_rule(S, teacher, tau, r) || !fill_pack(pk, probs, nullptr, S) || !map || pixels < 1) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = wide_grid(pixels);
-  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_map_fwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, r.invS, mse_wgt(C, r), r.kden, map, kept, (long long)pixels)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_map_fwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, r.invS, mse_wgt(C, r), r.kden, map, kept, (long long)pixels)); }
-  return dct_check_launch();
+  return cons_map_fwd(MseRule{}, true, probs, S, teacher, tau, map, kept, pixels, C_, stream);
 }
 extern "C" int dct_mse_map_bwd(const float* const* probs, int S, int teacher, float tau, const float* dmap, float* const* dprobs,
                                int64_t pixels, int C_, dct_stream stream) {
-  PtrPack pk;
-  MseRule r;
-  if (!mse_rule(S, teacher, tau, r) || !dprobs || !fill_pack(pk, probs, dprobs, S) || !dmap || pixels < 1) return DCT_ERR_BAD_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = wide_grid(pixels);
-  if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_map_bwd_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, r.invS, mse_wgt(C, r), dmap, (long long)pixels)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_map_bwd_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, S, teacher, tau, r.invS, mse_wgt(C, r), dmap, (long long)pixels)); }
-  return dct_check_launch();
+  return cons_map_bwd(MseRule{}, true, probs, S, teacher, tau, dmap, dprobs, pixels, C_, stream);
 }
 extern "C" int dct_mse_logits_step(const float* const* logits, int S, int teacher, float tau, int64_t pixels, int C_, float* out2,
                                    float* const* probs, const float* gscale, float gmul, float* const* dlogits, int accumulate,
                                    void* workspace, size_t workspace_bytes, dct_stream stream) {
-  PtrPack pk, pp;
-  MseRule r;
-  if (!mse_rule(S, teacher, tau, r) || !fill_pack(pk, logits, dlogits, S) || !out2 || pixels < 1) return DCT_ERR_BAD_ARG;
-  for (int s = 0; s < MAXS; ++s) { pp.in[s] = nullptr; pp.out[s] = (probs && s < S) ? probs[s] : nullptr; }
-  if (!ws_ok(workspace, workspace_bytes)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned grid = grid_for(pixels);
-  const int want = dlogits ? 1 : 0;
-  if (S <= 2) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_step_kernel<C, 2>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, r.invS, mse_wgt(C, r), (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  else if (S <= 4) { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_step_kernel<C, 4>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, r.invS, mse_wgt(C, r), (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  else { DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, (mse_step_kernel<C, MAXS>), dim3(grid), dim3(256), 0, st, pk, pp, S, teacher, tau, r.invS, mse_wgt(C, r), (long long)pixels, gscale, gmul, accumulate, want, (float*)workspace)); }
-  DCT_LAUNCH(DCT_PROF_LOSS, pl_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)grid, out2, (float)pixels, (float)pixels * r.kden);
-  return dct_check_launch();
+  return cons_step(MseRule{}, true, logits, S, teacher, tau, pixels, C_, out2, probs, gscale, gmul, dlogits, accumulate, workspace,
+                   workspace_bytes, stream);
 }
 
 extern "C" int dct_kl_map_fwd(const float* p, const float* y, float* map, int64_t pixels, int C_, float eps, dct_stream stream) {

@@ -823,96 +823,81 @@ PL_CROSS, PL_ENSEMBLE = 0, 1        # include/dct.h DCT_PL_*
 PL_TEACHERS = {"cross": PL_CROSS, "ensemble": PL_ENSEMBLE}
 
 
-def pl_map_fwd(probs: List[torch.Tensor], C_, teacher=PL_CROSS, tau=0.0, eps=1e-10, want_kept: bool = True):
-    """-> (map [P], kept map [P] or None) of the pseudo-label consistency term over S probability maps (the rule: include/dct.h, dct_pl_*)."""
+# The three view-consistency families (hard pseudo-labels dct_pl_*, sharpened soft pseudo-labels dct_spl_*, softmax-MSE dct_mse_*) differ
+# in the entry point's name and in the rule's scalars, which follow (S, teacher, tau) in every signature.
+def _cons_map_fwd(entry, probs, C_, teacher, tau, scalars, want_kept):
     P = probs[0].numel() // C_
     out = torch.empty(P, dtype=torch.float32, device=probs[0].device)
     kept = torch.empty_like(out) if want_kept else None
-    call("dct_pl_map_fwd", _ptr_array(probs), len(probs), int(teacher), float(tau), float(eps), ptr(out), ptr(kept), P, C_, stream())
+    call(entry, _ptr_array(probs), len(probs), int(teacher), float(tau), *map(float, scalars), ptr(out), ptr(kept), P, C_, stream())
     return out, kept
 
 
-def pl_map_bwd(probs: List[torch.Tensor], dmap, C_, teacher=PL_CROSS, tau=0.0, eps=1e-10):
+def _cons_map_bwd(entry, probs, dmap, C_, teacher, tau, scalars):
     outs = [torch.empty_like(p) for p in probs]
-    call("dct_pl_map_bwd", _ptr_array(probs), len(probs), int(teacher), float(tau), float(eps), ptr(dmap), _ptr_array(outs),
+    call(entry, _ptr_array(probs), len(probs), int(teacher), float(tau), *map(float, scalars), ptr(dmap), _ptr_array(outs),
          probs[0].numel() // C_, C_, stream())
     return outs
+
+
+def _cons_logits_step(entry, logits, C_, dlogits, want_probs, gscale, gmul, accumulate, teacher, tau, scalars):
+    dev = logits[0].device
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = _loss_ws(dev)
+    probs = [torch.empty_like(lp) for lp in logits] if want_probs else None
+    call(entry, _ptr_array(logits), len(logits), int(teacher), float(tau), *map(float, scalars), logits[0].numel() // C_, C_, ptr(out),
+         _ptr_array(probs) if probs is not None else None, ptr(gscale), float(gmul),
+         _ptr_array(dlogits) if dlogits is not None else None, int(accumulate), ptr(ws), ws.numel(), stream())
+    return out, probs
+
+
+def pl_map_fwd(probs: List[torch.Tensor], C_, teacher=PL_CROSS, tau=0.0, eps=1e-10, want_kept: bool = True):
+    """-> (map [P], kept map [P] or None) of the pseudo-label consistency term over S probability maps (the rule: include/dct.h, dct_pl_*)."""
+    return _cons_map_fwd("dct_pl_map_fwd", probs, C_, teacher, tau, (eps,), want_kept)
+
+
+def pl_map_bwd(probs: List[torch.Tensor], dmap, C_, teacher=PL_CROSS, tau=0.0, eps=1e-10):
+    return _cons_map_bwd("dct_pl_map_bwd", probs, dmap, C_, teacher, tau, (eps,))
 
 
 def pl_logits_step(logits: List[torch.Tensor], C_, dlogits: List[torch.Tensor] = None, want_probs: bool = True, gscale=None, gmul=1.0,
                    accumulate=False, teacher=PL_CROSS, tau=0.0, eps=1e-10):
     """-> (out2 = (mean loss over all pixels, kept fraction), [softmax(logits_s)] or None): the pseudo-label consistency term of the step from
     logits, its S softmax maps and its logit gradients into ``dlogits`` (None: no gradients) in ONE pass + the finalize (dct_pl_logits_step)."""
-    dev = logits[0].device
-    out = torch.empty(2, dtype=torch.float32, device=dev)
-    ws = _loss_ws(dev)
-    probs = [torch.empty_like(lp) for lp in logits] if want_probs else None
-    call("dct_pl_logits_step", _ptr_array(logits), len(logits), int(teacher), float(tau), float(eps), logits[0].numel() // C_, C_, ptr(out),
-         _ptr_array(probs) if probs is not None else None, ptr(gscale), float(gmul),
-         _ptr_array(dlogits) if dlogits is not None else None, int(accumulate), ptr(ws), ws.numel(), stream())
-    return out, probs
+    return _cons_logits_step("dct_pl_logits_step", logits, C_, dlogits, want_probs, gscale, gmul, accumulate, teacher, tau, (eps,))
 
 
 def spl_map_fwd(probs: List[torch.Tensor], C_, teacher=PL_CROSS, tau=0.0, temperature=0.5, eps=1e-10, want_kept: bool = True):
     """-> (map [P], kept map [P] or None) of the soft pseudo-label consistency term (sharpened teachers) over S probability maps (the rule:
     include/dct.h, dct_spl_*)."""
-    P = probs[0].numel() // C_
-    out = torch.empty(P, dtype=torch.float32, device=probs[0].device)
-    kept = torch.empty_like(out) if want_kept else None
-    call("dct_spl_map_fwd", _ptr_array(probs), len(probs), int(teacher), float(tau), float(temperature), float(eps), ptr(out), ptr(kept), P, C_,
-         stream())
-    return out, kept
+    return _cons_map_fwd("dct_spl_map_fwd", probs, C_, teacher, tau, (temperature, eps), want_kept)
 
 
 def spl_map_bwd(probs: List[torch.Tensor], dmap, C_, teacher=PL_CROSS, tau=0.0, temperature=0.5, eps=1e-10):
-    outs = [torch.empty_like(p) for p in probs]
-    call("dct_spl_map_bwd", _ptr_array(probs), len(probs), int(teacher), float(tau), float(temperature), float(eps), ptr(dmap), _ptr_array(outs),
-         probs[0].numel() // C_, C_, stream())
-    return outs
+    return _cons_map_bwd("dct_spl_map_bwd", probs, dmap, C_, teacher, tau, (temperature, eps))
 
 
 def spl_logits_step(logits: List[torch.Tensor], C_, dlogits: List[torch.Tensor] = None, want_probs: bool = True, gscale=None, gmul=1.0,
                     accumulate=False, teacher=PL_CROSS, tau=0.0, temperature=0.5, eps=1e-10):
     """`pl_logits_step` with sharpened soft teachers: -> (out2 = (mean loss over all pixels, kept fraction), [softmax(logits_s)] or None), the
     logit gradients into ``dlogits`` (None: no gradients), in ONE pass + the finalize (dct_spl_logits_step)."""
-    dev = logits[0].device
-    out = torch.empty(2, dtype=torch.float32, device=dev)
-    ws = _loss_ws(dev)
-    probs = [torch.empty_like(lp) for lp in logits] if want_probs else None
-    call("dct_spl_logits_step", _ptr_array(logits), len(logits), int(teacher), float(tau), float(temperature), float(eps),
-         logits[0].numel() // C_, C_, ptr(out), _ptr_array(probs) if probs is not None else None, ptr(gscale), float(gmul),
-         _ptr_array(dlogits) if dlogits is not None else None, int(accumulate), ptr(ws), ws.numel(), stream())
-    return out, probs
+    return _cons_logits_step("dct_spl_logits_step", logits, C_, dlogits, want_probs, gscale, gmul, accumulate, teacher, tau, (temperature, eps))
 
 
 def mse_map_fwd(probs: List[torch.Tensor], C_, teacher=PL_CROSS, tau=0.0, want_kept: bool = True):
     """-> (map [P], kept map [P] or None) of the softmax-MSE consistency term over S probability maps (the rule: include/dct.h, dct_mse_*)."""
-    P = probs[0].numel() // C_
-    out = torch.empty(P, dtype=torch.float32, device=probs[0].device)
-    kept = torch.empty_like(out) if want_kept else None
-    call("dct_mse_map_fwd", _ptr_array(probs), len(probs), int(teacher), float(tau), ptr(out), ptr(kept), P, C_, stream())
-    return out, kept
+    return _cons_map_fwd("dct_mse_map_fwd", probs, C_, teacher, tau, (), want_kept)
 
 
 def mse_map_bwd(probs: List[torch.Tensor], dmap, C_, teacher=PL_CROSS, tau=0.0):
-    outs = [torch.empty_like(p) for p in probs]
-    call("dct_mse_map_bwd", _ptr_array(probs), len(probs), int(teacher), float(tau), ptr(dmap), _ptr_array(outs), probs[0].numel() // C_, C_,
-         stream())
-    return outs
+    return _cons_map_bwd("dct_mse_map_bwd", probs, dmap, C_, teacher, tau, ())
 
 
 def mse_logits_step(logits: List[torch.Tensor], C_, dlogits: List[torch.Tensor] = None, want_probs: bool = True, gscale=None, gmul=1.0,
                     accumulate=False, teacher=PL_CROSS, tau=0.0):
     """`pl_logits_step` with the squared distance between the softmax outputs: -> (out2 = (mean loss over all pixels, kept fraction),
     [softmax(logits_s)] or None), the logit gradients into ``dlogits`` (None: no gradients), in ONE pass + the finalize (dct_mse_logits_step)."""
-    dev = logits[0].device
-    out = torch.empty(2, dtype=torch.float32, device=dev)
-    ws = _loss_ws(dev)
-    probs = [torch.empty_like(lp) for lp in logits] if want_probs else None
-    call("dct_mse_logits_step", _ptr_array(logits), len(logits), int(teacher), float(tau), logits[0].numel() // C_, C_, ptr(out),
-         _ptr_array(probs) if probs is not None else None, ptr(gscale), float(gmul),
-         _ptr_array(dlogits) if dlogits is not None else None, int(accumulate), ptr(ws), ws.numel(), stream())
-    return out, probs
+    return _cons_logits_step("dct_mse_logits_step", logits, C_, dlogits, want_probs, gscale, gmul, accumulate, teacher, tau, ())
 
 
 def kl_logits_fwd(p_logits, y_logits, C_, eps=1e-10):

@@ -662,16 +662,16 @@ class JSD_2D(nn.Module):
         return _JSDMapFn.apply(*input)
 
 
-class _PLMapFn(torch.autograd.Function):
-    """The pseudo-label consistency map on dct_pl_map_*; ``rule``: ``PseudoLabel_2D.launch_args()``.  Returns the [B,H,W] map and, without a
-    gradient, the per-pixel kept map.  Nothing but the inputs is saved: the backward recomputes the teachers."""
+class _ConsMapFn(torch.autograd.Function):
+    """A view-consistency map on dct_{pl,spl,mse}_map_*; ``family``: the criterion's ``family``, ``rule``: its ``launch_args()``.  Returns
+    the [B,H,W] map and, without a gradient, the per-pixel kept map.  Nothing but the inputs is saved: the backward recomputes the teachers."""
 
     @staticmethod
-    def forward(ctx, rule, *probs):
+    def forward(ctx, family, rule, *probs):
         pps = [_pc(p) for p in probs]
         ctx.save_for_backward(*pps)
-        ctx.rule = rule
-        out, kept = K.pl_map_fwd(pps, pps[0].shape[3], **rule)
+        ctx.family, ctx.rule = family, rule
+        out, kept = getattr(K, family + "_map_fwd")(pps, pps[0].shape[3], **rule)
         kept = kept.view(pps[0].shape[:3])
         ctx.mark_non_differentiable(kept)
         return out.view(pps[0].shape[:3]), kept
@@ -679,38 +679,32 @@ class _PLMapFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _):
         pps = list(ctx.saved_tensors)
-        dps = K.pl_map_bwd(pps, g.to(torch.float32).contiguous().view(-1), pps[0].shape[3], **ctx.rule)
-        return (None,) + tuple(_nchw(d) for d in dps)
+        dps = getattr(K, ctx.family + "_map_bwd")(pps, g.to(torch.float32).contiguous().view(-1), pps[0].shape[3], **ctx.rule)
+        return (None, None) + tuple(_nchw(d) for d in dps)
 
 
-class PseudoLabel_2D(nn.Module):
-    """Hard pseudo-label consistency of S views (the rule: include/dct.h, dct_pl_*), with ``JSD_2D``'s call shape: a list of [B,C,H,W]
-    probabilities in, a [B,H,W] map out, whose mean over ALL pixels is the loss.  ``teacher='cross'``: cross pseudo supervision, every
-    view learns the argmax of every other view (2 or more views); ``teacher='ensemble'``: every view learns the argmax of the summed
-    probabilities.  ``threshold``: a teacher whose confidence (its maximum probability; for the ensemble the mean of the views') is below
-    it is masked out; 0 keeps every teacher.  Teachers are constants: no gradient flows through argmax, confidence or mask.  After a
-    call ``last_kept`` is a device scalar, the kept fraction of the teacher terms (nothing synchronises)."""
+class _ViewConsistency_2D(nn.Module):
+    """What the view-consistency criteria share: a list of [B,C,H,W] probabilities in, a [B,H,W] map out, whose mean over ALL pixels is the
+    loss; a teacher mode, a confidence threshold and (the logarithmic ones) eps; ``last_kept``.  A criterion names its ``family`` (the
+    prefix of its hip_ops functions) and its ``launch_args()``.  The public criteria are unrelated to each other beyond this base: the
+    trainer tells them apart by exact type."""
+    family = None
 
-    def __init__(self, teacher='cross', threshold=0.0, eps=1e-10):
+    def __init__(self, teacher):
         super().__init__()
-        name = type(self).__name__
         if teacher not in K.PL_TEACHERS:
-            raise ValueError(f"dct_amd {name}: teacher must be 'cross' or 'ensemble', got {teacher!r}")
+            raise ValueError(f"dct_amd {type(self).__name__}: teacher must be 'cross' or 'ensemble', got {teacher!r}")
         self.teacher = teacher
-        try:
-            self.threshold, self.eps = float(threshold), float(eps)
-        except (TypeError, ValueError):
-            raise ValueError(f"dct_amd {name}: threshold and eps must be numbers, got {threshold!r}, {eps!r}")
-        if not (0.0 <= self.threshold <= float('inf')):
-            raise ValueError(f"dct_amd {name}: threshold must be >= 0, got {threshold}")
-        # (eps is handed to the kernels as fp32: one that rounds to 0 there would put log(0) back)
-        if not (0.0 < self.eps < float('inf')) or float(torch.tensor(self.eps, dtype=torch.float32)) == 0.0:
-            raise ValueError(f"dct_amd {name}: eps must be finite and > 0 in fp32, got {eps}")
         self.last_kept = None
 
-    def launch_args(self):
-        """The keyword arguments of hip_ops.pl_* (and what a captured step is valid for)."""
-        return dict(teacher=K.PL_TEACHERS[self.teacher], tau=self.threshold, eps=self.eps)
+    def _check_threshold(self, threshold):
+        if not (0.0 <= self.threshold <= float('inf')):
+            raise ValueError(f"dct_amd {type(self).__name__}: threshold must be >= 0, got {threshold}")
+
+    def _check_eps(self, eps):
+        # (eps is handed to the kernels as fp32: one that rounds to 0 there would put log(0) back)
+        if not (0.0 < self.eps < float('inf')) or float(torch.tensor(self.eps, dtype=torch.float32)) == 0.0:
+            raise ValueError(f"dct_amd {type(self).__name__}: eps must be finite and > 0 in fp32, got {eps}")
 
     def min_views(self):
         return 2 if self.teacher == 'cross' else 1
@@ -727,9 +721,32 @@ class PseudoLabel_2D(nn.Module):
         if DEBUG_ASSERTS:
             for inprob in input:
                 assert _simplex(inprob, 1)
-        out, kept = _PLMapFn.apply(self.launch_args(), *input)
+        out, kept = _ConsMapFn.apply(self.family, self.launch_args(), *input)
         self.last_kept = kept.mean()
         return out
+
+
+class PseudoLabel_2D(_ViewConsistency_2D):
+    """Hard pseudo-label consistency of S views (the rule: include/dct.h, dct_pl_*), with ``JSD_2D``'s call shape: a list of [B,C,H,W]
+    probabilities in, a [B,H,W] map out, whose mean over ALL pixels is the loss.  ``teacher='cross'``: cross pseudo supervision, every
+    view learns the argmax of every other view (2 or more views); ``teacher='ensemble'``: every view learns the argmax of the summed
+    probabilities.  ``threshold``: a teacher whose confidence (its maximum probability; for the ensemble the mean of the views') is below
+    it is masked out; 0 keeps every teacher.  Teachers are constants: no gradient flows through argmax, confidence or mask.  After a
+    call ``last_kept`` is a device scalar, the kept fraction of the teacher terms (nothing synchronises)."""
+    family = 'pl'
+
+    def __init__(self, teacher='cross', threshold=0.0, eps=1e-10):
+        super().__init__(teacher)
+        try:
+            self.threshold, self.eps = float(threshold), float(eps)
+        except (TypeError, ValueError):
+            raise ValueError(f"dct_amd {type(self).__name__}: threshold and eps must be numbers, got {threshold!r}, {eps!r}")
+        self._check_threshold(threshold)
+        self._check_eps(eps)
+
+    def launch_args(self):
+        """The keyword arguments of hip_ops.pl_* (and what a captured step is valid for)."""
+        return dict(teacher=K.PL_TEACHERS[self.teacher], tau=self.threshold, eps=self.eps)
 
 
 class CrossPseudoSupervision_2D(PseudoLabel_2D):
@@ -746,28 +763,7 @@ class EnsemblePseudoLabel_2D(PseudoLabel_2D):
         super().__init__('ensemble', threshold, eps)
 
 
-class _SPLMapFn(torch.autograd.Function):
-    """The soft pseudo-label consistency map on dct_spl_map_*; ``rule``: ``SoftPseudoLabel_2D.launch_args()``.  As ``_PLMapFn``: nothing
-    but the inputs is saved, the backward recomputes the sharpened teachers."""
-
-    @staticmethod
-    def forward(ctx, rule, *probs):
-        pps = [_pc(p) for p in probs]
-        ctx.save_for_backward(*pps)
-        ctx.rule = rule
-        out, kept = K.spl_map_fwd(pps, pps[0].shape[3], **rule)
-        kept = kept.view(pps[0].shape[:3])
-        ctx.mark_non_differentiable(kept)
-        return out.view(pps[0].shape[:3]), kept
-
-    @staticmethod
-    def backward(ctx, g, _):
-        pps = list(ctx.saved_tensors)
-        dps = K.spl_map_bwd(pps, g.to(torch.float32).contiguous().view(-1), pps[0].shape[3], **ctx.rule)
-        return (None,) + tuple(_nchw(d) for d in dps)
-
-
-class SoftPseudoLabel_2D(nn.Module):
+class SoftPseudoLabel_2D(_ViewConsistency_2D):
     """Soft pseudo-label consistency of S views (the rule: include/dct.h, dct_spl_*), with ``PseudoLabel_2D``'s call shape: a list of
     [B,C,H,W] probabilities in, a [B,H,W] map out, whose mean over ALL pixels is the loss.  The teacher is the other views' prediction
     (``teacher='cross'``, 2 or more views) or the summed prediction (``teacher='ensemble'``), sharpened with ``temperature`` T as
@@ -775,13 +771,11 @@ class SoftPseudoLabel_2D(nn.Module):
     pseudo-label.  ``threshold`` masks a teacher by its raw confidence, before sharpening.  Teachers are constants.  After a call
     ``last_kept`` is a device scalar, the kept fraction of the teacher terms (nothing synchronises).
     Not a ``PseudoLabel_2D``: the trainer tells the criteria apart by exact type."""
+    family = 'spl'
 
     def __init__(self, teacher='cross', temperature=0.5, threshold=0.0, eps=1e-10):
-        super().__init__()
+        super().__init__(teacher)
         name = type(self).__name__
-        if teacher not in K.PL_TEACHERS:
-            raise ValueError(f"dct_amd {name}: teacher must be 'cross' or 'ensemble', got {teacher!r}")
-        self.teacher = teacher
         try:
             self.temperature, self.threshold, self.eps = float(temperature), float(threshold), float(eps)
         except (TypeError, ValueError):
@@ -791,34 +785,12 @@ class SoftPseudoLabel_2D(nn.Module):
         r32 = 1.0 / t32
         if not (0.0 < float(t32) < float('inf')) or not (0.0 < float(r32) < float('inf')):
             raise ValueError(f"dct_amd {name}: temperature and 1 / temperature must be finite and > 0 in fp32, got {temperature}")
-        if not (0.0 <= self.threshold <= float('inf')):
-            raise ValueError(f"dct_amd {name}: threshold must be >= 0, got {threshold}")
-        if not (0.0 < self.eps < float('inf')) or float(torch.tensor(self.eps, dtype=torch.float32)) == 0.0:
-            raise ValueError(f"dct_amd {name}: eps must be finite and > 0 in fp32, got {eps}")
-        self.last_kept = None
+        self._check_threshold(threshold)
+        self._check_eps(eps)
 
     def launch_args(self):
         """The keyword arguments of hip_ops.spl_* (and what a captured step is valid for)."""
         return dict(teacher=K.PL_TEACHERS[self.teacher], tau=self.threshold, temperature=self.temperature, eps=self.eps)
-
-    def min_views(self):
-        return 2 if self.teacher == 'cross' else 1
-
-    def forward(self, input: List[torch.Tensor]):
-        input = list(input)
-        name = type(self).__name__
-        if len(input) < self.min_views():
-            raise ValueError(f"dct_amd {name}: teacher='{self.teacher}' needs at least {self.min_views()} views, got {len(input)}")
-        if len(input) > MAX_VIEWS:
-            raise ValueError(f"dct_amd {name} handles up to {MAX_VIEWS} views per call, got {len(input)}")
-        if not all(p.is_cuda for p in input):
-            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
-        if DEBUG_ASSERTS:
-            for inprob in input:
-                assert _simplex(inprob, 1)
-        out, kept = _SPLMapFn.apply(self.launch_args(), *input)
-        self.last_kept = kept.mean()
-        return out
 
 
 class SoftCrossPseudoSupervision_2D(SoftPseudoLabel_2D):
@@ -836,28 +808,7 @@ class SoftEnsemblePseudoLabel_2D(SoftPseudoLabel_2D):
         super().__init__('ensemble', temperature, threshold, eps)
 
 
-class _MSEMapFn(torch.autograd.Function):
-    """The softmax-MSE consistency map on dct_mse_map_*; ``rule``: ``MSEConsistency_2D.launch_args()``.  As ``_PLMapFn``: nothing but the
-    inputs is saved, the backward recomputes the masks."""
-
-    @staticmethod
-    def forward(ctx, rule, *probs):
-        pps = [_pc(p) for p in probs]
-        ctx.save_for_backward(*pps)
-        ctx.rule = rule
-        out, kept = K.mse_map_fwd(pps, pps[0].shape[3], **rule)
-        kept = kept.view(pps[0].shape[:3])
-        ctx.mark_non_differentiable(kept)
-        return out.view(pps[0].shape[:3]), kept
-
-    @staticmethod
-    def backward(ctx, g, _):
-        pps = list(ctx.saved_tensors)
-        dps = K.mse_map_bwd(pps, g.to(torch.float32).contiguous().view(-1), pps[0].shape[3], **ctx.rule)
-        return (None,) + tuple(_nchw(d) for d in dps)
-
-
-class MSEConsistency_2D(nn.Module):
+class MSEConsistency_2D(_ViewConsistency_2D):
     """Softmax-MSE consistency of S views (the rule: include/dct.h, dct_mse_*), with ``PseudoLabel_2D``'s call shape: a list of [B,C,H,W]
     probabilities in, a [B,H,W] map out, whose mean over ALL pixels is the loss.  Every view is pulled towards every other view's
     prediction (``teacher='cross'``, 2 or more views) or towards the mean prediction (``teacher='ensemble'``) by the squared distance,
@@ -865,43 +816,19 @@ class MSEConsistency_2D(nn.Module):
     the pseudo-label criteria; 0 keeps every teacher.  Teachers are constants.  After a call ``last_kept`` is a device scalar, the kept
     fraction of the teacher terms (nothing synchronises).
     Not a ``PseudoLabel_2D``: the trainer tells the criteria apart by exact type."""
+    family = 'mse'
 
     def __init__(self, teacher='cross', threshold=0.0):
-        super().__init__()
-        name = type(self).__name__
-        if teacher not in K.PL_TEACHERS:
-            raise ValueError(f"dct_amd {name}: teacher must be 'cross' or 'ensemble', got {teacher!r}")
-        self.teacher = teacher
+        super().__init__(teacher)
         try:
             self.threshold = float(threshold)
         except (TypeError, ValueError):
-            raise ValueError(f"dct_amd {name}: threshold must be a number, got {threshold!r}")
-        if not (0.0 <= self.threshold <= float('inf')):
-            raise ValueError(f"dct_amd {name}: threshold must be >= 0, got {threshold}")
-        self.last_kept = None
+            raise ValueError(f"dct_amd {type(self).__name__}: threshold must be a number, got {threshold!r}")
+        self._check_threshold(threshold)
 
     def launch_args(self):
         """The keyword arguments of hip_ops.mse_* (and what a captured step is valid for)."""
         return dict(teacher=K.PL_TEACHERS[self.teacher], tau=self.threshold)
-
-    def min_views(self):
-        return 2 if self.teacher == 'cross' else 1
-
-    def forward(self, input: List[torch.Tensor]):
-        input = list(input)
-        name = type(self).__name__
-        if len(input) < self.min_views():
-            raise ValueError(f"dct_amd {name}: teacher='{self.teacher}' needs at least {self.min_views()} views, got {len(input)}")
-        if len(input) > MAX_VIEWS:
-            raise ValueError(f"dct_amd {name} handles up to {MAX_VIEWS} views per call, got {len(input)}")
-        if not all(p.is_cuda for p in input):
-            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
-        if DEBUG_ASSERTS:
-            for inprob in input:
-                assert _simplex(inprob, 1)
-        out, kept = _MSEMapFn.apply(self.launch_args(), *input)
-        self.last_kept = kept.mean()
-        return out
 
 
 class CrossMSE_2D(MSEConsistency_2D):

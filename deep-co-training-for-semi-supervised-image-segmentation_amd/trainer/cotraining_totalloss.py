@@ -115,10 +115,10 @@ class ExecutionPlan:
 class _StepContext(object):
     """What one issue of the step carries from its forward passes to its optimizers; dropped when the step returns (the join closure
     holds this step's streams, the pass buffers' owners its tapes)."""
-    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice", "pl", "focal", "topk", "tversky", "spl", "mse")
+    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice", "cons", "focal", "topk", "tversky")
 
-    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None, pl=None, focal=None, topk=None,
-                 spl=None, mse=None, tversky=None):
+    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None, cons=None, focal=None, topk=None,
+                 tversky=None):
         self.sched, self.route = sched, route
         # the gradient exchange as far as it is issued from inside the step (between two graphs it is the replay's business)
         self.sync = grad_sync if any(e in ("model", "buckets") for e in route.exchange) else None
@@ -133,11 +133,9 @@ class _StepContext(object):
         self.ignore = ignore
         self.ce_weight = ce_weight          # the supervised criterion's fp32 class weights on the device, or None (all ones)
         self.ce_dice = ce_dice              # a Dice / CE + Dice criterion's launch arguments (CrossEntropyDiceLoss2d.launch_args), or None
-        self.pl = pl                        # a pseudo-label consistency criterion's launch arguments (PseudoLabel_2D.launch_args), or None: JSD
+        self.cons = cons                    # a view-consistency criterion's (family, launch arguments) (PseudoLabel_2D, SoftPseudoLabel_2D, MSEConsistency_2D), or None: JSD
         self.focal = focal                  # a focal criterion's launch arguments (FocalLoss2d.launch_args), or None
         self.topk = topk                    # a top-k criterion's launch arguments (TopKCrossEntropyLoss2d.launch_args), or None
-        self.spl = spl                      # a soft pseudo-label consistency criterion's launch arguments (SoftPseudoLabel_2D.launch_args), or None
-        self.mse = mse                      # a softmax-MSE consistency criterion's launch arguments (MSEConsistency_2D.launch_args), or None
         self.tversky = tversky              # a Tversky / focal Tversky / CE + Tversky criterion's launch arguments (CrossEntropyTverskyLoss2d.launch_args), or None
 
     def on(self, streams, i):
@@ -500,20 +498,13 @@ class CoTrainer(Trainer):
 
     def _jsd(self, ctx, lps, dl_outs):
         """Value, the S softmax maps and the S logit gradients in ONE pass over the logits (dct_jsd_logits_step: bit for bit the five
-        separate launches; dct_pl_logits_step when the consistency criterion is a pseudo-label one, dct_spl_logits_step when it is a soft
-        pseudo-label one, dct_mse_logits_step when it is a softmax-MSE one: their ``last_kept`` is set to the kept fraction on the device).  -> (value, NCHW softmax maps)."""
+        separate launches; dct_{pl,spl,mse}_logits_step when the consistency criterion is a pseudo-label, soft pseudo-label or softmax-MSE
+        one: its ``last_kept`` is set to the kept fraction on the device).  -> (value, NCHW softmax maps)."""
         from .. import hip_ops as K
         from ..loss.loss import _nchw
-        if ctx.mse is not None:
-            out2, probs = K.mse_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot, **ctx.mse)
-            self.criterions['jsd'].last_kept = out2[1]
-            return out2[0], [_nchw(p_) for p_ in probs]
-        if ctx.spl is not None:
-            out2, probs = K.spl_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot, **ctx.spl)
-            self.criterions['jsd'].last_kept = out2[1]
-            return out2[0], [_nchw(p_) for p_ in probs]
-        if ctx.pl is not None:
-            out2, probs = K.pl_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot, **ctx.pl)
+        if ctx.cons is not None:
+            family, rule = ctx.cons
+            out2, probs = getattr(K, family + "_logits_step")(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot, **rule)
             self.criterions['jsd'].last_kept = out2[1]
             return out2[0], [_nchw(p_) for p_ in probs]
         jsd1, probs = K.jsd_logits_step(lps, self.C, dl_outs if ctx.lam_cot != 0.0 else None, True, **ctx.g_cot)
@@ -699,18 +690,15 @@ class CoTrainer(Trainer):
         ``lam_dev`` (float32[2] device tensor holding lambda_cot, lambda_adv): the loss weights are then read on the
         device, as a captured graph needs."""
         nets = [s.torchnet for s in self.segmentators]
-        from ..loss.loss import CrossEntropyTverskyLoss2d, FocalLoss2d, MSEConsistency_2D, SoftPseudoLabel_2D, TopKCrossEntropyLoss2d
+        from ..loss.loss import CrossEntropyTverskyLoss2d, FocalLoss2d, TopKCrossEntropyLoss2d
         sup, cons = self.criterions['sup'], self.criterions['jsd']
         rule = sup.launch_args(self.C) if hasattr(sup, "launch_args") else None
         focal, topk, tversky = type(sup) is FocalLoss2d, type(sup) is TopKCrossEntropyLoss2d, isinstance(sup, CrossEntropyTverskyLoss2d)
-        soft = isinstance(cons, SoftPseudoLabel_2D)         # (only the three exact types reach the fused step: _step_facts)
-        mse = isinstance(cons, MSEConsistency_2D)           # (likewise)
         ctx = _StepContext(self._sched, route, self.grad_sync, (float(self.cot_scheduler.value), float(self.adv_scheduler.value)),
                            lam_dev, sup.ignore_index, sup.device_weight(self.device, self.C),
                            None if focal or topk or tversky else rule,
-                           cons.launch_args() if hasattr(cons, "launch_args") and not soft and not mse else None,
-                           rule if focal else None, rule if topk else None, tversky=rule if tversky else None,
-                           spl=cons.launch_args() if soft else None, mse=cons.launch_args() if mse else None)
+                           (cons.family, cons.launch_args()) if hasattr(cons, "launch_args") else None,   # (JSD_2D has none)
+                           rule if focal else None, rule if topk else None, tversky=rule if tversky else None)
         streams = self._streams() if route.model_streams else None
         if train_adv and route.kind != "sequential" and step_route.adv_settings(self.adv_training_dict)[0] != 'fgsm':
             raise RuntimeError(f"dct_amd: the {route.kind} layout is scheduled around FGSM; the planner routes other generators sequentially")

@@ -63,7 +63,7 @@ def _logits(P, S, C):
         xs[s][sen, s % C] = MARGIN_UFL
         xs[s][tie] = 0.0
     for n_, i in enumerate(tie):
-        if n_ % 2:
+        if n_ % 2 and S > 1:               # (a single view has no partner to mirror)
             xs[0][i, 0], xs[0][i, 1] = 1.5, -0.5
             xs[1][i, 0], xs[1][i, 1] = -0.5, 1.5
     return tuple(xs)
@@ -252,6 +252,18 @@ def test_step_kernel(ops, P, S, C, teacher):
         if tau == 0.0 and teacher == "cross":
             # the sentinels are exactly one-hot after softmax_px, so the float64 value there is the closed form
             np.testing.assert_allclose(v[sen].numpy(), _sentinel_value(S, C), rtol=1e-15)
+
+
+CLASS_SWEEP = [(S, C, teacher) for C in range(2, 9) for S in (1, 2, 3, 5) for teacher in TEACHERS if S > 1 or teacher == "ensemble"]
+
+
+@pytest.mark.parametrize("S,C,teacher", CLASS_SWEEP)
+def test_every_class_count_of_the_dispatch(ops, S, C, teacher):
+    """The dispatch instantiates C = 2..8 and the grids above use 2, 4 and 8: the map kernels and the step kernel at every C, at 257
+    pixels (one full block and a grid-stride tail of one pixel), S = 2, 3, 5 (every SMAX instantiation) and the ensemble's single
+    view; the references, thresholds and bounds are the tests' above, which this runs as they are."""
+    test_map_kernels(ops, 257, S, C, teacher)
+    test_step_kernel(ops, 257, S, C, teacher)
 
 
 @pytest.mark.parametrize("teacher,S", [("cross", 2), ("cross", 3), ("cross", 5), ("cross", 8), ("ensemble", 1), ("ensemble", 2)])

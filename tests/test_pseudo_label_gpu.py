@@ -63,7 +63,7 @@ def _logits(P, S, C):
         xs[s][sen, s % C] = MARGIN_UFL
         xs[s][tie] = 0.0
     for n_, i in enumerate(tie):
-        if n_ % 2:
+        if n_ % 2 and S > 1:               # (a single view has no partner to mirror)
             xs[0][i, 0], xs[0][i, 1] = 1.5, -0.5
             xs[1][i, 0], xs[1][i, 1] = -0.5, 1.5
     return xs
@@ -156,7 +156,7 @@ def test_map_kernels(ops, P, S, C, teacher):
         for s in range(S):
             ref = dmap.double()[:, None] * d[s]
             _check(dps[s], ref, (drel + U) * ref.abs() + TINY, what + f" dprobs {s}")
-        if tau == 0.0 and S <= C:
+        if tau == 0.0 and 1 < S <= C:
             # the sentinels (one-hot views of distinct classes): every term of a student on another view's class is log(0 + eps) = -23.03;
             # the ensemble votes class 0 (all sums tie), which view 0 itself holds with p = 1: S - 1 such terms
             w = R.weight(teacher, S)
@@ -221,6 +221,18 @@ def test_step_kernel(ops, P, S, C, teacher):
             gref, gb = grads[s]
             _check(dls[s], gref, gb, what + f" dlogits {s}")
             assert (dls[s].cpu()[(n[s] == 0).all(1)] == 0).all(), what                  # a student without a teacher term: exactly 0
+
+
+CLASS_SWEEP = [(S, C, teacher) for C in range(2, 9) for S in (1, 2, 3, 5) for teacher in TEACHERS if S > 1 or teacher == "ensemble"]
+
+
+@pytest.mark.parametrize("S,C,teacher", CLASS_SWEEP)
+def test_every_class_count_of_the_dispatch(ops, S, C, teacher):
+    """The dispatch instantiates C = 2..8 and the grids above use 2, 4 and 8: the map kernels and the step kernel at every C, at 257
+    pixels (one full block and a grid-stride tail of one pixel), S = 2, 3, 5 (every SMAX instantiation) and the ensemble's single
+    view; the references, thresholds and bounds are the tests' above, which this runs as they are."""
+    test_map_kernels(ops, 257, S, C, teacher)
+    test_step_kernel(ops, 257, S, C, teacher)
 
 
 def test_status_codes(ops):
