@@ -549,14 +549,18 @@ __global__ __launch_bounds__(256) void bd_bwd_kernel(const float* logits, const 
   }
 }
 
-// ---- soft Dice and CE + Dice (the rule: include/dct.h) ---------------------------------------------------------------------------------
+// ---- the overlap criteria: soft Dice, Tversky and focal Tversky, alone or beside CE (the rules: include/dct.h) -------------------------------
+// One kernel family over a rule (DiceTerms, TverskyTerms): the rule is the step from a group's sums {I, S, Y} to (index, term, qa, qb) and
+// the line from the masked sum of terms to the reported value, evaluated per block (and by one thread per group for the outputs), never
+// per pixel.  The forward kernel, the folds and the per-pixel gradient know no rule.
 // Grid: x walks one image's pixels, y is the image (dice_kernel's choice), so a block's partial row is one image's and a group's sums
 // depend on that group's pixels alone.  A row is NS = 3 C + 2 floats: {sum w l, sum w, then I, S, Y per class}.  A sum is folded in one
 // fixed order wherever it is formed: over all rows by a block (fold_rows: thread tid takes rows tid, tid + 256, ... in order, then the wave
 // shuffle, then the four wave sums), over one image's rows by a wave (wave_fold_rows).
 constexpr int kDiceFwdBlocks = 512;      // rows every backward block folds: kept small (the fold is L2 traffic per backward block)
 constexpr int kDiceBwdBlocks = 1024;
-struct DiceRule { int mask, per_image; float smooth, ce_coef, dice_coef, inv_gk; };
+// what every overlap rule shares: coef weighs the overlap term beside ce_coef's cross entropy, inv_gk = 1 / (G K)
+struct OverlapArgs { int mask, per_image; float smooth, ce_coef, coef, inv_gk; };
 
 template <int N> __device__ __forceinline__ void block_partial_n(const float a[N], float* row) {
   __shared__ float sm[4 * N];
@@ -593,7 +597,7 @@ __device__ __forceinline__ void fold_rows(const float* partial, int first, int c
 }
 // The same sums by ONE wave, in every lane: lane l takes rows l, l + 64, ... in order, then the wave shuffle.  This is the order of a group's
 // sums under per_image (a group is one image's rows, at most kDiceFwdBlocks / B of them): no LDS and no barrier, so the four waves of
-// ce_dice_finish fold four groups at a time and a backward block's waves each fold their image's rows for themselves.
+// overlap_finish fold four groups at a time and a backward block's waves each fold their image's rows for themselves.
 template <int NS, int OFF, int N>
 __device__ __forceinline__ void wave_fold_rows(const float* partial, int first, int count, float out[N]) {
   float a[N];
@@ -609,7 +613,7 @@ __device__ __forceinline__ void wave_fold_rows(const float* partial, int first, 
 }
 // {sum w l, sum w} over every row and group g's {I, S, Y} per class: the one group of the whole batch folds all columns of all rows at once
 template <int C>
-__device__ __forceinline__ void ce_dice_fold(const float* partial, int B, int fbx, int per_image, int g, float* sm, float ce2[2], float d[3 * C]) {
+__device__ __forceinline__ void overlap_fold(const float* partial, int B, int fbx, int per_image, int g, float* sm, float ce2[2], float d[3 * C]) {
   constexpr int NS = 3 * C + 2;
   if (!per_image) {
     float a[NS];
@@ -622,77 +626,118 @@ __device__ __forceinline__ void ce_dice_fold(const float* partial, int B, int fb
     wave_fold_rows<NS, 2, 3 * C>(partial, g * fbx, fbx, d);
   }
 }
-// D = (2 I + smooth) / (S + Y + smooth), alpha = 2 / (S + Y + smooth), beta = D / (S + Y + smooth); an empty denominator: D = 1, no gradient
-__device__ __forceinline__ void dice_terms(float I, float S, float Y, float smooth, float& D, float& alpha, float& beta) {
-#pragma clang fp contract(off)    // one rounding per operation wherever this is inlined: _step's numbers are _fwd's and _bwd's
-  const float den = (S + Y) + smooth;
-  const float num = 2.f * I + smooth;
-  const bool empty = den == 0.f;
-  D = empty ? 1.f : num / den;
-  alpha = empty ? 0.f : 2.f / den;
-  beta = empty ? 0.f : D / den;
-}
-// q_c = qb[c] - [t == c] qa[c] with qa = m_c alpha_c / (G K), qb = m_c beta_c / (G K), from a group's folded sums d = {I, S, Y} per class
-template <int C> __device__ __forceinline__ void dice_coeffs(const float* d, DiceRule r, float qa[C], float qb[C]) {
+// A rule's terms(I, S, Y, smooth, m, index, term, a, b): the index reported per group and class, the term whose masked sum makes the value,
+// and the gradient's coefficients a, b with the weight m = m_c / (G K) folded in (q_c = b_c - [t == c] a_c); value(): the reported value
+// from the masked sum of terms.  One rounding per operation wherever they are inlined: _step's numbers are _fwd's and _bwd's.
+// Dice: D = (2 I + smooth) / (S + Y + smooth) is index and term, a = m 2 / den, b = m D / den; an empty denominator: D = 1, no gradient.
+struct DiceTerms {
+  __device__ __forceinline__ void terms(float I, float S, float Y, float smooth, float m, float& D, float& term, float& a, float& b) const {
+#pragma clang fp contract(off)
+    const float den = (S + Y) + smooth;
+    const float num = 2.f * I + smooth;
+    const bool empty = den == 0.f;
+    D = term = empty ? 1.f : num / den;
+    a = m * (empty ? 0.f : 2.f / den);
+    b = m * (empty ? 0.f : D / den);
+  }
+  static __device__ __forceinline__ float value(float sum, float inv_gk) {
+#pragma clang fp contract(off)
+    return 1.f - sum * inv_gk;
+  }
+};
+// Tversky: T = (I + smooth) / Den, Den = c0 I + alpha S + beta Y + smooth in the order written; term = u^e with u = max(1 - T, 0) (u when
+// !focal); with f = m e u^(e - 1) (m when !focal): a = f (1 - c0 T) / Den, b = f alpha T / Den.  Den == 0: T = 1; Den == 0 or u == 0:
+// term = a = b = 0.  c0 = fl(1 - alpha - beta) and e = fl(1 / gamma), formed on the host in double; focal = gamma != 1 (gamma == 1
+// evaluates no power function).
+struct TverskyTerms {
+  float alpha, beta, c0, e;
+  int focal;
+  __device__ __forceinline__ void terms(float I, float S, float Y, float smooth, float m, float& T, float& term, float& a, float& b) const {
+#pragma clang fp contract(off)
+    const float den = ((c0 * I + alpha * S) + beta * Y) + smooth;
+    const float num = I + smooth;
+    const bool empty = den == 0.f;
+    const float ds = empty ? 1.f : den;
+    T = empty ? 1.f : num / ds;
+    const float u = fmaxf(1.f - T, 0.f);
+    const bool some = u > 0.f;                                             // (false under an empty denominator: T = 1)
+    const float us = some ? u : 1.f;
+    float pw = us, f = m;
+    if (focal) {                                                           // (the same in every lane)
+      const float lg = log2f(us);
+      pw = exp2f(e * lg);
+      f = (m * e) * exp2f((e - 1.f) * lg);
+    }
+    term = some ? pw : 0.f;
+    a = some ? (f * (1.f - c0 * T)) / ds : 0.f;
+    b = some ? ((f * alpha) * T) / ds : 0.f;
+  }
+  static __device__ __forceinline__ float value(float sum, float inv_gk) {
+#pragma clang fp contract(off)
+    return sum * inv_gk;
+  }
+};
+// q_c = qb[c] - [t == c] qa[c] from a group's folded sums d = {I, S, Y} per class
+template <int C, class Rule> __device__ __forceinline__ void overlap_coeffs(const float* d, OverlapArgs r, Rule rule, float qa[C], float qb[C]) {
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    float D, alpha, beta;
-    dice_terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r.smooth, D, alpha, beta);
-    const float m = ((r.mask >> c) & 1) ? r.inv_gk : 0.f;
-    qa[c] = m * alpha; qb[c] = m * beta;
+    float index, term;
+    rule.terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r.smooth, ((r.mask >> c) & 1) ? r.inv_gk : 0.f, index, term, qa[c], qb[c]);
   }
 }
-// group g's rows of dice_gc [G][C] and sums [G][C][3] from its folded sums (one thread); -> the sum of D over the classes of the mask
-template <int C> __device__ __forceinline__ float dice_group_out(const float d[3 * C], int g, DiceRule r, float* dice_gc, float* sums) {
-  float dsum = 0.f;
+// group g's rows of index_gc [G][C] and sums [G][C][3] from its folded sums (one thread); -> the sum of the terms over the classes of the mask
+template <int C, class Rule>
+__device__ __forceinline__ float overlap_group_out(const float d[3 * C], int g, OverlapArgs r, Rule rule, float* index_gc, float* sums) {
+  float tsum = 0.f;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    float D, alpha, beta;
-    dice_terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r.smooth, D, alpha, beta);
-    dice_gc[g * C + c] = D;
+    float index, term, a, b;
+    rule.terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r.smooth, 0.f, index, term, a, b);
+    index_gc[g * C + c] = index;
     sums[(g * C + c) * 3 + 0] = d[3 * c]; sums[(g * C + c) * 3 + 1] = d[3 * c + 1]; sums[(g * C + c) * 3 + 2] = d[3 * c + 2];
-    if ((r.mask >> c) & 1) dsum += D;
+    if ((r.mask >> c) & 1) tsum += term;
   }
-  return dsum;
+  return tsum;
 }
-// out4, dice_gc and sums from the partial rows; the whole block calls it.  Under per_image wave w takes groups w, w + 4, ... and the four
-// waves' sums of D are added in order.
-template <int C>
-__device__ __forceinline__ void ce_dice_finish(const float* partial, int B, int fbx, DiceRule r, float* out4, float* dice_gc, float* sums, float* sm) {
+// out4 = {total, ce, sum w, value}, index_gc and sums from the partial rows; the whole block calls it.  Under per_image wave w takes groups
+// w, w + 4, ... and the four waves' sums of terms are added in order.
+template <int C, class Rule>
+__device__ __forceinline__ void overlap_finish(const float* partial, int B, int fbx, OverlapArgs r, Rule rule, float* out4, float* index_gc,
+                                               float* sums, float* sm) {
   constexpr int NS = 3 * C + 2;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float ce2[2], d[3 * C], dsum = 0.f;
+  float ce2[2], d[3 * C], tsum = 0.f;
   if (!r.per_image) {
-    ce_dice_fold<C>(partial, B, fbx, 0, 0, sm, ce2, d);
-    if (threadIdx.x == 0) dsum = dice_group_out<C>(d, 0, r, dice_gc, sums);
+    overlap_fold<C>(partial, B, fbx, 0, 0, sm, ce2, d);
+    if (threadIdx.x == 0) tsum = overlap_group_out<C>(d, 0, r, rule, index_gc, sums);
   } else {
     fold_rows<NS, 0, 2>(partial, 0, B * fbx, sm, ce2);
     for (int g = w; g < B; g += 4) {
       wave_fold_rows<NS, 2, 3 * C>(partial, g * fbx, fbx, d);
-      if (lane == 0) dsum += dice_group_out<C>(d, g, r, dice_gc, sums);
+      if (lane == 0) tsum += overlap_group_out<C>(d, g, r, rule, index_gc, sums);
     }
     __syncthreads();                     // (fold_rows' readers are done with sm)
-    if (lane == 0) sm[w] = dsum;
+    if (lane == 0) sm[w] = tsum;
     __syncthreads();
-    dsum = sm[0] + sm[1] + sm[2] + sm[3];
+    tsum = sm[0] + sm[1] + sm[2] + sm[3];
   }
   if (threadIdx.x == 0) {
 #pragma clang fp contract(off)
     const float ce = ce2[0] / ce2[1];
-    const float dice = 1.f - dsum * r.inv_gk;
+    const float value = Rule::value(tsum, r.inv_gk);
     float total = 0.f;
     if (r.ce_coef != 0.f) total = r.ce_coef * ce;            // a coefficient of exactly 0 removes its term (a NaN ce with it)
-    if (r.dice_coef != 0.f) total = total + r.dice_coef * dice;
-    out4[0] = total; out4[1] = ce; out4[2] = ce2[1]; out4[3] = dice;
+    if (r.coef != 0.f) total = total + r.coef * value;
+    out4[0] = total; out4[1] = ce; out4[2] = ce2[1]; out4[3] = value;
   }
 }
-// dl (=|+=) g (ce_coef (w_t / den)(p - y) + dice_coef p (q - sum_k p_k q_k)) over the block's pixels of image blockIdx.y
+// dl (=|+=) g (ce_coef (w_t / den)(p - y) + coef p (q - sum_k p_k q_k)) over the block's pixels of image blockIdx.y
 template <int C>
-__device__ __forceinline__ void ce_dice_grad_pixels(const float* logits, const long long* tgt, long long PPI, int ignore, const float wr[C],
-                                                    float g, float den, DiceRule r, const float qa[C], const float qb[C], float* dl, int acc) {
-  const bool ce_on = r.ce_coef != 0.f, dice_on = r.dice_coef != 0.f;
+__device__ __forceinline__ void overlap_grad_pixels(const float* logits, const long long* tgt, long long PPI, int ignore, const float wr[C],
+                                                    float g, float den, OverlapArgs r, const float qa[C], const float qb[C], float* dl, int acc) {
+  const bool ce_on = r.ce_coef != 0.f, dice_on = r.coef != 0.f;
   const float gce = ce_on ? g * r.ce_coef / den : 0.f;
-  const float gd = g * r.dice_coef;
+  const float gd = g * r.coef;
   const long long base = (long long)blockIdx.y * PPI;
   for (long long pix = (long long)blockIdx.x * 256 + threadIdx.x; pix < PPI; pix += (long long)gridDim.x * 256) {
     const long long t = tgt[base + pix];
@@ -715,7 +760,7 @@ __device__ __forceinline__ void ce_dice_grad_pixels(const float* logits, const l
 }
 // one softmax per counted pixel feeds both terms: WeightedRule's {w l, w} and {p_t, p_c, [t == c]} per class
 template <int C>
-__global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
+__global__ __launch_bounds__(256) void overlap_fwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
                                                            const float* weight, float* partial) {
   constexpr int NS = 3 * C + 2;
   float wr[C];
@@ -744,148 +789,37 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* logits, c
   }
   block_partial_n<NS>(a, partial + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * NS);
 }
-template <int C>
-__global__ __launch_bounds__(256) void ce_dice_fin_kernel(const float* partial, int B, int fbx, DiceRule r, float* out4, float* dice_gc, float* sums) {
+template <int C, class Rule>
+__global__ __launch_bounds__(256) void overlap_fin_kernel(const float* partial, int B, int fbx, OverlapArgs r, Rule rule, float* out4, float* index_gc,
+                                                           float* sums) {
   __shared__ float sm[4 * (3 * C + 2)];
-  ce_dice_finish<C>(partial, B, fbx, r, out4, dice_gc, sums, sm);
+  overlap_finish<C>(partial, B, fbx, r, rule, out4, index_gc, sums, sm);
 }
-template <int C>
-__global__ __launch_bounds__(256) void ce_dice_bwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore, const float* weight,
-                                                           DiceRule r, const float* out4, const float* sums, const float* gscale, float gmul,
-                                                           float* dl, int acc) {
+template <int C, class Rule>
+__global__ __launch_bounds__(256) void overlap_bwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore, const float* weight,
+                                                           OverlapArgs r, Rule rule, const float* out4, const float* sums, const float* gscale,
+                                                           float gmul, float* dl, int acc) {
   float wr[C], qa[C], qb[C];
   load_weights<C>(weight, wr);
-  dice_coeffs<C>(sums + (r.per_image ? (long long)blockIdx.y * C * 3 : 0), r, qa, qb);
-  ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, out4[2], r, qa, qb, dl, acc);
+  overlap_coeffs<C>(sums + (r.per_image ? (long long)blockIdx.y * C * 3 : 0), r, rule, qa, qb);
+  overlap_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, out4[2], r, qa, qb, dl, acc);
 }
-// loss_bwd_fin_kernel's pattern: every block folds the forward rows it needs (all of them for sum w; its own group's for the Dice sums)
-// in ce_dice_fin_kernel's order, block (0, 0) also writes what that kernel writes, then the gradient
-template <int C>
-__global__ __launch_bounds__(256) void ce_dice_bwd_fin_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
-                                                               const float* weight, DiceRule r, const float* partial, int fbx, float* out4,
-                                                               float* dice_gc, float* sums, const float* gscale, float gmul, float* dl, int acc) {
-  __shared__ float sm[4 * (3 * C + 2)];
-  const int B = gridDim.y;
-  float ce2[2], d[3 * C];
-  ce_dice_fold<C>(partial, B, fbx, r.per_image, blockIdx.y, sm, ce2, d);
-  if (blockIdx.x == 0 && blockIdx.y == 0) ce_dice_finish<C>(partial, B, fbx, r, out4, dice_gc, sums, sm);
-  float wr[C], qa[C], qb[C];
-  load_weights<C>(weight, wr);
-  dice_coeffs<C>(d, r, qa, qb);
-  ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, ce2[1], r, qa, qb, dl, acc);
-}
-
-// ---- Tversky and focal Tversky, alone or beside CE (the rule: include/dct.h) -----------------------------------------------------------------
-// The sums are Dice's: ce_dice_fwd_kernel writes the partial rows, fold_rows / wave_fold_rows / ce_dice_fold fold them in Dice's order and
-// ce_dice_grad_pixels writes the gradient from qa, qb.  What differs is the rule from {I, S, Y} to the value and to qa, qb (tversky_terms),
-// evaluated per block (and by one thread per group for the outputs), never per pixel.
-// c0 = fl(1 - alpha - beta) and e = fl(1 / gamma), formed on the host in double; focal = gamma != 1 (gamma == 1 evaluates no power function)
-struct TverskyRule { int mask, per_image, focal; float smooth, ce_coef, tv_coef, inv_gk, alpha, beta, c0, e; };
-
-__device__ __forceinline__ DiceRule as_dice(TverskyRule r) { return DiceRule{r.mask, r.per_image, r.smooth, r.ce_coef, r.tv_coef, r.inv_gk}; }
-// T = (I + smooth) / Den, Den = c0 I + alpha S + beta Y + smooth in the order written; term = u^e with u = max(1 - T, 0) (u when !focal);
-// with f = m e u^(e - 1) (m when !focal): a = f (1 - c0 T) / Den, b = f alpha T / Den.  Den == 0: T = 1; Den == 0 or u == 0: term = a = b = 0.
-__device__ __forceinline__ void tversky_terms(float I, float S, float Y, TverskyRule r, float m, float& T, float& term, float& a, float& b) {
-#pragma clang fp contract(off)    // one rounding per operation wherever this is inlined: _step's numbers are _fwd's and _bwd's
-  const float den = ((r.c0 * I + r.alpha * S) + r.beta * Y) + r.smooth;
-  const float num = I + r.smooth;
-  const bool empty = den == 0.f;
-  const float ds = empty ? 1.f : den;
-  T = empty ? 1.f : num / ds;
-  const float u = fmaxf(1.f - T, 0.f);
-  const bool some = u > 0.f;                                               // (false under an empty denominator: T = 1)
-  const float us = some ? u : 1.f;
-  float pw = us, f = m;
-  if (r.focal) {                                                           // (the same in every lane)
-    const float lg = log2f(us);
-    pw = exp2f(r.e * lg);
-    f = (m * r.e) * exp2f((r.e - 1.f) * lg);
-  }
-  term = some ? pw : 0.f;
-  a = some ? (f * (1.f - r.c0 * T)) / ds : 0.f;
-  b = some ? ((f * r.alpha) * T) / ds : 0.f;
-}
-// q_c = qb[c] - [t == c] qa[c] from a group's folded sums d = {I, S, Y} per class
-template <int C> __device__ __forceinline__ void tversky_coeffs(const float* d, TverskyRule r, float qa[C], float qb[C]) {
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    float T, term;
-    tversky_terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r, ((r.mask >> c) & 1) ? r.inv_gk : 0.f, T, term, qa[c], qb[c]);
-  }
-}
-// group g's rows of tversky_gc [G][C] and sums [G][C][3] from its folded sums (one thread); -> the sum of the terms over the classes of the mask
-template <int C> __device__ __forceinline__ float tversky_group_out(const float d[3 * C], int g, TverskyRule r, float* tversky_gc, float* sums) {
-  float tsum = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    float T, term, a, b;
-    tversky_terms(d[3 * c], d[3 * c + 1], d[3 * c + 2], r, 0.f, T, term, a, b);
-    tversky_gc[g * C + c] = T;
-    sums[(g * C + c) * 3 + 0] = d[3 * c]; sums[(g * C + c) * 3 + 1] = d[3 * c + 1]; sums[(g * C + c) * 3 + 2] = d[3 * c + 2];
-    if ((r.mask >> c) & 1) tsum += term;
-  }
-  return tsum;
-}
-// ce_dice_finish's walk (the whole block calls it; under per_image wave w takes groups w, w + 4, ... and the four waves' sums are added
-// in order) with the Tversky terms: out4 = {total, ce, sum w, tversky}
-template <int C>
-__device__ __forceinline__ void ce_tversky_finish(const float* partial, int B, int fbx, TverskyRule r, float* out4, float* tversky_gc, float* sums, float* sm) {
-  constexpr int NS = 3 * C + 2;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float ce2[2], d[3 * C], tsum = 0.f;
-  if (!r.per_image) {
-    ce_dice_fold<C>(partial, B, fbx, 0, 0, sm, ce2, d);
-    if (threadIdx.x == 0) tsum = tversky_group_out<C>(d, 0, r, tversky_gc, sums);
-  } else {
-    fold_rows<NS, 0, 2>(partial, 0, B * fbx, sm, ce2);
-    for (int g = w; g < B; g += 4) {
-      wave_fold_rows<NS, 2, 3 * C>(partial, g * fbx, fbx, d);
-      if (lane == 0) tsum += tversky_group_out<C>(d, g, r, tversky_gc, sums);
-    }
-    __syncthreads();                     // (fold_rows' readers are done with sm)
-    if (lane == 0) sm[w] = tsum;
-    __syncthreads();
-    tsum = sm[0] + sm[1] + sm[2] + sm[3];
-  }
-  if (threadIdx.x == 0) {
-#pragma clang fp contract(off)
-    const float ce = ce2[0] / ce2[1];
-    const float tv = tsum * r.inv_gk;
-    float total = 0.f;
-    if (r.ce_coef != 0.f) total = r.ce_coef * ce;            // a coefficient of exactly 0 removes its term (a NaN ce with it)
-    if (r.tv_coef != 0.f) total = total + r.tv_coef * tv;
-    out4[0] = total; out4[1] = ce; out4[2] = ce2[1]; out4[3] = tv;
-  }
-}
-template <int C>
-__global__ __launch_bounds__(256) void ce_tversky_fin_kernel(const float* partial, int B, int fbx, TverskyRule r, float* out4, float* tversky_gc, float* sums) {
-  __shared__ float sm[4 * (3 * C + 2)];
-  ce_tversky_finish<C>(partial, B, fbx, r, out4, tversky_gc, sums, sm);
-}
-template <int C>
-__global__ __launch_bounds__(256) void ce_tversky_bwd_kernel(const float* logits, const long long* tgt, long long PPI, int ignore, const float* weight,
-                                                              TverskyRule r, const float* out4, const float* sums, const float* gscale, float gmul,
-                                                              float* dl, int acc) {
-  float wr[C], qa[C], qb[C];
-  load_weights<C>(weight, wr);
-  tversky_coeffs<C>(sums + (r.per_image ? (long long)blockIdx.y * C * 3 : 0), r, qa, qb);
-  ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, out4[2], as_dice(r), qa, qb, dl, acc);
-}
-// ce_dice_bwd_fin_kernel's pattern: every block folds the forward rows it needs in ce_tversky_fin_kernel's order, block (0, 0) also writes
-// what that kernel writes, then the gradient
-template <int C>
-__global__ __launch_bounds__(256) void ce_tversky_bwd_fin_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
-                                                                  const float* weight, TverskyRule r, const float* partial, int fbx, float* out4,
-                                                                  float* tversky_gc, float* sums, const float* gscale, float gmul, float* dl, int acc) {
+// loss_bwd_fin_kernel's pattern: every block folds the forward rows it needs (all of them for sum w; its own group's for the overlap sums)
+// in overlap_fin_kernel's order, block (0, 0) also writes what that kernel writes, then the gradient
+template <int C, class Rule>
+__global__ __launch_bounds__(256) void overlap_bwd_fin_kernel(const float* logits, const long long* tgt, long long PPI, int ignore,
+                                                               const float* weight, OverlapArgs r, Rule rule, const float* partial, int fbx,
+                                                               float* out4, float* index_gc, float* sums, const float* gscale, float gmul,
+                                                               float* dl, int acc) {
   __shared__ float sm[4 * (3 * C + 2)];
   const int B = gridDim.y;
   float ce2[2], d[3 * C];
-  ce_dice_fold<C>(partial, B, fbx, r.per_image, blockIdx.y, sm, ce2, d);
-  if (blockIdx.x == 0 && blockIdx.y == 0) ce_tversky_finish<C>(partial, B, fbx, r, out4, tversky_gc, sums, sm);
+  overlap_fold<C>(partial, B, fbx, r.per_image, blockIdx.y, sm, ce2, d);
+  if (blockIdx.x == 0 && blockIdx.y == 0) overlap_finish<C>(partial, B, fbx, r, rule, out4, index_gc, sums, sm);
   float wr[C], qa[C], qb[C];
   load_weights<C>(weight, wr);
-  tversky_coeffs<C>(d, r, qa, qb);
-  ce_dice_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, ce2[1], as_dice(r), qa, qb, dl, acc);
+  overlap_coeffs<C>(d, r, rule, qa, qb);
+  overlap_grad_pixels<C>(logits, tgt, PPI, ignore, wr, (gscale ? gscale[0] : 1.f) * gmul, ce2[1], r, qa, qb, dl, acc);
 }
 
 // ---- softmax / entropy (module API) -------------------------------------------------------------
@@ -1996,119 +1930,115 @@ static inline unsigned dice_grid_x(long long ppi, int B, int cap) {
 static inline size_t dice_ws_bytes(int B, int C_) {
   return (size_t)(B > kDiceFwdBlocks ? B : kDiceFwdBlocks) * (size_t)(3 * C_ + 2) * sizeof(float);
 }
-// the checks the three calls share (pointers apart) and the rule as the kernels take it
-static int dice_rule(int B, int64_t ppi, int C_, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, DiceRule& r) {
-  if (B < 1 || ppi < 1 || !(smooth >= 0.f) || __builtin_isinf(smooth) || (per_image != 0 && per_image != 1)) return DCT_ERR_BAD_ARG;
-  if (C_ < 2 || C_ > 8 || B > 65535) return DCT_ERR_UNSUPPORTED;
+// what the three calls of both families take beside their outputs: the tensors and sizes, the common block as the kernels take it and the
+// status of the rule's check
+struct OverlapCall { const float* logits; const long long* targets; int B; long long ppi; int C_, ignore; const float* weight; hipStream_t st; OverlapArgs r; int status; };
+// The rule check, from an entry point's arguments: the checks the three calls share (pointers apart) and, with tv, the Tversky parameters'
+// own and their rule (Dice has none): 1 - alpha - beta and 1 / gamma are formed in double and rounded once each.
+static OverlapCall overlap_call(const float* logits, const int64_t* targets, int B, int64_t ppi, int C_, int ignore_index, const float* weight,
+                                int class_mask, float smooth, int per_image, float ce_coef, float coef, dct_stream stream, float alpha = .5f,
+                                float beta = .5f, float gamma = 1.f, TverskyTerms* tv = nullptr) {
+  OverlapCall c{logits, (const long long*)targets, B, (long long)ppi, C_, ignore_index, weight, (hipStream_t)stream, OverlapArgs{}, DCT_ERR_BAD_ARG};
+  if (B < 1 || ppi < 1 || !(smooth >= 0.f) || __builtin_isinf(smooth) || (per_image != 0 && per_image != 1)) return c;
+  if (C_ < 2 || C_ > 8 || B > 65535) { c.status = DCT_ERR_UNSUPPORTED; return c; }
   const int mask = class_mask & ((1 << C_) - 1);
-  if (!mask) return DCT_ERR_BAD_ARG;
+  if (!mask) return c;
+  if (!(alpha >= 0.f) || !(beta >= 0.f) || __builtin_isinf(alpha) || __builtin_isinf(beta) || alpha + beta == 0.f) return c;
+  if (!(gamma > 0.f) || __builtin_isinf(gamma)) return c;
   const int G = per_image ? B : 1, K = __builtin_popcount((unsigned)mask);
-  r = DiceRule{mask, per_image, smooth, ce_coef, dice_coef, 1.f / (float)((long long)G * K)};
-  return DCT_OK;
+  c.r = OverlapArgs{mask, per_image, smooth, ce_coef, coef, 1.f / (float)((long long)G * K)};
+  if (tv) *tv = TverskyTerms{alpha, beta, (float)(1.0 - (double)alpha - (double)beta), (float)(1.0 / (double)gamma), gamma != 1.f};
+  c.status = DCT_OK;
+  return c;
 }
+// The status of a bad call: BAD_ARG (the pointers, then the rule's check), UNSUPPORTED (C, B), then WORKSPACE
+#define OVERLAP_LAUNCH(kernel, blocks, ...)                                                                                                 \
+  DISPATCH_C(c.C_, DCT_LAUNCH(DCT_PROF_LOSS, kernel, dim3(dice_grid_x(c.ppi, c.B, blocks), (unsigned)c.B), dim3(256), 0, c.st, c.logits, c.targets, \
+                              c.ppi, c.ignore, c.weight, __VA_ARGS__))
+template <class Rule>
+static int overlap_fwd(const Rule& rule, const OverlapCall& c, float* out4, float* index_gc, float* sums, void* workspace, size_t workspace_bytes) {
+  if (!c.logits || !c.targets || !out4 || !index_gc || !sums) return DCT_ERR_BAD_ARG;
+  if (c.status != DCT_OK) return c.status;
+  if (!workspace || workspace_bytes < dice_ws_bytes(c.B, c.C_)) return DCT_ERR_WORKSPACE;
+  const int fbx = (int)dice_grid_x(c.ppi, c.B, kDiceFwdBlocks);
+  OVERLAP_LAUNCH(overlap_fwd_kernel<C>, kDiceFwdBlocks, (float*)workspace);
+  DISPATCH_C(c.C_, DCT_LAUNCH(DCT_PROF_LOSS, (overlap_fin_kernel<C, Rule>), dim3(1), dim3(256), 0, c.st, (const float*)workspace, c.B, fbx, c.r, rule,
+                              out4, index_gc, sums));
+  return dct_check_launch();
+}
+template <class Rule>
+static int overlap_bwd(const Rule& rule, const OverlapCall& c, const float* out4, const float* sums, const float* gscale, float gmul, float* dlogits,
+                       int accumulate) {
+  if (!c.logits || !c.targets || !out4 || !sums || !dlogits) return DCT_ERR_BAD_ARG;
+  if (c.status != DCT_OK) return c.status;
+  OVERLAP_LAUNCH((overlap_bwd_kernel<C, Rule>), kDiceBwdBlocks, c.r, rule, out4, sums, gscale, gmul, dlogits, accumulate);
+  return dct_check_launch();
+}
+// overlap_fwd's forward launch (the same partial rows) and overlap_bwd's grid
+template <class Rule>
+static int overlap_step(const Rule& rule, const OverlapCall& c, float* out4, float* index_gc, float* sums, const float* gscale, float gmul,
+                        float* dlogits, int accumulate, void* workspace, size_t workspace_bytes) {
+  if (!c.logits || !c.targets || !out4 || !index_gc || !sums || !dlogits) return DCT_ERR_BAD_ARG;
+  if (c.status != DCT_OK) return c.status;
+  if (!workspace || workspace_bytes < dice_ws_bytes(c.B, c.C_)) return DCT_ERR_WORKSPACE;
+  const int fbx = (int)dice_grid_x(c.ppi, c.B, kDiceFwdBlocks);
+  OVERLAP_LAUNCH(overlap_fwd_kernel<C>, kDiceFwdBlocks, (float*)workspace);
+  OVERLAP_LAUNCH((overlap_bwd_fin_kernel<C, Rule>), kDiceBwdBlocks, c.r, rule, (const float*)workspace, fbx, out4, index_gc, sums, gscale, gmul,
+                 dlogits, accumulate);
+  return dct_check_launch();
+}
+#undef OVERLAP_LAUNCH
+
 extern "C" size_t dct_ce_dice_workspace_bytes(int B, int C_, int /*per_image*/) {
   return dice_ws_bytes(B < 1 ? 1 : B, C_ < 2 ? 2 : (C_ > 8 ? 8 : C_));
 }
 extern "C" int dct_ce_dice_fwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
                                const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, float* out4,
                                float* dice_gc, float* sums, void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out4 || !dice_gc || !sums) return DCT_ERR_BAD_ARG;
-  DiceRule r;
-  if (const int e = dice_rule(B, pixels_per_image, C_, class_mask, smooth, per_image, ce_coef, dice_coef, r)) return e;
-  if (!workspace || workspace_bytes < dice_ws_bytes(B, C_)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned fbx = dice_grid_x(pixels_per_image, B, kDiceFwdBlocks);
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fwd_kernel<C>, dim3(fbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
-                            ignore_index, weight, (float*)workspace));
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fin_kernel<C>, dim3(1), dim3(256), 0, st, (const float*)workspace, B, (int)fbx, r, out4, dice_gc, sums));
-  return dct_check_launch();
+  const OverlapCall c = overlap_call(logits, targets, B, pixels_per_image, C_, ignore_index, weight, class_mask, smooth, per_image, ce_coef, dice_coef, stream);
+  return overlap_fwd(DiceTerms{}, c, out4, dice_gc, sums, workspace, workspace_bytes);
 }
 extern "C" int dct_ce_dice_bwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
                                const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef,
                                const float* out4, const float* sums, const float* gscale, float gmul, float* dlogits, int accumulate,
                                dct_stream stream) {
-  if (!logits || !targets || !out4 || !sums || !dlogits) return DCT_ERR_BAD_ARG;
-  DiceRule r;
-  if (const int e = dice_rule(B, pixels_per_image, C_, class_mask, smooth, per_image, ce_coef, dice_coef, r)) return e;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned bbx = dice_grid_x(pixels_per_image, B, kDiceBwdBlocks);
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_bwd_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
-                            ignore_index, weight, r, out4, sums, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  const OverlapCall c = overlap_call(logits, targets, B, pixels_per_image, C_, ignore_index, weight, class_mask, smooth, per_image, ce_coef, dice_coef, stream);
+  return overlap_bwd(DiceTerms{}, c, out4, sums, gscale, gmul, dlogits, accumulate);
 }
 extern "C" int dct_ce_dice_step(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
                                 const float* weight, int class_mask, float smooth, int per_image, float ce_coef, float dice_coef, float* out4,
                                 float* dice_gc, float* sums, const float* gscale, float gmul, float* dlogits, int accumulate,
                                 void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out4 || !dice_gc || !sums || !dlogits) return DCT_ERR_BAD_ARG;
-  DiceRule r;
-  if (const int e = dice_rule(B, pixels_per_image, C_, class_mask, smooth, per_image, ce_coef, dice_coef, r)) return e;
-  if (!workspace || workspace_bytes < dice_ws_bytes(B, C_)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned fbx = dice_grid_x(pixels_per_image, B, kDiceFwdBlocks);       // dct_ce_dice_fwd's grid: the same partial rows
-  const unsigned bbx = dice_grid_x(pixels_per_image, B, kDiceBwdBlocks);       // dct_ce_dice_bwd's grid
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fwd_kernel<C>, dim3(fbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
-                            ignore_index, weight, (float*)workspace));
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_bwd_fin_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
-                            ignore_index, weight, r, (const float*)workspace, (int)fbx, out4, dice_gc, sums, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
-}
-// dice_rule's checks and the Tversky parameters' own; 1 - alpha - beta and 1 / gamma are formed in double and rounded once each
-static int tversky_rule(int B, int64_t ppi, int C_, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
-                        float ce_coef, float tv_coef, TverskyRule& r) {
-  DiceRule d;
-  if (const int e = dice_rule(B, ppi, C_, class_mask, smooth, per_image, ce_coef, tv_coef, d)) return e;
-  if (!(alpha >= 0.f) || !(beta >= 0.f) || __builtin_isinf(alpha) || __builtin_isinf(beta) || alpha + beta == 0.f) return DCT_ERR_BAD_ARG;
-  if (!(gamma > 0.f) || __builtin_isinf(gamma)) return DCT_ERR_BAD_ARG;
-  r = TverskyRule{d.mask, per_image, gamma != 1.f, smooth, ce_coef, tv_coef, d.inv_gk, alpha, beta,
-                  (float)(1.0 - (double)alpha - (double)beta), (float)(1.0 / (double)gamma)};
-  return DCT_OK;
+  const OverlapCall c = overlap_call(logits, targets, B, pixels_per_image, C_, ignore_index, weight, class_mask, smooth, per_image, ce_coef, dice_coef, stream);
+  return overlap_step(DiceTerms{}, c, out4, dice_gc, sums, gscale, gmul, dlogits, accumulate, workspace, workspace_bytes);
 }
 extern "C" size_t dct_ce_tversky_workspace_bytes(int B, int C_, int per_image) { return dct_ce_dice_workspace_bytes(B, C_, per_image); }
 extern "C" int dct_ce_tversky_fwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
                                   const float* weight, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
                                   float ce_coef, float tversky_coef, float* out4, float* tversky_gc, float* sums, void* workspace,
                                   size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out4 || !tversky_gc || !sums) return DCT_ERR_BAD_ARG;
-  TverskyRule r;
-  if (const int e = tversky_rule(B, pixels_per_image, C_, class_mask, smooth, alpha, beta, gamma, per_image, ce_coef, tversky_coef, r)) return e;
-  if (!workspace || workspace_bytes < dice_ws_bytes(B, C_)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned fbx = dice_grid_x(pixels_per_image, B, kDiceFwdBlocks);
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fwd_kernel<C>, dim3(fbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
-                            ignore_index, weight, (float*)workspace));
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_tversky_fin_kernel<C>, dim3(1), dim3(256), 0, st, (const float*)workspace, B, (int)fbx, r, out4, tversky_gc, sums));
-  return dct_check_launch();
+  TverskyTerms tv;
+  const OverlapCall c = overlap_call(logits, targets, B, pixels_per_image, C_, ignore_index, weight, class_mask, smooth, per_image, ce_coef, tversky_coef,
+                                     stream, alpha, beta, gamma, &tv);
+  return overlap_fwd(tv, c, out4, tversky_gc, sums, workspace, workspace_bytes);
 }
 extern "C" int dct_ce_tversky_bwd(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
                                   const float* weight, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
                                   float ce_coef, float tversky_coef, const float* out4, const float* sums, const float* gscale, float gmul,
                                   float* dlogits, int accumulate, dct_stream stream) {
-  if (!logits || !targets || !out4 || !sums || !dlogits) return DCT_ERR_BAD_ARG;
-  TverskyRule r;
-  if (const int e = tversky_rule(B, pixels_per_image, C_, class_mask, smooth, alpha, beta, gamma, per_image, ce_coef, tversky_coef, r)) return e;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned bbx = dice_grid_x(pixels_per_image, B, kDiceBwdBlocks);
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_tversky_bwd_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
-                            ignore_index, weight, r, out4, sums, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  TverskyTerms tv;
+  const OverlapCall c = overlap_call(logits, targets, B, pixels_per_image, C_, ignore_index, weight, class_mask, smooth, per_image, ce_coef, tversky_coef,
+                                     stream, alpha, beta, gamma, &tv);
+  return overlap_bwd(tv, c, out4, sums, gscale, gmul, dlogits, accumulate);
 }
 extern "C" int dct_ce_tversky_step(const float* logits, const int64_t* targets, int B, int64_t pixels_per_image, int C_, int ignore_index,
                                    const float* weight, int class_mask, float smooth, float alpha, float beta, float gamma, int per_image,
                                    float ce_coef, float tversky_coef, float* out4, float* tversky_gc, float* sums, const float* gscale,
                                    float gmul, float* dlogits, int accumulate, void* workspace, size_t workspace_bytes, dct_stream stream) {
-  if (!logits || !targets || !out4 || !tversky_gc || !sums || !dlogits) return DCT_ERR_BAD_ARG;
-  TverskyRule r;
-  if (const int e = tversky_rule(B, pixels_per_image, C_, class_mask, smooth, alpha, beta, gamma, per_image, ce_coef, tversky_coef, r)) return e;
-  if (!workspace || workspace_bytes < dice_ws_bytes(B, C_)) return DCT_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned fbx = dice_grid_x(pixels_per_image, B, kDiceFwdBlocks);       // dct_ce_tversky_fwd's grid: the same partial rows
-  const unsigned bbx = dice_grid_x(pixels_per_image, B, kDiceBwdBlocks);       // dct_ce_tversky_bwd's grid
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_dice_fwd_kernel<C>, dim3(fbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
-                            ignore_index, weight, (float*)workspace));
-  DISPATCH_C(C_, DCT_LAUNCH(DCT_PROF_LOSS, ce_tversky_bwd_fin_kernel<C>, dim3(bbx, (unsigned)B), dim3(256), 0, st, logits, (const long long*)targets, (long long)pixels_per_image,
-                            ignore_index, weight, r, (const float*)workspace, (int)fbx, out4, tversky_gc, sums, gscale, gmul, dlogits, accumulate));
-  return dct_check_launch();
+  TverskyTerms tv;
+  const OverlapCall c = overlap_call(logits, targets, B, pixels_per_image, C_, ignore_index, weight, class_mask, smooth, per_image, ce_coef, tversky_coef,
+                                     stream, alpha, beta, gamma, &tv);
+  return overlap_step(tv, c, out4, tversky_gc, sums, gscale, gmul, dlogits, accumulate, workspace, workspace_bytes);
 }
 extern "C" int dct_softmax_fwd(const float* logits, float* probs, int64_t pixels, int C_, dct_stream stream) {
   if (!logits || !probs || pixels < 1) return DCT_ERR_BAD_ARG;

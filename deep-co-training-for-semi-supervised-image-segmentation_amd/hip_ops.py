@@ -644,14 +644,51 @@ def boundary_bwd(logits_pc, targets, phi, C_, count, dlogits, class_mask=None, g
     return dlogits
 
 
-def _ce_dice_args(logits_bpc, C_, class_mask, per_image):
+# The overlap criteria (dct_ce_dice_*, dct_ce_tversky_*): one argument list, in which a family's own parameters (``rule``: none for Dice;
+# alpha, beta, gamma for Tversky) stand between ``smooth`` and ``per_image``.
+def _overlap_args(logits_bpc, C_, class_mask, per_image):
     """(B, pixels per image, mask, G) of fp32 logits [B, ..., C] (dense; the first dimension counts the images)."""
     B = logits_bpc.shape[0]
     return B, logits_bpc.numel() // (B * C_), (1 << C_) - 1 if class_mask is None else int(class_mask), B if per_image else 1
 
 
-def _ce_dice_ws(B, C_, per_image, device):
+def _overlap_ws(B, C_, per_image, device):
     return torch.empty(_lib.load().dct_ce_dice_workspace_bytes(B, C_, int(per_image)), dtype=torch.uint8, device=device)
+
+
+def _overlap_outputs(G, C_, device):
+    """(out4, index_gc [G, C], sums [G, C, 3])"""
+    return (torch.empty(4, dtype=torch.float32, device=device), torch.empty(G, C_, dtype=torch.float32, device=device),
+            torch.empty(G, C_, 3, dtype=torch.float32, device=device))
+
+
+def _overlap_fwd(family, rule, logits_bpc, targets, C_, weight, class_mask, smooth, per_image, ce_coef, coef, ignore_index):
+    B, ppi, mask, G = _overlap_args(logits_bpc, C_, class_mask, per_image)
+    out4, index_gc, sums = _overlap_outputs(G, C_, logits_bpc.device)
+    ws = _overlap_ws(B, C_, per_image, logits_bpc.device)
+    call(f"dct_ce_{family}_fwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth),
+         *(float(v) for v in rule), int(per_image), float(ce_coef), float(coef), ptr(out4), ptr(index_gc), ptr(sums), ptr(ws), ws.numel(), stream())
+    return out4, index_gc, sums
+
+
+def _overlap_bwd(family, rule, logits_bpc, targets, C_, out4, sums, dlogits, weight, class_mask, smooth, per_image, ce_coef, coef, gscale, gmul,
+                 ignore_index, accumulate):
+    B, ppi, mask, _ = _overlap_args(logits_bpc, C_, class_mask, per_image)
+    call(f"dct_ce_{family}_bwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth),
+         *(float(v) for v in rule), int(per_image), float(ce_coef), float(coef), ptr(out4), ptr(sums), ptr(gscale), float(gmul), ptr(dlogits),
+         int(accumulate), stream())
+    return dlogits
+
+
+def _overlap_step(family, rule, logits_bpc, targets, C_, dlogits, weight, class_mask, smooth, per_image, ce_coef, coef, gscale, gmul,
+                  ignore_index, accumulate):
+    B, ppi, mask, G = _overlap_args(logits_bpc, C_, class_mask, per_image)
+    out4, index_gc, sums = _overlap_outputs(G, C_, logits_bpc.device)
+    ws = _overlap_ws(B, C_, per_image, logits_bpc.device)
+    call(f"dct_ce_{family}_step", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth),
+         *(float(v) for v in rule), int(per_image), float(ce_coef), float(coef), ptr(out4), ptr(index_gc), ptr(sums), ptr(gscale), float(gmul),
+         ptr(dlogits), int(accumulate), ptr(ws), ws.numel(), stream())
+    return out4, index_gc, sums
 
 
 def ce_dice_fwd(logits_bpc, targets, C_, weight=None, class_mask=None, smooth=1e-5, per_image=False, ce_coef=1.0, dice_coef=1.0,
@@ -659,44 +696,22 @@ def ce_dice_fwd(logits_bpc, targets, C_, weight=None, class_mask=None, smooth=1e
     """Soft Dice / CE + Dice (dct_ce_dice_fwd; the rule: include/dct.h).  ``logits_bpc``: fp32 [B, ..., C] dense; ``targets``: int64, one per
     pixel; ``class_mask``: bit c = class c is in the Dice mean (None: all).  Returns device tensors ``out4`` = (total, ce, sum w, dice),
     ``dice_gc`` [G, C] and ``sums`` [G, C, 3] (G = B under ``per_image``, else 1)."""
-    B, ppi, mask, G = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
-    dev = logits_bpc.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    dice_gc = torch.empty(G, C_, dtype=torch.float32, device=dev)
-    sums = torch.empty(G, C_, 3, dtype=torch.float32, device=dev)
-    ws = _ce_dice_ws(B, C_, per_image, dev)
-    call("dct_ce_dice_fwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), int(per_image),
-         float(ce_coef), float(dice_coef), ptr(out4), ptr(dice_gc), ptr(sums), ptr(ws), ws.numel(), stream())
-    return out4, dice_gc, sums
+    return _overlap_fwd("dice", (), logits_bpc, targets, C_, weight, class_mask, smooth, per_image, ce_coef, dice_coef, ignore_index)
 
 
 def ce_dice_bwd(logits_bpc, targets, C_, out4, sums, dlogits, weight=None, class_mask=None, smooth=1e-5, per_image=False, ce_coef=1.0,
                 dice_coef=1.0, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
     """``out4`` and ``sums``: those of ce_dice_fwd under the same arguments."""
-    B, ppi, mask, _ = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
-    call("dct_ce_dice_bwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), int(per_image),
-         float(ce_coef), float(dice_coef), ptr(out4), ptr(sums), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate), stream())
-    return dlogits
+    return _overlap_bwd("dice", (), logits_bpc, targets, C_, out4, sums, dlogits, weight, class_mask, smooth, per_image, ce_coef, dice_coef,
+                        gscale, gmul, ignore_index, accumulate)
 
 
 def ce_dice_step(logits_bpc, targets, C_, dlogits, weight=None, class_mask=None, smooth=1e-5, per_image=False, ce_coef=1.0, dice_coef=1.0,
                  gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
     """ce_dice_fwd + ce_dice_bwd of the same logits in two launches (dct_ce_dice_step; bit for bit the two calls).  Returns
     (out4, dice_gc, sums); ``dlogits`` is written (added to)."""
-    B, ppi, mask, G = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
-    dev = logits_bpc.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    dice_gc = torch.empty(G, C_, dtype=torch.float32, device=dev)
-    sums = torch.empty(G, C_, 3, dtype=torch.float32, device=dev)
-    ws = _ce_dice_ws(B, C_, per_image, dev)
-    call("dct_ce_dice_step", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), int(per_image),
-         float(ce_coef), float(dice_coef), ptr(out4), ptr(dice_gc), ptr(sums), ptr(gscale), float(gmul), ptr(dlogits), int(accumulate),
-         ptr(ws), ws.numel(), stream())
-    return out4, dice_gc, sums
-
-
-def _ce_tversky_ws(B, C_, per_image, device):
-    return torch.empty(_lib.load().dct_ce_tversky_workspace_bytes(B, C_, int(per_image)), dtype=torch.uint8, device=device)
+    return _overlap_step("dice", (), logits_bpc, targets, C_, dlogits, weight, class_mask, smooth, per_image, ce_coef, dice_coef, gscale, gmul,
+                         ignore_index, accumulate)
 
 
 def ce_tversky_fwd(logits_bpc, targets, C_, weight=None, class_mask=None, smooth=1e-5, alpha=0.3, beta=0.7, gamma=1.0, per_image=False,
@@ -704,42 +719,23 @@ def ce_tversky_fwd(logits_bpc, targets, C_, weight=None, class_mask=None, smooth
     """Tversky / focal Tversky / CE + Tversky (dct_ce_tversky_fwd; the rule: include/dct.h).  ``logits_bpc``: fp32 [B, ..., C] dense;
     ``targets``: int64, one per pixel; ``class_mask``: bit c = class c is in the mean (None: all).  Returns device tensors ``out4`` =
     (total, ce, sum w, tversky), ``tversky_gc`` [G, C] (the index T_gc) and ``sums`` [G, C, 3] (G = B under ``per_image``, else 1)."""
-    B, ppi, mask, G = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
-    dev = logits_bpc.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    tversky_gc = torch.empty(G, C_, dtype=torch.float32, device=dev)
-    sums = torch.empty(G, C_, 3, dtype=torch.float32, device=dev)
-    ws = _ce_tversky_ws(B, C_, per_image, dev)
-    call("dct_ce_tversky_fwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), float(alpha),
-         float(beta), float(gamma), int(per_image), float(ce_coef), float(tversky_coef), ptr(out4), ptr(tversky_gc), ptr(sums), ptr(ws),
-         ws.numel(), stream())
-    return out4, tversky_gc, sums
+    return _overlap_fwd("tversky", (alpha, beta, gamma), logits_bpc, targets, C_, weight, class_mask, smooth, per_image, ce_coef, tversky_coef,
+                        ignore_index)
 
 
 def ce_tversky_bwd(logits_bpc, targets, C_, out4, sums, dlogits, weight=None, class_mask=None, smooth=1e-5, alpha=0.3, beta=0.7, gamma=1.0,
                    per_image=False, ce_coef=1.0, tversky_coef=1.0, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
     """``out4`` and ``sums``: those of ce_tversky_fwd under the same arguments."""
-    B, ppi, mask, _ = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
-    call("dct_ce_tversky_bwd", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), float(alpha),
-         float(beta), float(gamma), int(per_image), float(ce_coef), float(tversky_coef), ptr(out4), ptr(sums), ptr(gscale), float(gmul),
-         ptr(dlogits), int(accumulate), stream())
-    return dlogits
+    return _overlap_bwd("tversky", (alpha, beta, gamma), logits_bpc, targets, C_, out4, sums, dlogits, weight, class_mask, smooth, per_image,
+                        ce_coef, tversky_coef, gscale, gmul, ignore_index, accumulate)
 
 
 def ce_tversky_step(logits_bpc, targets, C_, dlogits, weight=None, class_mask=None, smooth=1e-5, alpha=0.3, beta=0.7, gamma=1.0,
                     per_image=False, ce_coef=1.0, tversky_coef=1.0, gscale=None, gmul=1.0, ignore_index=255, accumulate=False):
     """ce_tversky_fwd + ce_tversky_bwd of the same logits in two launches (dct_ce_tversky_step; bit for bit the two calls).  Returns
     (out4, tversky_gc, sums); ``dlogits`` is written (added to)."""
-    B, ppi, mask, G = _ce_dice_args(logits_bpc, C_, class_mask, per_image)
-    dev = logits_bpc.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    tversky_gc = torch.empty(G, C_, dtype=torch.float32, device=dev)
-    sums = torch.empty(G, C_, 3, dtype=torch.float32, device=dev)
-    ws = _ce_tversky_ws(B, C_, per_image, dev)
-    call("dct_ce_tversky_step", ptr(logits_bpc), ptr(targets), B, ppi, C_, int(ignore_index), ptr(weight), mask, float(smooth), float(alpha),
-         float(beta), float(gamma), int(per_image), float(ce_coef), float(tversky_coef), ptr(out4), ptr(tversky_gc), ptr(sums), ptr(gscale),
-         float(gmul), ptr(dlogits), int(accumulate), ptr(ws), ws.numel(), stream())
-    return out4, tversky_gc, sums
+    return _overlap_step("tversky", (alpha, beta, gamma), logits_bpc, targets, C_, dlogits, weight, class_mask, smooth, per_image, ce_coef,
+                         tversky_coef, gscale, gmul, ignore_index, accumulate)
 
 
 def softmax_fwd(logits_pc, C_):

@@ -251,58 +251,57 @@ class TopKCrossEntropyLoss2d(_ClassWeighted):
         return value
 
 
-class _CEDiceFn(torch.autograd.Function):
-    """``ce_coef`` ce + ``dice_coef`` dice on dct_ce_dice_*; ``rule``: the launch arguments of ``CrossEntropyDiceLoss2d.launch_args``.
-    Returns the total and, without a gradient, the [G, C] table of D_gc."""
+class _OverlapFn(torch.autograd.Function):
+    """``ce_coef`` ce + coefficient * overlap term on one hip_ops family of the overlap kernels: ``family`` is 'ce_dice' or 'ce_tversky' (its
+    ``_fwd`` and ``_bwd`` wrappers are called), ``rule`` the criterion's ``launch_args``.  Returns the total and, without a gradient, the [G, C] table
+    of the index (D_gc, T_gc)."""
 
     @staticmethod
-    def forward(ctx, logits, targets, weight, rule, ignore_index):
+    def forward(ctx, logits, targets, weight, family, rule, ignore_index):
         lp = _pc(logits)
         t = _targets(targets)
-        out4, dice_gc, sums = K.ce_dice_fwd(lp, t, lp.shape[3], weight, ignore_index=ignore_index, **rule)
+        out4, index_gc, sums = getattr(K, family + "_fwd")(lp, t, lp.shape[3], weight, ignore_index=ignore_index, **rule)
         ctx.save_for_backward(lp, t, out4, sums)
-        ctx.weight, ctx.rule, ctx.ignore_index = weight, rule, ignore_index
-        ctx.mark_non_differentiable(dice_gc)
-        return out4[0], dice_gc
+        ctx.weight, ctx.family, ctx.rule, ctx.ignore_index = weight, family, rule, ignore_index
+        ctx.mark_non_differentiable(index_gc)
+        return out4[0], index_gc
 
     @staticmethod
     def backward(ctx, g, _):
         lp, t, out4, sums = ctx.saved_tensors
         dl = torch.empty_like(lp)
         g = g.to(torch.float32).contiguous()
-        K.ce_dice_bwd(lp, t, lp.shape[3], out4, sums, dl, weight=ctx.weight, gscale=g, ignore_index=ctx.ignore_index, **ctx.rule)
-        return _nchw(dl), None, None, None, None
+        getattr(K, ctx.family + "_bwd")(lp, t, lp.shape[3], out4, sums, dl, weight=ctx.weight, gscale=g, ignore_index=ctx.ignore_index, **ctx.rule)
+        return _nchw(dl), None, None, None, None, None
 
 
-class CrossEntropyDiceLoss2d(_ClassWeighted):
-    """``ce_coef`` * class-weighted mean cross entropy + ``dice_coef`` * soft Dice loss of the softmax (the rule: include/dct.h,
-    dct_ce_dice_*), in one forward and one backward launch pair.  ``classes``: the class indices of the Dice mean (None: all;
-    ``range(1, C)``: foreground only); ``per_image``: one Dice per image and class instead of one per class over the batch; ``weight``
-    and ``ignore_index`` as on ``CrossEntropyLoss2d``.  After a call ``last_dice`` is the [G, C] device tensor of D_gc of every class
-    (nothing synchronises).  A coefficient of exactly 0 removes its term."""
+class _OverlapLoss2d(_ClassWeighted):
+    """What the overlap criteria share: the class weights, ``classes``, ``smooth``, ``per_image``, ``ignore_index`` and the call.  A
+    family names its hip_ops functions' prefix (``family``), its coefficient (``_coef``) and the attribute that publishes the index table
+    (``_last``), and adds its own parameters to the launch arguments (``_rule_args``)."""
+    family = _coef = _last = None
 
-    def __init__(self, weight=None, ce_coef=1.0, dice_coef=1.0, classes=None, smooth=1e-5, per_image=False, ignore_index=255):
+    def __init__(self, weight, ce_coef, coef, classes, smooth, per_image, ignore_index):
         super().__init__()
+        who = type(self).__name__
         self._set_weight(weight)
-        self.ce_coef, self.dice_coef = float(ce_coef), float(dice_coef)
-        self.classes = None if classes is None else sorted({int(c) for c in classes})
-        if self.classes is not None and not self.classes:
-            raise ValueError(f"dct_amd {type(self).__name__}: classes is empty")
-        if self.classes is not None and self.classes[0] < 0:
-            raise ValueError(f"dct_amd {type(self).__name__}: class {self.classes[0]} is negative")
-        self.smooth = float(smooth)
+        self.ce_coef = _number(ce_coef, "ce_coef", who)
+        setattr(self, self._coef, _number(coef, self._coef, who))
+        self.classes = _class_list(classes, who)
+        self.smooth = _number(smooth, "smooth", who)
         if not (0.0 <= self.smooth < float('inf')):
-            raise ValueError(f"dct_amd {type(self).__name__}: smooth must be finite and >= 0, got {smooth}")
+            raise ValueError(f"dct_amd {who}: smooth must be finite and >= 0, got {smooth!r}")
         self.per_image = bool(per_image)
         self.ignore_index = ignore_index
-        self.last_dice = None
+        setattr(self, self._last, None)
+
+    def _rule_args(self):
+        return {}
 
     def launch_args(self, C):
-        """The keyword arguments of hip_ops.ce_dice_* for logits of ``C`` classes (checks ``classes`` against C)."""
-        if self.classes is not None and self.classes[-1] >= C:
-            raise ValueError(f"dct_amd {type(self).__name__}: class {self.classes[-1]} outside [0, {C})")
-        mask = (1 << C) - 1 if self.classes is None else sum(1 << c for c in self.classes)
-        return dict(class_mask=mask, smooth=self.smooth, per_image=self.per_image, ce_coef=self.ce_coef, dice_coef=self.dice_coef)
+        """The keyword arguments of the family's hip_ops functions for logits of ``C`` classes (checks ``classes`` against C)."""
+        return dict(class_mask=_class_mask(self.classes, C, type(self).__name__), smooth=self.smooth, **self._rule_args(),
+                    per_image=self.per_image, ce_coef=self.ce_coef, **{self._coef: getattr(self, self._coef)})
 
     def forward(self, outputs, targets):
         assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
@@ -310,8 +309,21 @@ class CrossEntropyDiceLoss2d(_ClassWeighted):
             raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
         rule = self.launch_args(outputs.shape[1])
         w = self.device_weight(outputs.device, outputs.shape[1])
-        total, self.last_dice = _CEDiceFn.apply(outputs, targets, w, rule, self.ignore_index)
+        total, index_gc = _OverlapFn.apply(outputs, targets, w, self.family, rule, self.ignore_index)
+        setattr(self, self._last, index_gc)
         return total
+
+
+class CrossEntropyDiceLoss2d(_OverlapLoss2d):
+    """``ce_coef`` * class-weighted mean cross entropy + ``dice_coef`` * soft Dice loss of the softmax (the rule: include/dct.h,
+    dct_ce_dice_*), in one forward and one backward launch pair.  ``classes``: the class indices of the Dice mean (None: all;
+    ``range(1, C)``: foreground only); ``per_image``: one Dice per image and class instead of one per class over the batch; ``weight``
+    and ``ignore_index`` as on ``CrossEntropyLoss2d``.  After a call ``last_dice`` is the [G, C] device tensor of D_gc of every class
+    (nothing synchronises).  A coefficient of exactly 0 removes its term."""
+    family, _coef, _last = "ce_dice", "dice_coef", "last_dice"
+
+    def __init__(self, weight=None, ce_coef=1.0, dice_coef=1.0, classes=None, smooth=1e-5, per_image=False, ignore_index=255):
+        super().__init__(weight, ce_coef, dice_coef, classes, smooth, per_image, ignore_index)
 
 
 class DiceLoss(CrossEntropyDiceLoss2d):
@@ -322,29 +334,6 @@ class DiceLoss(CrossEntropyDiceLoss2d):
         super().__init__(None, 0.0, 1.0, classes, smooth, per_image, ignore_index)
 
 
-class _CETverskyFn(torch.autograd.Function):
-    """``ce_coef`` ce + ``tversky_coef`` tversky on dct_ce_tversky_*; ``rule``: the launch arguments of
-    ``CrossEntropyTverskyLoss2d.launch_args``.  Returns the total and, without a gradient, the [G, C] table of T_gc."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, weight, rule, ignore_index):
-        lp = _pc(logits)
-        t = _targets(targets)
-        out4, tversky_gc, sums = K.ce_tversky_fwd(lp, t, lp.shape[3], weight, ignore_index=ignore_index, **rule)
-        ctx.save_for_backward(lp, t, out4, sums)
-        ctx.weight, ctx.rule, ctx.ignore_index = weight, rule, ignore_index
-        ctx.mark_non_differentiable(tversky_gc)
-        return out4[0], tversky_gc
-
-    @staticmethod
-    def backward(ctx, g, _):
-        lp, t, out4, sums = ctx.saved_tensors
-        dl = torch.empty_like(lp)
-        g = g.to(torch.float32).contiguous()
-        K.ce_tversky_bwd(lp, t, lp.shape[3], out4, sums, dl, weight=ctx.weight, gscale=g, ignore_index=ctx.ignore_index, **ctx.rule)
-        return _nchw(dl), None, None, None, None
-
-
 def _number(value, what, who):
     try:
         return float(value)
@@ -352,7 +341,7 @@ def _number(value, what, who):
         raise ValueError(f"dct_amd {who}: {what} must be a number, got {value!r}")
 
 
-class CrossEntropyTverskyLoss2d(_ClassWeighted):
+class CrossEntropyTverskyLoss2d(_OverlapLoss2d):
     """``ce_coef`` * class-weighted mean cross entropy + ``tversky_coef`` * focal Tversky loss of the softmax (Salehi et al. 2017; Abraham &
     Khan 2019; the rule: include/dct.h, dct_ce_tversky_*), in one forward and one backward launch pair.  Per group and class the index is
     ``T = (I + smooth) / (I + alpha FP + beta FN + smooth)`` and the loss the mean of ``(1 - T)^(1 / gamma)``: ``alpha`` weighs the false
@@ -360,13 +349,12 @@ class CrossEntropyTverskyLoss2d(_ClassWeighted):
     1: plain Tversky) is the focal parameter.  ``classes``, ``smooth``, ``per_image``, ``weight`` and ``ignore_index`` as on
     ``CrossEntropyDiceLoss2d``.  After a call ``last_tversky`` is the [G, C] device tensor of T_gc of every class (nothing synchronises).
     A coefficient of exactly 0 removes its term."""
+    family, _coef, _last = "ce_tversky", "tversky_coef", "last_tversky"
 
     def __init__(self, weight=None, ce_coef=1.0, tversky_coef=1.0, alpha=0.3, beta=0.7, gamma=1.0, classes=None, smooth=1e-5,
                  per_image=False, ignore_index=255):
-        super().__init__()
+        super().__init__(weight, ce_coef, tversky_coef, classes, smooth, per_image, ignore_index)
         who = type(self).__name__
-        self._set_weight(weight)
-        self.ce_coef, self.tversky_coef = _number(ce_coef, "ce_coef", who), _number(tversky_coef, "tversky_coef", who)
         self.alpha, self.beta, self.gamma = _number(alpha, "alpha", who), _number(beta, "beta", who), _number(gamma, "gamma", who)
         for name, v, given in (("alpha", self.alpha, alpha), ("beta", self.beta, beta)):
             if not (0.0 <= v < float('inf')):
@@ -377,27 +365,9 @@ class CrossEntropyTverskyLoss2d(_ClassWeighted):
             raise ValueError(f"dct_amd {who}: alpha + beta must be > 0 and finite in fp32, got {alpha!r}, {beta!r}")
         if not (0.0 < self.gamma < float('inf')) or not (0.0 < g32 < float('inf')):
             raise ValueError(f"dct_amd {who}: gamma must be finite and > 0, got {gamma!r}")
-        self.classes = _class_list(classes, who)
-        self.smooth = _number(smooth, "smooth", who)
-        if not (0.0 <= self.smooth < float('inf')):
-            raise ValueError(f"dct_amd {who}: smooth must be finite and >= 0, got {smooth!r}")
-        self.per_image = bool(per_image)
-        self.ignore_index = ignore_index
-        self.last_tversky = None
 
-    def launch_args(self, C):
-        """The keyword arguments of hip_ops.ce_tversky_* for logits of ``C`` classes (checks ``classes`` against C)."""
-        return dict(class_mask=_class_mask(self.classes, C, type(self).__name__), smooth=self.smooth, alpha=self.alpha, beta=self.beta,
-                    gamma=self.gamma, per_image=self.per_image, ce_coef=self.ce_coef, tversky_coef=self.tversky_coef)
-
-    def forward(self, outputs, targets):
-        assert outputs.dim() == 4 and targets.dim() == 3, (outputs.shape, targets.shape)
-        if not outputs.is_cuda:
-            raise RuntimeError("dct_amd losses run on the HIP device only (no CPU fallback)")
-        rule = self.launch_args(outputs.shape[1])
-        w = self.device_weight(outputs.device, outputs.shape[1])
-        total, self.last_tversky = _CETverskyFn.apply(outputs, targets, w, rule, self.ignore_index)
-        return total
+    def _rule_args(self):
+        return dict(alpha=self.alpha, beta=self.beta, gamma=self.gamma)
 
 
 class FocalTverskyLoss(CrossEntropyTverskyLoss2d):

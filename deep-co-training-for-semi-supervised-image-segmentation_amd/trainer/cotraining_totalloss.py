@@ -115,10 +115,10 @@ class ExecutionPlan:
 class _StepContext(object):
     """What one issue of the step carries from its forward passes to its optimizers; dropped when the step returns (the join closure
     holds this step's streams, the pass buffers' owners its tapes)."""
-    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "ce_dice", "cons", "focal", "topk", "tversky")
+    __slots__ = ("sched", "route", "sync", "join", "early", "pending", "loss_scale", "grad_unscale", "lam_cot", "lam_adv", "g_cot", "g_adv", "ignore", "ce_weight", "cons", "focal", "topk", "overlap")
 
-    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, ce_dice=None, cons=None, focal=None, topk=None,
-                 tversky=None):
+    def __init__(self, sched, route, grad_sync=None, lam=(0.0, 0.0), lam_dev=None, ignore=None, ce_weight=None, cons=None, focal=None, topk=None,
+                 overlap=None):
         self.sched, self.route = sched, route
         # the gradient exchange as far as it is issued from inside the step (between two graphs it is the replay's business)
         self.sync = grad_sync if any(e in ("model", "buckets") for e in route.exchange) else None
@@ -132,11 +132,10 @@ class _StepContext(object):
         self.g_adv = dict(gscale=lam_dev[1:2], gmul=gs) if lam_dev is not None else dict(gmul=lam[1] * gs)
         self.ignore = ignore
         self.ce_weight = ce_weight          # the supervised criterion's fp32 class weights on the device, or None (all ones)
-        self.ce_dice = ce_dice              # a Dice / CE + Dice criterion's launch arguments (CrossEntropyDiceLoss2d.launch_args), or None
         self.cons = cons                    # a view-consistency criterion's (family, launch arguments) (PseudoLabel_2D, SoftPseudoLabel_2D, MSEConsistency_2D), or None: JSD
         self.focal = focal                  # a focal criterion's launch arguments (FocalLoss2d.launch_args), or None
         self.topk = topk                    # a top-k criterion's launch arguments (TopKCrossEntropyLoss2d.launch_args), or None
-        self.tversky = tversky              # a Tversky / focal Tversky / CE + Tversky criterion's launch arguments (CrossEntropyTverskyLoss2d.launch_args), or None
+        self.overlap = overlap              # an overlap criterion's (family, launch arguments) (CrossEntropyDiceLoss2d, CrossEntropyTverskyLoss2d and theirs), or None
 
     def on(self, streams, i):
         """Model i's stream of ``streams`` as the current one (no-op without streams, or for the joint backward of the generic step)."""
@@ -467,8 +466,8 @@ class CoTrainer(Trainer):
         return out[0], _nchw(lp)
 
     def _ce_step(self, ctx, lp, t, dl):
-        """The supervised criterion's value + logit gradient: Dice / CE + Dice (dct_ce_dice_step over the images of ``lp``: [B, H, W, C]),
-        Tversky / focal Tversky / CE + Tversky (dct_ce_tversky_step likewise; the criterion's ``last_tversky`` is set to this launch's table),
+        """The supervised criterion's value + logit gradient: an overlap criterion (dct_ce_dice_step / dct_ce_tversky_step over the images
+        of ``lp``: [B, H, W, C]; a Tversky criterion's ``last_tversky`` is set to this launch's table),
         focal (dct_focal_step, whatever its gamma), top-k (dct_topk_ce_step; the criterion's ``last_topk`` is set), class-weighted when it carries weights (dct_ce_weighted_step), else dct_ce_step."""
         from .. import hip_ops as K
         if ctx.focal is not None:
@@ -477,12 +476,12 @@ class CoTrainer(Trainer):
             out2, counts4, _ = K.topk_ce_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore, **ctx.topk)
             self.criterions['sup'].last_topk = (out2, counts4)
             return out2
-        if ctx.tversky is not None:
-            out4, tversky_gc, _ = K.ce_tversky_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore, **ctx.tversky)
-            self.criterions['sup'].last_tversky = tversky_gc
+        if ctx.overlap is not None:
+            family, rule = ctx.overlap
+            out4, index_gc, _ = getattr(K, family + "_step")(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore, **rule)
+            if family == "ce_tversky":          # (a Dice criterion's last_dice stays its own call's)
+                self.criterions['sup'].last_tversky = index_gc
             return out4
-        if ctx.ce_dice is not None:
-            return K.ce_dice_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore, **ctx.ce_dice)[0]
         if ctx.ce_weight is not None:
             return K.ce_weighted_step(lp, t, self.C, dl, weight=ctx.ce_weight, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
         return K.ce_step(lp, t, self.C, dl, gmul=ctx.loss_scale, ignore_index=ctx.ignore)
@@ -690,15 +689,14 @@ class CoTrainer(Trainer):
         ``lam_dev`` (float32[2] device tensor holding lambda_cot, lambda_adv): the loss weights are then read on the
         device, as a captured graph needs."""
         nets = [s.torchnet for s in self.segmentators]
-        from ..loss.loss import CrossEntropyTverskyLoss2d, FocalLoss2d, TopKCrossEntropyLoss2d
+        from ..loss.loss import FocalLoss2d, TopKCrossEntropyLoss2d, _OverlapLoss2d
         sup, cons = self.criterions['sup'], self.criterions['jsd']
         rule = sup.launch_args(self.C) if hasattr(sup, "launch_args") else None
-        focal, topk, tversky = type(sup) is FocalLoss2d, type(sup) is TopKCrossEntropyLoss2d, isinstance(sup, CrossEntropyTverskyLoss2d)
+        focal, topk, overlap = type(sup) is FocalLoss2d, type(sup) is TopKCrossEntropyLoss2d, isinstance(sup, _OverlapLoss2d)
         ctx = _StepContext(self._sched, route, self.grad_sync, (float(self.cot_scheduler.value), float(self.adv_scheduler.value)),
                            lam_dev, sup.ignore_index, sup.device_weight(self.device, self.C),
-                           None if focal or topk or tversky else rule,
                            (cons.family, cons.launch_args()) if hasattr(cons, "launch_args") else None,   # (JSD_2D has none)
-                           rule if focal else None, rule if topk else None, tversky=rule if tversky else None)
+                           rule if focal else None, rule if topk else None, overlap=(sup.family, rule) if overlap else None)
         streams = self._streams() if route.model_streams else None
         if train_adv and route.kind != "sequential" and step_route.adv_settings(self.adv_training_dict)[0] != 'fgsm':
             raise RuntimeError(f"dct_amd: the {route.kind} layout is scheduled around FGSM; the planner routes other generators sequentially")

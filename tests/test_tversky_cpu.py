@@ -183,7 +183,7 @@ def test_trainer_counts_the_family_as_fused_criteria():
     import inspect
     from dct_amd.trainer import cotraining_totalloss as ct
     params = list(inspect.signature(ct._StepContext.__init__).parameters)
-    assert params[-1] == "tversky" and "tversky" in ct._StepContext.__slots__
+    assert params[-1] == "overlap" and "overlap" in ct._StepContext.__slots__
     src = inspect.getsource(ct.CoTrainer._step_facts)
     for name in ("CrossEntropyTverskyLoss2d", "TverskyLoss", "FocalTverskyLoss"):
         assert name in src

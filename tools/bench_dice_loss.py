@@ -79,7 +79,7 @@ for B, H, C in ((16, 256, 4), (16, 200, 2)):
     fg = (1 << C) - 2
     dl, out2, ws = torch.empty_like(x), torch.empty(2, device=dev), K._loss_ws(dev)
     out4, dgc, sums = torch.empty(4, device=dev), torch.empty(B, C, device=dev), torch.empty(B, C, 3, device=dev)
-    wsd = K._ce_dice_ws(B, C, True, dev)
+    wsd = K._overlap_ws(B, C, True, dev)
     p = K.ptr
 
     def floor():

@@ -39,7 +39,7 @@ for B, H, C in ((8, 256, 4), (8, 200, 2)):
     fg = (1 << C) - 2
     dl, out4 = torch.empty_like(x), torch.empty(4, device=dev)
     gc, sums = torch.empty(B, C, device=dev), torch.empty(B, C, 3, device=dev)
-    ws = K._ce_tversky_ws(B, C, True, dev)
+    ws = K._overlap_ws(B, C, True, dev)
     p, st, call = K.ptr, _lib.stream, _lib.call
     head = (p(x), p(t), B, PPI, C, 255, p(w), fg)
     tail = (p(out4), p(gc), p(sums), None, 1.0, p(dl), 0, p(ws), ws.numel())
